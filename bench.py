@@ -28,6 +28,13 @@ all S sessions take the same LM decisions.  Strong scaling: the job is the same 
 joint solve / max-over-ranks time.  `--chain` instead runs the reference's own semantics of that config on one GPU: the sessions one
 after the other, each starting from the long-term map of its predecessor (ltm_trajectory_sequence_executor.py:45-92).
 
+A plain run sets up, warms up, times the K steps and prints the headline (`metric`, `value`, `unit`, `ms_per_step`, ...).  Everything else
+the line can carry -- per-kernel and roofline figures from instrumented solves, measured peaks, the deterministic-mode leg, the end-to-end
+runs, the CPU oracle baseline and its parity / end-state comparisons, collective latencies, the one-window scaling baseline of N > 1, the
+one-session yardstick of config 5 -- runs only with `--full` (the `--no-*` switches then drop single legs of it).
+`--dump-outputs DIR` writes what the timed path hands back after its last step as DIR/<name>.npy, replayed on a deterministic handle so that the
+same arguments give the same outputs in every run (deterministic_replay); the timed solve and the headline are those of a plain run.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -51,6 +58,46 @@ CONFIGS = {
 }
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 FP64_MATRIX_PEAK_TF = 78.6   # MI355X datasheet FP64 matrix (== FP64 vector) rate; not in the guide's table
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def deterministic_replay(args, obvi_ba, synth, device, prob):
+    """--dump-outputs: the timed path -- upload, symbolic phase, W warm-up steps, K steps -- once more from the same inputs on a deterministic handle
+    (obvi_ba_options.deterministic: fixed-order sums, one stream), outside the timed region, and what that handle hands back written by dump_outputs.
+    The timed default handle adds with fp64 atomics in whatever order the device runs them, and this zero-tolerance problem amplifies that
+    round-off step by step (up to 7e-10 at step 2, 4e-6 at step 4; percent level by step 8), so its own end state differs
+    from run to run; the replay's is the same in every run of the same arguments.  Returns the replay's summary for the JSON line."""
+    bd = obvi_ba.BundleAdjuster(device_id=device, deterministic=True)
+    try:
+        synth.upload(bd, prob)
+        bd.evaluate(True, False)
+        if args.warmup > 0:
+            bd.solve(solver_params(obvi_ba, args.warmup))
+        sd = bd.solve(solver_params(obvi_ba, args.steps))
+        dump_outputs(args.dump_outputs, bd, bd.iterations())
+        return {"handle": "deterministic replay of the timed path (same inputs, warm-up and steps; fixed-order sums)", "steps_done": sd.num_iterations - 1,
+                "final_cost": sd.final_cost, "timed_final_cost": None}
+    finally:
+        bd.close()
+
+
+def dump_outputs(directory, ba, iterations):
+    """--dump-outputs: what a caller of the timed path receives after its last step -- the estimates read back through the C ABI (poses,
+    features, objects) and the cost after every LM iteration of the timed solve -- as float64 DIR/<name>.npy.  A state larger than
+    DUMP_LIMIT_BYTES keeps a fixed, seeded sample of the feature rows (the same rows in every run; their indices in point_rows.npy)."""
+    arrays = {"poses": ba.get_poses(), "points": ba.get_points(), "objects": ba.get_objects(),
+              "iteration_costs": [it.cost for it in iterations]}
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        pts = arrays["points"]
+        row_bytes = pts.itemsize * pts.shape[1] + 8                 # a kept row + its index
+        keep = max(0, (DUMP_LIMIT_BYTES - (total - pts.nbytes)) // row_bytes)
+        rows = np.sort(np.random.default_rng(20241008).choice(len(pts), size=min(keep, len(pts)), replace=False))
+        arrays["points"], arrays["point_rows"] = pts[rows], rows.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def solver_params(obvi_ba, iters):
@@ -737,7 +784,7 @@ def run_sessions(args, torch, obvi_ba, synth, dist_util, rank, local_rank, world
 
     # what one session costs alone on this GPU (no exchange attached: the shared objects are ordinary objects): the serial yardstick of the rank
     alone = None
-    if rank == 0 and not (fused and k_sessions > 1):
+    if args.full and rank == 0 and not (fused and k_sessions > 1):
         handles[0].evaluate(True, False)
         if args.warmup > 0:
             handles[0].solve(solver_params(obvi_ba, args.warmup))
@@ -747,7 +794,7 @@ def run_sessions(args, torch, obvi_ba, synth, dist_util, rank, local_rank, world
         torch.cuda.synchronize()
         alone = 1e3 * (time.perf_counter() - t0) / max(1, sa.num_iterations - 1)
         synth.upload(handles[0], mine[0])
-    if rank == 0 and fused and k_sessions > 1:
+    if args.full and rank == 0 and fused and k_sessions > 1:
         # the yardstick is ONE session: a handle of its own for it
         one = obvi_ba.BundleAdjuster(device_id=local_rank)
         synth.upload(one, first_session)
@@ -782,25 +829,22 @@ def run_sessions(args, torch, obvi_ba, synth, dist_util, rank, local_rank, world
     steps_done = min(sm.num_iterations for sm in summ) - 1
     dt, steps_done = dist_util.reduce_timing(dist, ddev, dt, steps_done)
     issue_order = check_issue_order(comm, dist, dist_util, issue_log, "after the warm-up solve and after the timed solve") if world > 1 else None
-    # device timings: the same steps twice more with events on (every handle runs them: the collectives need all contributors); rank 0 reads session 0
-    for ba in handles:
-        ba.set_profiling(1)
-    k0 = handles[0].kernel_times()
-    in_threads(lambda m: handles[m].solve(solver_params(obvi_ba, args.steps)))
-    k1 = handles[0].kernel_times()
-    for ba in handles:
-        ba.set_profiling(2)
-    p0 = handles[0].kernel_times()
-    in_threads(lambda m: handles[m].solve(solver_params(obvi_ba, args.steps)))
-    p1 = handles[0].kernel_times()
-    for ba in handles:
-        ba.set_profiling(0)
+    # --full: device timings, the same steps twice more with events on (every handle runs them: the collectives need all contributors); rank 0 reads session 0
+    if args.full:
+        for ba in handles:
+            ba.set_profiling(1)
+        k0 = handles[0].kernel_times()
+        in_threads(lambda m: handles[m].solve(solver_params(obvi_ba, args.steps)))
+        k1 = handles[0].kernel_times()
+        for ba in handles:
+            ba.set_profiling(2)
+        p0 = handles[0].kernel_times()
+        in_threads(lambda m: handles[m].solve(solver_params(obvi_ba, args.steps)))
+        p1 = handles[0].kernel_times()
+        for ba in handles:
+            ba.set_profiling(0)
     if rank == 0:
         pst = handles[0].problem_stats()
-        peaks = handles[0].measure_peaks()
-        table, phases = kernel_table(pst, (k0, k1), (p0, p1), peaks)
-        dom = max(table, key=lambda kk: table[kk]["ms_per_step"])
-        d = table[dom]
         ntail = -(-7 * n_obj // 64)
         submissions = steps_done + 1                                    # every LM step + the linearisation-only submission behind the last one
         sizes = {"shared_blocks": 8 * 56 * n_obj, "shared_tail": 8 * (ntail * (ntail + 1) // 2 * 64 * 64 + ntail * 64), "scalars": 8 * (9 + S)}
@@ -826,19 +870,27 @@ def run_sessions(args, torch, obvi_ba, synth, dist_util, rank, local_rank, world
                        "final_cost_per_session": [sm.final_cost for sm in summ] * (k_sessions if fused else 1), "termination": summ[0].message.decode()},
             "value_note": "value = sessions x LM iterations of the joint solve / max-over-ranks seconds (every session advances one iteration per joint step; config 4 counts "
                           "its windows the same way); ms_per_step = one JOINT LM step of all %d sessions" % S,
-            "concurrency": {"one_session_alone_ms_per_step": round(alone, 4), "sessions_on_this_gpu": k_sessions, "joint_ms_per_step": round(ms_step, 4),
-                            "speedup_vs_serial": round(k_sessions * alone / ms_step, 3),
-                            "note": "the k sessions of this GPU solved jointly (fused into one problem, or k handles in k host threads with --group) against k x ONE session solved "
-                                    "alone, no exchange: what putting window-sized solves together buys on a device that one of them leaves mostly idle"},
-            "roofline": {"kernel": dom, "bound": d.get("bound", "hbm"), "achieved": d.get("achieved"), "peak": HBM_PEAK_GBS if d.get("bound", "hbm") == "hbm" else FP64_MATRIX_PEAK_TF,
-                         "unit": d.get("unit", "GB/s"), "frac": d.get("frac"), "frac_measured": d.get("frac_measured"), "traffic": None, "avg_launch_us": d["avg_us"],
-                         "peaks_measured": {kk: round(v, 2) for kk, v in peaks.items()},
-                         "note": "dominant kernel of session 0 on rank 0 by device time per LM step, HIP events in an instrumented solve of the same steps while the rank's other "
-                                 "sessions run beside it (their kernels share the device: launch durations include that); traffic: no PMC pass for this workload"},
-            "kernels": dict(sorted(table.items(), key=lambda kv: -kv[1]["ms_per_step"])),
-            "host": {"upload_ms_all_sessions": round(upload_ms, 1), "symbolic_phase_ms_all_sessions_concurrently": round(symbolic_ms, 1)},
         }
-        if not args.no_cpu_baseline:
+        if args.full:
+            peaks = handles[0].measure_peaks()
+            table, phases = kernel_table(pst, (k0, k1), (p0, p1), peaks)
+            dom = max(table, key=lambda kk: table[kk]["ms_per_step"])
+            d = table[dom]
+            out["concurrency"] = {"one_session_alone_ms_per_step": round(alone, 4), "sessions_on_this_gpu": k_sessions, "joint_ms_per_step": round(ms_step, 4),
+                                  "speedup_vs_serial": round(k_sessions * alone / ms_step, 3),
+                                  "note": "the k sessions of this GPU solved jointly (fused into one problem, or k handles in k host threads with --group) against k x ONE session solved "
+                                          "alone, no exchange: what putting window-sized solves together buys on a device that one of them leaves mostly idle"}
+            out["roofline"] = {"kernel": dom, "bound": d.get("bound", "hbm"), "achieved": d.get("achieved"), "peak": HBM_PEAK_GBS if d.get("bound", "hbm") == "hbm" else FP64_MATRIX_PEAK_TF,
+                               "unit": d.get("unit", "GB/s"), "frac": d.get("frac"), "frac_measured": d.get("frac_measured"), "traffic": None, "avg_launch_us": d["avg_us"],
+                               "peaks_measured": {kk: round(v, 2) for kk, v in peaks.items()},
+                               "note": "dominant kernel of session 0 on rank 0 by device time per LM step, HIP events in an instrumented solve of the same steps while the rank's other "
+                                       "sessions run beside it (their kernels share the device: launch durations include that); traffic: no PMC pass for this workload"}
+            out["kernels"] = dict(sorted(table.items(), key=lambda kv: -kv[1]["ms_per_step"]))
+        out["host"] = {"upload_ms_all_sessions": round(upload_ms, 1), "symbolic_phase_ms_all_sessions_concurrently": round(symbolic_ms, 1)}
+        if args.dump_outputs:
+            out["dump"] = deterministic_replay(args, obvi_ba, synth, local_rank, mine[0])
+            out["dump"]["timed_final_cost"] = summ[0].final_cost
+        if args.full and not args.no_cpu_baseline:
             q0 = dict(mine[0])
             base_line = cpu_baseline(q0, legs={})
             if base_line is not None:
@@ -864,36 +916,47 @@ def run_session_chain(args, torch, obvi_ba, synth, S):
     cfg = CONFIGS[5]
     prm = obvi_ba.SolverParams(max_num_iterations=50, allow_non_monotonic_steps=True, function_tolerance=1e-4, gradient_tolerance=1e-10,
                                parameter_tolerance=1e-8, initial_trust_region_radius=100.0, max_trust_region_radius=1e4)
+    def chain(g):
+        ltm, rows, iters, t_all = None, [], 0, 0.0
+        for sidx in range(S):
+            prob = synth.make_problem(P=cfg["P"], L=cfg["L"], O=cfg["O"], seed=1000 + sidx, object_seed=77, const_poses=1, min_obj_obs=10, object_classes=("bench",))
+            if ltm is not None:
+                prob["objects"][ltm[0]] = ltm[1]
+                prob.update(lt_obj=ltm[0].astype(np.uint32), lt_mean=ltm[1], lt_cov=ltm[2].reshape(-1, 49), lt_huber=1.0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            synth.upload(g, prob)
+            s1 = g.solve(prm)
+            mask, _ = g.select_outliers(0, 0.1)
+            g.set_active_mask(0, mask)
+            s2 = g.solve(prm)
+            g.set_active_mask(0, np.ones_like(mask))
+            ids = np.arange(len(prob["objects"]), dtype=np.uint32)
+            cov = g.object_covariances(ids)
+            est = g.get_objects()
+            dt = time.perf_counter() - t0
+            seen = np.abs(cov).max(axis=(1, 2)) > 0
+            err = np.linalg.norm(est[seen, :3] - prob["gt_objects"][seen, :3], axis=1)
+            rows.append({"session": sidx, "ms": round(1e3 * dt, 2), "lm_iterations": int(s1.num_iterations + s2.num_iterations - 2), "objects_mapped": int(seen.sum()),
+                         "centre_error_median_m": round(float(np.median(err)), 4)})
+            iters += s1.num_iterations + s2.num_iterations - 2
+            t_all += dt
+            ltm = (ids[seen], est[seen], cov[seen])
+        return rows, iters, t_all, s2
+
     g = obvi_ba.BundleAdjuster(device_id=0)
-    ltm, rows, iters, t_all = None, [], 0, 0.0
-    for sidx in range(S):
-        prob = synth.make_problem(P=cfg["P"], L=cfg["L"], O=cfg["O"], seed=1000 + sidx, object_seed=77, const_poses=1, min_obj_obs=10, object_classes=("bench",))
-        if ltm is not None:
-            prob["objects"][ltm[0]] = ltm[1]
-            prob.update(lt_obj=ltm[0].astype(np.uint32), lt_mean=ltm[1], lt_cov=ltm[2].reshape(-1, 49), lt_huber=1.0)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        synth.upload(g, prob)
-        s1 = g.solve(prm)
-        mask, _ = g.select_outliers(0, 0.1)
-        g.set_active_mask(0, mask)
-        s2 = g.solve(prm)
-        g.set_active_mask(0, np.ones_like(mask))
-        ids = np.arange(len(prob["objects"]), dtype=np.uint32)
-        cov = g.object_covariances(ids)
-        est = g.get_objects()
-        dt = time.perf_counter() - t0
-        seen = np.abs(cov).max(axis=(1, 2)) > 0
-        err = np.linalg.norm(est[seen, :3] - prob["gt_objects"][seen, :3], axis=1)
-        rows.append({"session": sidx, "ms": round(1e3 * dt, 2), "lm_iterations": int(s1.num_iterations + s2.num_iterations - 2), "objects_mapped": int(seen.sum()),
-                     "centre_error_median_m": round(float(np.median(err)), 4)})
-        iters += s1.num_iterations + s2.num_iterations - 2
-        t_all += dt
-        ltm = (ids[seen], est[seen], cov[seen])
+    rows, iters, t_all, last = chain(g)
+    dump = None
+    if args.dump_outputs:          # the same chain on a deterministic handle (deterministic_replay), its last session's state written out
+        gd = obvi_ba.BundleAdjuster(device_id=0, deterministic=True)
+        _, _, _, last_d = chain(gd)
+        dump_outputs(args.dump_outputs, gd, gd.iterations())
+        dump = {"handle": "deterministic replay of the timed chain (fixed-order sums)", "final_cost": last_d.final_cost, "timed_final_cost": last.final_cost}
+        gd.close()
     print(json.dumps({"metric": "local-BA LM iterations/s (sessions chained through the long-term map)", "value": iters / t_all, "unit": "LM iterations/s", "n_gpus": 1,
                       "steps": S, "warmup": 0, "ms_per_step": 1e3 * t_all / S, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
                       "config": {"workload": "config 5 (chain): %d sessions x (500 KF / 50k features) over one 200-object map, one after the other through the long-term map" % S,
-                                 "sessions": S, "step": "one session: upload + two-phase BA + map extraction"}, "sessions": rows}))
+                                 "sessions": S, "step": "one session: upload + two-phase BA + map extraction"}, "sessions": rows, "dump": dump}))
 
 
 def main():
@@ -911,10 +974,18 @@ def main():
     ap.add_argument("--windows-per-gpu", type=int, default=0, help="config 4: K windows per GPU, all sharing the object set, behind the group hook (0: the one-window-per-GPU path)")
     ap.add_argument("--group", action="store_true", help="config 5 / config 4 --windows-per-gpu: one handle per session behind obvi_rccl_group_* instead of fusing a rank's sessions into one problem")
     ap.add_argument("--chain", action="store_true", help="config 5 the reference's way: sessions one after the other through the long-term map, one GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-deterministic-leg", action="store_true", help="skip the deterministic-mode timing of the same steps")
-    ap.add_argument("--no-end-to-end", action="store_true", help="skip the end-to-end two-phase global BA (config 3, one GPU; about 2 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: instrumented solves (per-kernel table, roofline, measured peaks), collective latencies, the scaling / one-session "
+                         "yardsticks, the deterministic-mode leg, the end-to-end runs and the CPU oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path hands back after its last step as DIR/<name>.npy, replayed on a deterministic handle outside the timed "
+                         "region so that the same arguments give the same outputs in every run (one GPU)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-deterministic-leg", action="store_true", help="with --full: skip the deterministic-mode timing of the same steps")
+    ap.add_argument("--no-end-to-end", action="store_true", help="with --full: skip the end-to-end two-phase global BA (config 3, one GPU; about 2 s)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or args.group):
+        ap.error("--dump-outputs replays the timed path on one deterministic handle: one GPU, sessions fused (no --group)")
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -977,7 +1048,7 @@ def main():
     scaling_baseline = None
     rccl_versions = None
     issue_log = dist_util.IssueLog()
-    if shared:
+    if shared and args.full:
         # the N = 1 point of THIS workload (the driver's N = 1 run is the config-3 headline, another problem): every rank solves its own
         # window alone -- no exchange attached yet, shared objects are ordinary objects -- for the same steps, before the group solve
         ba.evaluate(True, False)
@@ -1031,12 +1102,14 @@ def main():
     dt = time.perf_counter() - t0
     ba_timed_iterations = ba.iterations()
     steps_done = summ.num_iterations - 1
+    if steps_done != args.steps and rank == 0:
+        print("bench.py: the timed solve ended after %d of %d LM steps (%s)" % (steps_done, args.steps, summ.message.decode()), file=sys.stderr)
     dt, steps_done = dist_util.reduce_timing(dist, ddev, dt, steps_done)
     # one communicator, two streams (first collective of a step on the side stream, the other two on the main stream): legal only if every rank
     # issues the same collectives in the same host order -- compared here, after the timed solve
     issue_order = check_issue_order(comm, dist, dist_util, issue_log, "after the warm-up solve and after the timed solve") if shared else None
-    collectives_us = collective_latency(torch, ba, comm, dist, args, prob, world) if shared else None
-    if world == 1 and rank == 0:
+    collectives_us = collective_latency(torch, ba, comm, dist, args, prob, world) if shared and args.full else None
+    if world == 1 and rank == 0 and args.full:
         # the latency budget of the exchange is needed BEFORE eight ranks exist: the three per-step sizes of config 4 and of
         # config 5 on a ONE-rank communicator of libobvi_rccl.so -- what RCCL's launch path costs per collective before any byte crosses xGMI
         try:
@@ -1049,51 +1122,24 @@ def main():
         except Exception as e:                  # noqa: BLE001 -- a diagnostic: never fails the bench
             collectives_us = "unavailable: %r" % (e,)
 
-    # Device timings come from two more solves of the same K steps, outside the timed region (the timed solve records no
+    # --full: device timings come from two more solves of the same K steps, outside the timed region (the timed solve records no
     # events at all): level 1 = one HIP event pair per phase of an LM step, same schedule as the timed solve (side stream on);
     # level 2 = additionally an event after every launch of the tile Cholesky (single stream, costs a few percent).
-    ba.set_profiling(1)
-    k0 = ba.kernel_times()
-    ba.solve(solver_params(obvi_ba, args.steps))
-    k1 = ba.kernel_times()
-    ba.set_profiling(2)
-    p0 = ba.kernel_times()
-    ba.solve(solver_params(obvi_ba, args.steps))
-    p1 = ba.kernel_times()
-    ba.set_profiling(0)
+    if args.full:
+        ba.set_profiling(1)
+        k0 = ba.kernel_times()
+        ba.solve(solver_params(obvi_ba, args.steps))
+        k1 = ba.kernel_times()
+        ba.set_profiling(2)
+        p0 = ba.kernel_times()
+        ba.solve(solver_params(obvi_ba, args.steps))
+        p1 = ba.kernel_times()
+        ba.set_profiling(0)
 
     det_first = None
     if rank == 0:
         pst = ba.problem_stats()
-        n_r, n_b = pst["reproj_active"], pst["bbox_active"]
-        peaks = ba.measure_peaks()   # triad / copy / read GB/s and the fp64 MFMA rates of THIS device (obvi_ba_measure_peaks)
-        table, phases = kernel_table(pst, (k0, k1), (p0, p1), peaks)
-        dom = max(table, key=lambda k: table[k]["ms_per_step"])
-        d = table[dom]
-        man, stale = profile_manifest()
-        fresh = man if stale is None else None
-        roof = {"kernel": dom, "bound": d.get("bound", "hbm"), "achieved": d.get("achieved"), "peak": HBM_PEAK_GBS if d.get("bound", "hbm") == "hbm" else FP64_MATRIX_PEAK_TF,
-                "unit": d.get("unit", "GB/s"), "frac": d.get("frac"),
-                "peak_measured": round(peaks["hbm_triad_gbs"] if d.get("bound", "hbm") == "hbm" else peaks["mfma_f64_issue_tflops"], 2), "frac_measured": d.get("frac_measured"),
-                "peaks_measured": {k: round(v, 2) for k, v in peaks.items()},
-                "traffic": pmc_traffic(dom, fresh),
-                "avg_launch_us": d["avg_us"], "launches_per_step": d["launches_per_step"], "rocprof_avg_us": rocprof_avg_us(dom, fresh), "sq": sq_counters(dom, fresh),
-                "profiles": {"tag": man.get("tag") if man else None, "kernel_source_sha": man.get("kernel_source_sha") if man else None, "stale": stale},
-                "note": "peak = public figure (HBM3E 8 TB/s; fp64 matrix 78.6 TFLOP/s), peak_measured = obvi_ba_measure_peaks in THIS run (HBM: triad over 3 x 1 GiB; "
-                        "MFMA: issue rate of v_mfma_f64_16x16x4_f64 with register operands; peaks_measured also has copy / read and the LDS-fed 64x64x64 tile product). "
-                        "dominant kernel by device time per LM step; achieved / frac from HIP events around every launch (they include the launch "
-                        "boundary, about 3 us) in an instrumented solve of the same steps in THIS run; traffic, rocprof_avg_us and sq come from the "
-                        "rocprofv3 passes committed under profiles/ and are null when profiles/manifest.json was not measured on the kernel sources "
-                        "this run uses (profiles.stale says why)"}
         ms_step = 1e3 * dt / max(steps_done, 1)
-        alg_step = n_r * 496.0 + n_b * 1008.0             # B_step without B_S
-        pmc_step = pmc_step_bytes(fresh, table)
-        roof["step"] = {"alg_bytes": alg_step, "pmc_bytes": pmc_step, "ms": round(ms_step, 4),
-                        "achieved_gbs": round(alg_step / (ms_step * 1e-3) / 1e9, 1),
-                        "frac_of_peak": round(alg_step / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                        "frac_of_measured": round(alg_step / (ms_step * 1e-3) / 1e9 / peaks["hbm_triad_gbs"], 4),
-                        "note": "whole LM step: algorithmic bytes N_r 496 + N_b 1008 (SURVEY 8d) over the TIMED ms per step, against the 8 TB/s public figure and the "
-                                "triad measured in this run; pmc_bytes = sum over the step's launches of the committed FETCH/WRITE passes (null when stale)"}
         out = {
             "metric": "global-BA LM iterations/s" if not cfg.get("shared") else "local-BA LM iterations/s (windows sharing objects)", "value": dist_util.aggregate_throughput(world, steps_done, dt), "unit": "LM iterations/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / max(steps_done, 1),
@@ -1113,17 +1159,50 @@ def main():
                        "potrf_wait_timeouts": int(ba.problem_stats().get("potrf_wait_timeouts", 0)), "fused_potrf_schedule": bool(ba.problem_stats().get("fused_potrf", 1)),
                        "accepted_steps": int(sum(1 for it in ba_timed_iterations[1:] if it.step_is_successful)),
                        "rejected_or_invalid_steps": int(sum(1 for it in ba_timed_iterations[1:] if not it.step_is_successful))},
-            "roofline": roof,
-            "kernels": dict(sorted(table.items(), key=lambda kv: -kv[1]["ms_per_step"])),
-            "phases_ms_avg": {k: round(v["ms_avg"], 4) for k, v in phases.items()},
-            # once per problem, outside the timed region: host -> device upload through the binding, and the host's symbolic phase
-            "host": {"upload_ms": round(upload_ms, 1), "symbolic_phase_ms": round(symbolic_ms, 1), "host_threads_used": int(pst.get("host_threads", 0)),
-                     "usable_cpus": int(pst.get("usable_cpus", 0)), "cpu_count": os.cpu_count(), "numa_node_of_caller": numa_node_of_caller()},
         }
+        if args.full:
+            n_r, n_b = pst["reproj_active"], pst["bbox_active"]
+            peaks = ba.measure_peaks()   # triad / copy / read GB/s and the fp64 MFMA rates of THIS device (obvi_ba_measure_peaks)
+            table, phases = kernel_table(pst, (k0, k1), (p0, p1), peaks)
+            dom = max(table, key=lambda k: table[k]["ms_per_step"])
+            d = table[dom]
+            man, stale = profile_manifest()
+            fresh = man if stale is None else None
+            roof = {"kernel": dom, "bound": d.get("bound", "hbm"), "achieved": d.get("achieved"), "peak": HBM_PEAK_GBS if d.get("bound", "hbm") == "hbm" else FP64_MATRIX_PEAK_TF,
+                    "unit": d.get("unit", "GB/s"), "frac": d.get("frac"),
+                    "peak_measured": round(peaks["hbm_triad_gbs"] if d.get("bound", "hbm") == "hbm" else peaks["mfma_f64_issue_tflops"], 2), "frac_measured": d.get("frac_measured"),
+                    "peaks_measured": {k: round(v, 2) for k, v in peaks.items()},
+                    "traffic": pmc_traffic(dom, fresh),
+                    "avg_launch_us": d["avg_us"], "launches_per_step": d["launches_per_step"], "rocprof_avg_us": rocprof_avg_us(dom, fresh), "sq": sq_counters(dom, fresh),
+                    "profiles": {"tag": man.get("tag") if man else None, "kernel_source_sha": man.get("kernel_source_sha") if man else None, "stale": stale},
+                    "note": "peak = public figure (HBM3E 8 TB/s; fp64 matrix 78.6 TFLOP/s), peak_measured = obvi_ba_measure_peaks in THIS run (HBM: triad over 3 x 1 GiB; "
+                            "MFMA: issue rate of v_mfma_f64_16x16x4_f64 with register operands; peaks_measured also has copy / read and the LDS-fed 64x64x64 tile product). "
+                            "dominant kernel by device time per LM step; achieved / frac from HIP events around every launch (they include the launch "
+                            "boundary, about 3 us) in an instrumented solve of the same steps in THIS run; traffic, rocprof_avg_us and sq come from the "
+                            "rocprofv3 passes committed under profiles/ and are null when profiles/manifest.json was not measured on the kernel sources "
+                            "this run uses (profiles.stale says why)"}
+            alg_step = n_r * 496.0 + n_b * 1008.0             # B_step without B_S
+            pmc_step = pmc_step_bytes(fresh, table)
+            roof["step"] = {"alg_bytes": alg_step, "pmc_bytes": pmc_step, "ms": round(ms_step, 4),
+                            "achieved_gbs": round(alg_step / (ms_step * 1e-3) / 1e9, 1),
+                            "frac_of_peak": round(alg_step / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                            "frac_of_measured": round(alg_step / (ms_step * 1e-3) / 1e9 / peaks["hbm_triad_gbs"], 4),
+                            "note": "whole LM step: algorithmic bytes N_r 496 + N_b 1008 (SURVEY 8d) over the TIMED ms per step, against the 8 TB/s public figure and the "
+                                    "triad measured in this run; pmc_bytes = sum over the step's launches of the committed FETCH/WRITE passes (null when stale)"}
+            out["roofline"] = roof
+            out["kernels"] = dict(sorted(table.items(), key=lambda kv: -kv[1]["ms_per_step"]))
+            out["phases_ms_avg"] = {k: round(v["ms_avg"], 4) for k, v in phases.items()}
+        # once per problem, outside the timed region: host -> device upload through the binding, and the host's symbolic phase
+        out["dump"] = None
+        if args.dump_outputs:
+            out["dump"] = deterministic_replay(args, obvi_ba, synth, local_rank, prob)
+            out["dump"]["timed_final_cost"] = summ.final_cost
+        out["host"] = {"upload_ms": round(upload_ms, 1), "symbolic_phase_ms": round(symbolic_ms, 1), "host_threads_used": int(pst.get("host_threads", 0)),
+                       "usable_cpus": int(pst.get("usable_cpus", 0)), "cpu_count": os.cpu_count(), "numa_node_of_caller": numa_node_of_caller()}
         if scaling_baseline is not None:
             out["scaling_baseline"] = scaling_baseline
             out["weak_scaling_efficiency"] = round(out["value"] / (world * scaling_baseline["value_one_gpu"]), 4)
-        if world == 1 and not args.no_deterministic_leg:
+        if args.full and world == 1 and not args.no_deterministic_leg:
             # the same steps in deterministic mode (obvi_ba_options.deterministic: fixed-order sums, one stream; for parity runs)
             bd = obvi_ba.BundleAdjuster(device_id=local_rank, deterministic=True)
             synth.upload(bd, prob)
@@ -1143,12 +1222,12 @@ def main():
                                          # ill-conditioned problem amplifies it (zero tolerances, non-monotonic steps: a chaotic trajectory)
                                          "cost_rel_diff_vs_default": {"after_step_%d" % k: abs(its_d[k].cost - its_0[k].cost) / its_0[k].cost for k in (1, 2, 4, 8, len(its_0) - 1) if k < min(len(its_d), len(its_0))}}
             bd.close()
-        if world == 1 and args.config == 3 and not args.no_end_to_end:
+        if args.full and world == 1 and args.config == 3 and not args.no_end_to_end:
             out["end_to_end"] = end_to_end_global_ba(obvi_ba, synth, prob, local_rank)
             out["end_to_end_cpp"] = end_to_end_cpp(prob, local_rank)
             out["sliding_window_session_cpp"] = sliding_window_session_cpp(synth, local_rank)
             out["concurrent_sessions_cpp"] = concurrent_sessions_cpp(synth, local_rank)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             legs = {}
             if world == 1:
                 synth.upload(ba, prob)

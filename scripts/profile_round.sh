@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (on the GPU box, from the repo root): scripts/profile_round.sh <tag>
 # Everything the judge needs to recompute the bench line's roofline from files: written under gpurun_out/<tag>/ (copy to profiles/):
-#   <tag>_bench_cfg3.json            the bench line (python bench.py, defaults)
+#   <tag>_bench_cfg3.json            the bench line (python bench.py --full, defaults otherwise)
 #   <tag>_kernel_stats_cfg3.csv      rocprofv3 --kernel-trace --stats of the same command
 #   <tag>_pmc_fetch.csv / _write.csv FETCH_SIZE and WRITE_SIZE, separate counter-only passes (MI355X_MICROARCH.md "HBM")
 #   <tag>_pmc_traffic.json           per-kernel HBM bytes per launch (scripts/pmc_summary.py: corrections documented there)
@@ -15,7 +15,7 @@ SHA=$(python3 $R/scripts/source_sha.py)
 cd /tmp && export TMPDIR=/tmp
 # (the legs of the default command that are not the timed workload -- CPU baseline, deterministic-mode comparison, end-to-end two-phase run -- are
 #  switched off under the profiler, so that a kernel's average is over the launches of the timed configuration only)
-LEGS="--no-cpu-baseline --no-deterministic-leg --no-end-to-end"
+LEGS="--full --no-cpu-baseline --no-deterministic-leg --no-end-to-end"
 rm -rf /tmp/pr_trace; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pr_trace -o cfg3 -- python $R/bench.py $LEGS > $OUT/${TAG}_bench_cfg3_under_rocprof.json 2> $OUT/rocprof.err
 cp $(find /tmp/pr_trace -name "*kernel_stats.csv" | head -1) $OUT/${TAG}_kernel_stats_cfg3.csv
 for C in FETCH_SIZE WRITE_SIZE; do
@@ -66,7 +66,7 @@ json.dump({"tag": tag, "kernel_source_sha": sha, "files": {"bench": tag + "_benc
           open(os.path.join(out, "manifest.json"), "w"), indent=1)
 PY
 cp $OUT/manifest.json $OUT/${TAG}_kernel_stats_cfg3.csv $OUT/${TAG}_pmc_traffic.json $OUT/${TAG}_sq_counters.json $R/profiles/ 2>/dev/null
-timeout 900 python $R/bench.py > $OUT/${TAG}_bench_cfg3.json 2> $OUT/bench.err
+timeout 900 python $R/bench.py --full > $OUT/${TAG}_bench_cfg3.json 2> $OUT/bench.err
 python3 - $OUT $TAG $SHA <<'PY'
 import json, os, subprocess, sys
 out, tag, sha = sys.argv[1:4]

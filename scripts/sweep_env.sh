@@ -3,7 +3,7 @@
 VAR=$1; VALS=$2; shift 2
 for v in $VALS; do
   export $VAR=$v
-  python bench.py --steps 6 --warmup 1 --no-cpu-baseline 2>/dev/null | grep metric | python -c "
+  python bench.py --full --steps 6 --warmup 1 --no-cpu-baseline 2>/dev/null | grep metric | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d['kernels']
 names=sys.argv[2:] or list(k)

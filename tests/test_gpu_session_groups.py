@@ -207,7 +207,7 @@ def test_bench_config5_two_ranks_oversubscribed(mode):
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--gpus", "2", "--config", "5", "--sessions", "4", "--oversubscribe", "--steps", "3", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--gpus", "2", "--config", "5", "--sessions", "4", "--oversubscribe", "--full", "--steps", "3", "--warmup", "1",
                           "--no-cpu-baseline"] + (["--group"] if mode == "group" else []), capture_output=True, text=True, timeout=1500, env=env)
     assert out.returncode == 0, out.stderr[-4000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -251,7 +251,7 @@ def test_bench_config5_chain_and_config4_windows_per_gpu():
     chain = _bench_line(["--config", "5", "--chain", "--sessions", "2"])
     assert "chain" in chain["config"]["workload"] and chain["steps"] == 2 and len(chain["sessions"]) == 2 and chain["value"] > 0
     assert all(r["objects_mapped"] > 100 and r["lm_iterations"] > 0 for r in chain["sessions"])
-    win = _bench_line(["--config", "4", "--windows-per-gpu", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"])
+    win = _bench_line(["--config", "4", "--windows-per-gpu", "2", "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"])
     cfg = win["config"]
     assert "config 4" in cfg["workload"] and cfg["sessions"] == 2 and cfg["sessions_per_rank"] == 2 and cfg["handles_per_rank"] == 1 and cfg["objects"] == 25
     assert win["scaling"] == "strong" and cfg["steps_done"] == 3 and win["concurrency"]["sessions_on_this_gpu"] == 2 and win["concurrency"]["speedup_vs_serial"] > 0.8

@@ -448,7 +448,7 @@ def test_bench_two_ranks_oversubscribed():
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--gpus", "2", "--oversubscribe", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--gpus", "2", "--oversubscribe", "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=1500, env=env)
     assert out.returncode == 0, out.stderr[-4000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -466,11 +466,13 @@ def test_bench_two_ranks_oversubscribed():
 
 
 @pytest.mark.parametrize("config", [4, 5])
-def test_bench_eight_ranks_oversubscribed(config):
-    """The command line the driver runs on an eight-GPU node -- `bench.py --gpus 8` -- with all eight ranks on this one GPU (`--oversubscribe`: process group gloo, the
-    three collectives staged through the host): config 4 (eight 500-keyframe windows sharing 25 objects) and config 5 (sixteen sessions over one 200-object map, two
-    fused per rank).  A smoke test of the WHOLE N = 8 path -- self-spawn, seeds, uploads, the scaling baseline, three collectives per step in the same order on every
-    rank, the time limit around them, the reduction of the timings, the one JSON line -- not a timing (DESIGN section 8 used to say "run by hand")."""
+def test_bench_four_ranks_oversubscribed(config):
+    """The N > 2 command line of both shared-object workloads -- `bench.py --gpus 4` -- with all four ranks on this one GPU (`--oversubscribe`: process group gloo, the
+    three collectives staged through the host): config 4 (four 500-keyframe windows sharing 25 objects) and config 5 (eight sessions over one 200-object map, two
+    fused per rank, as on an eight-GPU node), both with `--full`.  A smoke test of the WHOLE N > 2 path -- self-spawn, seeds, uploads, the scaling baseline / the
+    one-session yardstick, three collectives per step in the same order on every rank, the time limit around them, the reduction of the timings, the instrumented
+    solves, the one JSON line -- not a timing (DESIGN section 8 used to say "run by hand").  Four ranks rather than eight: eight ranks and this
+    process put nine processes on the one device, more than the machines the suite runs on allow at once."""
     import json
     import os
     import subprocess
@@ -478,20 +480,22 @@ def test_bench_eight_ranks_oversubscribed(config):
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--gpus", "8", "--oversubscribe", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--config", str(config)]
+    cmd = [sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--gpus", "4", "--oversubscribe", "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--config", str(config)]
+    cmd += ["--sessions", "8"] if config == 5 else []                                      # two fused sessions per rank, the split of eight ranks x sixteen sessions
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1700, env=env)
     assert out.returncode == 0, out.stderr[-4000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
     line = json.loads(lines[0])
     cfg = line["config"]
-    assert line["n_gpus"] == 8 and line["steps"] == 2 and line["scaling"] == ("weak" if config == 4 else "strong") and line["value"] > 0   # config 5: sixteen sessions whatever the rank count
-    assert cfg["rccl_ranks"] == 8 and cfg["oversubscribed"] and cfg["steps_done"] == 2
+    assert line["n_gpus"] == 4 and line["steps"] == 2 and line["scaling"] == ("weak" if config == 4 else "strong") and line["value"] > 0
+    assert cfg["rccl_ranks"] == 4 and cfg["oversubscribed"] and cfg["steps_done"] == 2
     assert cfg["collective_issue_order"]["same_on_every_rank"] and cfg["collective_issue_order"]["collectives_issued"] >= 3 * 2
     if config == 5:
-        assert cfg["sessions"] == 16 and cfg["sessions_per_rank"] == 2
+        assert cfg["sessions"] == 8 and cfg["sessions_per_rank"] == 2
+        assert line["concurrency"]["sessions_on_this_gpu"] == 2 and line["concurrency"]["one_session_alone_ms_per_step"] > 0 and line["roofline"]["kernel"]
     if config == 4:
-        assert len(line["scaling_baseline"]["per_rank_value"]) == 8                      # (config 5 is a strong-scaling workload: no one-window baseline)
+        assert len(line["scaling_baseline"]["per_rank_value"]) == 4                      # (config 5 is a strong-scaling workload: no one-window baseline)
 
 
 def test_rccl_rendezvous_file(tmp_path, monkeypatch):
