@@ -11,6 +11,59 @@ int handle_fail(obvi_ba_handle* h, int code, const char* msg) { return fail(h, c
 void make_dev_cam(const double* K4, const double* ext7, DevCam* out) { make_cam(K4, ext7, out); }
 }  // namespace obvi
 
+namespace obvi_lib {
+
+// The only reader of the library's tuning knobs (ba_handle.h); obvi_ba_create calls it once per handle.
+Knobs read_knobs() {
+  Knobs k;
+  auto set_int = [](const char* name, int& field) { if (const char* v = std::getenv(name)) field = std::atoi(v); };
+  auto set_i64 = [](const char* name, int64_t& field) { if (const char* v = std::getenv(name)) field = std::atoll(v); };
+  auto set_flag = [](const char* name, bool& field) { if (const char* v = std::getenv(name)) field = std::atoi(v) != 0; };
+  set_int("OBVI_ND_G", k.nd_g);
+  set_int("OBVI_ND_LEAF", k.nd_leaf);
+  set_flag("OBVI_ND_BALANCE", k.nd_balance);
+  set_flag("OBVI_TAIL_SPATIAL", k.tail_spatial);
+  set_int("OBVI_PAIR_BITMAP_MAX", k.pair_bitmap_max);
+  set_int("OBVI_SCHUR_WGS", k.schur_wgs);
+  set_flag("OBVI_PLAN_SLOTS_ON_HOST", k.slots_on_host);
+  set_int("OBVI_UPD_CHUNK", k.upd_chunk); k.upd_chunk = std::max(1, k.upd_chunk);
+  set_int("OBVI_SLICE_MAX", k.slice_max);
+  set_int("OBVI_PRE_MAX", k.pre_max); k.pre_max = std::max(0, k.pre_max);
+  set_flag("OBVI_CHOL_XCD", k.chol_xcd);
+  if (const char* v = std::getenv("OBVI_BACKWARD_LEVELS")) k.backward_levels = std::max(1, std::min(8, std::atoi(v)));
+  set_int("OBVI_COV_ROW_TILES", k.cov_row_tiles); k.cov_row_tiles = std::max(1, k.cov_row_tiles);
+  k.host_threads = std::min(16, usable_cpus()); set_int("OBVI_HOST_THREADS", k.host_threads); k.host_threads = std::max(1, k.host_threads);
+  set_i64("OBVI_POINT_RENUMBER_MIN", k.point_renumber_min);
+  set_flag("OBVI_SIDE", k.side);
+  set_int("OBVI_SIDE_MAX_SOLVERS", k.side_max_solvers);
+  set_i64("OBVI_FORK_EARLY_BELOW", k.fork_early_below);
+  set_i64("OBVI_SMALL_LANES_BELOW", k.small_lanes_below);
+  if (const char* v = std::getenv("OBVI_BACKSUB_LANES")) { const int n = std::atoi(v); if (n == 1 || n == 2 || n == 4 || n == 8 || n == 16 || n == 32) k.backsub_lanes = n; }
+  set_int("OBVI_DET_MIN_STRIDE", k.det_min_stride); k.det_min_stride = std::max(1, k.det_min_stride);
+  set_flag("OBVI_FUSED_POTRF", k.fused_potrf);
+  set_flag("OBVI_DETERMINISTIC", k.deterministic);
+  k.debug_create = std::getenv("OBVI_DEBUG_CREATE") != nullptr;
+  k.debug_prepare = std::getenv("OBVI_DEBUG_PREPARE") != nullptr;
+  k.debug_plan = std::getenv("OBVI_DEBUG_PLAN") != nullptr;
+  return k;
+}
+
+// ... and of the three that describe the process: read at the first use of any of them
+const ProcessKnobs& process_knobs() {
+  static const ProcessKnobs p = [] {
+    ProcessKnobs k;
+    k.api_timing = std::getenv("OBVI_API_TIMING") != nullptr;
+    const char* affinity = std::getenv("OBVI_HOST_AFFINITY");
+    k.host_affinity = affinity != nullptr && std::atoi(affinity) == 1;
+    const char* threads = std::getenv("OBVI_HOST_THREADS");
+    k.pool_threads = std::max(1, threads ? std::atoi(threads) : std::min(16, usable_cpus()));
+    return k;
+  }();
+  return p;
+}
+
+}  // namespace obvi_lib
+
 extern "C" {
 
 const char* obvi_ba_version(void) { return "obvi_ba 0.1 (gfx950)"; }
@@ -22,8 +75,9 @@ int obvi_ba_create(const obvi_ba_options* options, obvi_ba_handle** out) {
   *out = nullptr;
   if (options && options->object_block_size != 0 && options->object_block_size != 7 && options->object_block_size != 9) return OBVI_ERR_INVALID_ARGUMENT;   // 7: yaw only (the reference's build); 9: axis-angle
   if (options && options->reprojection_variant != OBVI_REPROJECTION_AUTODIFF && options->reprojection_variant != OBVI_REPROJECTION_ANALYTIC) return OBVI_ERR_INVALID_ARGUMENT;
+  const Knobs knobs = read_knobs();
   // OBVI_DEBUG_CREATE: where the time of a create goes, on stderr (the first one of a process also starts the HIP runtime)
-  const bool create_times = std::getenv("OBVI_DEBUG_CREATE") != nullptr;
+  const bool create_times = knobs.debug_create;
   auto t_prev = std::chrono::steady_clock::now();
   auto lap = [&](const char* what) {
     if (!create_times) return;
@@ -40,8 +94,9 @@ int obvi_ba_create(const obvi_ba_options* options, obvi_ba_handle** out) {
   if (!h) return OBVI_ERR_HIP;
   h->device = dev;
   if (options) { h->reproj_variant = options->reprojection_variant; h->deterministic = options->deterministic != 0; if (options->object_block_size == 9) h->od = 9; }
-  if (const char* env = std::getenv("OBVI_FUSED_POTRF")) h->fused_potrf = std::atoi(env) != 0;   // 0: two launches per level from the start (CI parity run)
-  if (const char* env = std::getenv("OBVI_DETERMINISTIC")) { if (std::atoi(env) != 0) h->deterministic = true; }   // every handle of the process (a session driven through a host that does not set the option)
+  h->knobs = knobs;
+  h->fused_potrf = knobs.fused_potrf;   // 0: two launches per level from the start (CI parity run)
+  if (knobs.deterministic) h->deterministic = true;   // every handle of the process (a session driven through a host that does not set the option)
   try {
     OBVI_HIP(hipSetDevice(dev));
     lap("hipSetDevice");
@@ -56,24 +111,8 @@ int obvi_ba_create(const obvi_ba_options* options, obvi_ba_handle** out) {
     h->staging.cap = kStagingBytes;
     lap("pinned staging arena");
     h->d_scal.resize(SC_COUNT);   // deterministic mode: grown by ensure_det_slots() to hold per-workgroup partial sums behind the block (ba_device.h)
-    // The side stream (pose pass, small factor families, diagonal blocks, far pairs: beside the Schur strips).  OBVI_SIDE_CUS = n (tuning knob,
-    // round 5 A/B): its queue may only use n of the device's compute units (the first n bits of the CU mask: the driver deals the bits over the
-    // XCDs, n / 8 per XCD), leaving the others to the strip kernel alone.  Default: no mask (measured: EXPERIMENTS.md round 5).
-    int side_cus = 0;
-    if (const char* env = std::getenv("OBVI_SIDE_CUS")) side_cus = std::atoi(env);
-    hipDeviceProp_t prop;
-    if (side_cus > 0 && hipGetDeviceProperties(&prop, dev) == hipSuccess && side_cus < prop.multiProcessorCount) {
-      std::vector<uint32_t> mask((size_t)(prop.multiProcessorCount + 31) / 32, 0u);
-      for (int c = 0; c < side_cus; ++c) mask[(size_t)c / 32] |= 1u << (c % 32);
-      OBVI_HIP(hipExtStreamCreateWithCUMask(&h->stream2, (uint32_t)mask.size(), mask.data()));
-    } else if (const char* pr = std::getenv("OBVI_SIDE_PRIORITY")) {
-      // (tuning knob, round 5 A/B) the side stream at another dispatch priority than the main stream: 1 = lowest, -1 = highest the device offers
-      int lo = 0, hi = 0;
-      OBVI_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-      OBVI_HIP(hipStreamCreateWithPriority(&h->stream2, hipStreamNonBlocking, std::atoi(pr) > 0 ? lo : hi));
-    } else {
-      OBVI_HIP(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
-    }
+    // the side stream (pose pass, small factor families, diagonal blocks, far pairs: beside the Schur strips)
+    OBVI_HIP(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
     for (auto& e : h->ev) OBVI_HIP(hipEventCreate(&e));
     for (auto& e : h->ev_end) OBVI_HIP(hipEventCreate(&e));
     OBVI_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming)); OBVI_HIP(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));   // ordering only: no timestamps
@@ -222,7 +261,7 @@ int obvi_ba_debug_reduced_system(obvi_ba_handle* h, double radius, double* lhs, 
   launch_zero_tiles(s, rd.S, rd.nt, h->d_tiles.get(), h->ntiles, h->d_is_pad.get(), step_clear(h, 0.0));
   launch_point_pass(s, b, rp, h->d_cams.get(), h->d_pc.get(), h->d_point.get(), rd, pt, radius, 1, h->d_scal.get(), h->d_wave_obs.get(), h->n_point_waves, h->d_long_points.get(), h->n_long_points);
   launch_pose_pass(s, b, reproj_pose_dev(h), h->d_cams.get(), h->d_pc.get(), h->d_point.get(), rd);
-  launch_small_factors(s, b, sf, h->d_cams.get(), h->d_pose.get(), h->d_obj.get(), rd, h->d_scal.get());
+  launch_small_factors(s, b, sf, h->d_cams.get(), h->d_pose.get(), h->d_obj.get(), rd, h->d_scal.get(), h->knobs.small_lanes_below);
   launch_reduced_diag(s, b, h->d_pose.get(), h->d_obj.get(), rd, radius, 1, h->d_scal.get());
   { launch_schur_window(s, h->nchunks, h->schur_twins, b, pt, rd, h->d_row_of_nat.get(), h->d_chunk_ptr.get(), h->d_batch_first.get(), h->d_batch_slot.get(), h->d_chunk_points.get(), h->d_slot_src.get(), h->d_chunk_f0.get(), h->d_chunk_group.get());
     launch_schur_blocks(s, h->nblk, h->d_blk_row.get(), h->d_blk_col.get(), h->d_blk_ptr.get(), h->d_pair_a.get(), h->d_pair_b.get(), rp.point, pt, rd); }
@@ -524,7 +563,7 @@ int obvi_ba_get_problem_stats(const obvi_ba_handle* h, double* out, int32_t cap)
   for (uint8_t a : h->h_bb_active) act_bb += a != 0;
   const double v[18] = {(double)h->nPv, (double)h->nOv, (double)h->nLv, (double)h->m_canon, (double)h->nt, (double)h->nblk, (double)(h->npairs + h->npairs_window),
                         (double)h->ntiles, (double)h->n_trsm_jobs, (double)h->n_upd_products, h->chol_flops, (double)act_rp, (double)act_bb,
-                        (double)h->nlevels, (double)host_threads(), (double)usable_cpus(),
+                        (double)h->nlevels, (double)h->knobs.host_threads, (double)usable_cpus(),
                         (double)h->potrf_wait_timeouts, h->fused_potrf ? 1.0 : 0.0};   // [16] LM steps re-run because a potrf workgroup of the fused level kernel timed out waiting for its jobs, [17] the fused schedule is still on
   const int n = std::min<int>(cap, 18);
   for (int i = 0; i < n; ++i) out[i] = v[i];

@@ -171,7 +171,7 @@ void launch_point_pass(hipStream_t s, const BlocksDev& b, const ReprojDev& rp, c
 void launch_pose_pass(hipStream_t s, const BlocksDev& b, const ReprojPoseDev& rq, const DevCam* cams, const PoseCache* pc,
                       const double* points, const ReducedDev& rd);
 void launch_small_factors(hipStream_t s, const BlocksDev& b, const SmallFactorsDev& sf, const DevCam* cams,
-                          const double* poses, const double* objects, const ReducedDev& rd, double* scal);
+                          const double* poses, const double* objects, const ReducedDev& rd, double* scal, int64_t lanes_below /* Knobs::small_lanes_below */);
 void launch_reduced_diag(hipStream_t s, const BlocksDev& b, const double* poses, const double* objects,
                          const ReducedDev& rd, double radius, int first_iter, double* scal);
 void launch_schur_blocks(hipStream_t s, int64_t nblk, const uint32_t* blk_row, const uint32_t* blk_col, const uint32_t* blk_ptr,
@@ -192,7 +192,8 @@ void launch_schur_window(hipStream_t s, int64_t nwg, int has_twins, const Blocks
                          const int32_t* wg_f0, const int32_t* wg_group);
 // point back-substitution and the candidate poses / objects (with the candidate's pose cache, both layouts of launch_pose_cache), one launch
 void launch_backsub_apply(hipStream_t s, const BlocksDev& b, const ReprojDev& rp, const PointDev& pt, const ReducedDev& rd, const double* points,
-                          double* points_cand, const double* poses, const double* objects, double* poses_cand, double* objects_cand, PoseCache* pc_cand, double* scal);
+                          double* points_cand, const double* poses, const double* objects, double* poses_cand, double* objects_cand, PoseCache* pc_cand, double* scal,
+                          int lanes /* Knobs::backsub_lanes; 0: by sightings per feature */);
 // trial-point cost + model cost change.  mode 0: cost at (poses,points,objects) into SC_COST_CAND and
 // model change of the step (cand - current); mode 1: cost only, split into SC_COST / SC_COST_FIXED.
 void launch_cost(hipStream_t s, const BlocksDev& b, const ReprojPoseDev& rq, const SmallFactorsDev& sf, const DevCam* cams,

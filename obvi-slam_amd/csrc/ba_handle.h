@@ -39,6 +39,48 @@ enum Phase { PH_POSE_CACHE = 0, PH_POINT_PASS, PH_POSE_PASS, PH_SMALL, PH_DIAG, 
 inline const char* const kPhaseNames[PH_COUNT] = {"pose_cache", "point_pass", "pose_pass", "small_factors", "reduced_diag", "schur_window", "schur_blocks",
                                      "cholesky_solve", "point_backsub", "apply_step", "cost"};
 
+// The tuning knobs of a handle.  read_knobs() is the only reader of the environment: obvi_ba_create takes one
+// snapshot and the handle keeps it for its life (obvi_ba_reset too), so a knob set after a handle was created does not affect that handle.
+// None of them changes a result beyond round-off; the tests use them to put the big-problem schedules on problems the oracle can follow.
+struct Knobs {
+  // symbolic phase (plan.cpp)
+  int nd_g = 4;                         // OBVI_ND_G: separators start / end on multiples of this many poses
+  int nd_leaf = 64;                     // OBVI_ND_LEAF: poses per leaf of the nested dissection
+  bool nd_balance = true;               // OBVI_ND_BALANCE
+  bool tail_spatial = true;             // OBVI_TAIL_SPATIAL: the shared tail along a Hilbert curve over the objects
+  int pair_bitmap_max = 8192;           // OBVI_PAIR_BITMAP_MAX: variable poses up to which the pose pairs go through a bitmap
+  int schur_wgs = 1536;                 // OBVI_SCHUR_WGS: workgroups of the Schur strip kernel
+  bool slots_on_host = false;           // OBVI_PLAN_SLOTS_ON_HOST: the host fills the strip kernel's slot tables
+  int upd_chunk = 2;                    // OBVI_UPD_CHUNK: tile products per update job (at least 1)
+  int slice_max = 512;                  // OBVI_SLICE_MAX: levels with at most this many tile jobs are row-sliced
+  int pre_max = 2;                      // OBVI_PRE_MAX: products of the previous level a potrf workgroup applies itself (at least 0)
+  bool chol_xcd = true;                 // OBVI_CHOL_XCD: XCD placement of the wide levels' jobs
+  int backward_levels = 0;              // OBVI_BACKWARD_LEVELS: levels per launch of the backward substitution, 1..8 (0: 8 or 4 by the depth of the tree)
+  int cov_row_tiles = 8;                // OBVI_COV_ROW_TILES: covariance extraction, tiles of a row of L per workgroup (at least 1)
+  int host_threads = 1;                 // OBVI_HOST_THREADS: ranges of the upload and the symbolic phase (unset: the usable CPUs, at most 16)
+  int64_t point_renumber_min = 1 << 18; // OBVI_POINT_RENUMBER_MIN: observations from which on obvi_ba_set_reproj renumbers the features (0: never)
+  // LM step (lm.cpp, launchers)
+  bool side = true;                     // OBVI_SIDE: the side stream
+  int side_max_solvers = 2;             // OBVI_SIDE_MAX_SOLVERS: a window-sized step forks only while at most this many solves are in flight
+  int64_t fork_early_below = 400000;    // OBVI_FORK_EARLY_BELOW: observations below which the side stream forks in front of the point pass
+  int64_t small_lanes_below = 4096;     // OBVI_SMALL_LANES_BELOW: bounding-box factors below which the small factors take 16 lanes each
+  int backsub_lanes = 0;                // OBVI_BACKSUB_LANES: lanes per feature of the back-substitution, 1, 2, 4, 8, 16 or 32 (0: by sightings per feature)
+  int det_min_stride = 4096;            // OBVI_DET_MIN_STRIDE: deterministic mode, first size of the partial-sum slots (at least 1)
+  // obvi_ba_create
+  bool fused_potrf = true;              // OBVI_FUSED_POTRF: 0 = the two-launch schedule of the tile Cholesky from the start
+  bool deterministic = false;           // OBVI_DETERMINISTIC: the handle is deterministic whatever its options say
+  // reports on stderr
+  bool debug_create = false, debug_prepare = false, debug_plan = false;   // OBVI_DEBUG_CREATE, OBVI_DEBUG_PREPARE, OBVI_DEBUG_PLAN
+};
+Knobs read_knobs();   // (abi.cpp)
+
+// What describes the process, not a handle: read once, at first use, by process_knobs() beside read_knobs().
+struct ProcessKnobs {
+  bool api_timing = false;      // OBVI_API_TIMING: wall time per entry point at exit (api_times)
+  bool host_affinity = false;   // OBVI_HOST_AFFINITY=1: the workers of host_pool() stay on the creating thread's block of CPUs
+  int pool_threads = 1;         // OBVI_HOST_THREADS: threads of host_pool(), the calling thread included (unset: the usable CPUs, at most 16)
+};
+const ProcessKnobs& process_knobs();   // (abi.cpp)
 
 }  // namespace obvi_lib
 using namespace obvi_lib;  // NOLINT
@@ -47,6 +89,7 @@ struct obvi_ba_handle {
   int device = 0;
   int reproj_variant = OBVI_REPROJECTION_AUTODIFF;   // obvi_ba_options.reprojection_variant
   int od = 7;                                        // obvi_ba_options.object_block_size: parameters of an ellipsoid block, 7 (x y z yaw dx dy dz) or 9 (x y z ax ay az dx dy dz)
+  Knobs knobs;                                       // read at obvi_ba_create
   bool deterministic = false;                        // obvi_ba_options.deterministic
   int32_t det_stride = 0;                            // ... workgroups each partial-sum slot behind d_scal has room for (ensure_det_slots)
   bool fused_potrf = true;                           // k_update_potrf (updates of level l + potrf of level l + 1 in one grid); switched off for the rest of the handle's life
@@ -241,7 +284,7 @@ struct ApiTimes {
   }
 };
 inline ApiTimes* api_times() {
-  static ApiTimes* t = std::getenv("OBVI_API_TIMING") ? new ApiTimes : nullptr;
+  static ApiTimes* t = process_knobs().api_timing ? new ApiTimes : nullptr;
   static const bool registered = t && (std::atexit([] { delete api_times(); }), true);
   (void)registered;
   return t;
@@ -395,16 +438,11 @@ inline int usable_cpus_uncached() {
   return n;
 }
 inline int usable_cpus() {
-  static const int n = usable_cpus_uncached();   // once per process: it reads two files, and host_threads() is asked several times per plan
+  static const int n = usable_cpus_uncached();   // once per process: it reads two files, and every obvi_ba_create asks (read_knobs)
   return n;
 }
-inline int host_threads() {
-  const char* v = std::getenv("OBVI_HOST_THREADS");
-  const int n = v ? std::atoi(v) : std::min(16, usable_cpus());
-  return std::max(1, n);
-}
 inline HostPool& host_pool() {
-  static HostPool pool(std::max(0, host_threads() - 1));   // process-wide; the calling thread is the last worker
+  static HostPool pool(std::max(0, process_knobs().pool_threads - 1), process_knobs().host_affinity);   // process-wide; the calling thread is the last worker
   return pool;
 }
 template <class F>
@@ -479,8 +517,7 @@ inline void ensure_det_slots(obvi_ba_handle* h) {
                                     h->P + (ns + 255) / 256, (h->n_rp + 255) / 256, (ns + 63) / 64});
   if (need > kDetMaxStride) throw HipError{hipErrorInvalidValue, "deterministic mode: the problem needs more partial-sum slots than kDetMaxStride", __FILE__, __LINE__};
   if (need <= h->det_stride) return;
-  const char* min_env = std::getenv("OBVI_DET_MIN_STRIDE");
-  int64_t stride = std::max(1, min_env ? std::atoi(min_env) : 4096);   // (the tests start small to see the block grow)
+  int64_t stride = h->knobs.det_min_stride;   // (the tests start small to see the block grow)
   while (stride < need) stride *= 2;
   sync(h);
   h->d_scal.resize(SC_COUNT + (size_t)kDetSlots * (size_t)stride);

@@ -1715,10 +1715,10 @@ void launch_pose_pass(hipStream_t s, const BlocksDev& b, const ReprojPoseDev& rq
   if (b.P <= 0 || rq.n <= 0) return;
   // a pose's workgroup walks its sightings 256 at a time; with few poses (a window) that loop is the latency of the launch: cut it
   // (not in the deterministic mode: one writer per block)
-  static const int max_slices = std::getenv("OBVI_POSE_PASS_SLICES") ? std::atoi(std::getenv("OBVI_POSE_PASS_SLICES")) : 8;   // tuning knob
+  constexpr int max_slices = 8;
   const int64_t per_pose = (rq.n + b.P - 1) / b.P;
   int slices = 1;
-  static const int64_t slice_below = std::getenv("OBVI_POSE_PASS_SLICE_BELOW") ? std::atoll(std::getenv("OBVI_POSE_PASS_SLICE_BELOW")) : 256;   // tuning knob (poses)
+  constexpr int64_t slice_below = 256;   // (poses)
   if (!b.deterministic && b.P <= slice_below) slices = (int)std::max<int64_t>(1, std::min<int64_t>(max_slices, (per_pose + kBlock - 1) / kBlock));
   // few poses: the loads of a sighting in two rounds with the next sighting's first round in flight (150 registers); many poses: the plain loop
   // (120 registers: beside the strip kernel the side stream is otherwise the longer one -- 2.02 vs 1.95 ms per LM iteration)
@@ -1726,9 +1726,8 @@ void launch_pose_pass(hipStream_t s, const BlocksDev& b, const ReprojPoseDev& rq
   else hipLaunchKernelGGL(k_pose_pass<false>, dim3((unsigned)(b.P * slices)), dim3(kBlock), 0, s, b, rq, cams, pc, points, rd, slices);
 }
 void launch_small_factors(hipStream_t s, const BlocksDev& b, const SmallFactorsDev& sf, const DevCam* cams, const double* poses,
-                          const double* objects, const ReducedDev& rd, double* scal) {
-  // few factors (a sliding window): 16 lanes per factor, the latency of a handful of wavefronts is the whole side stream; one launch
-  const int64_t lanes_below = std::getenv("OBVI_SMALL_LANES_BELOW") ? std::atoll(std::getenv("OBVI_SMALL_LANES_BELOW")) : 4096;   // tuning knob
+                          const double* objects, const ReducedDev& rd, double* scal, int64_t lanes_below) {
+  // few factors (below lanes_below: a sliding window): 16 lanes per factor, the latency of a handful of wavefronts is the whole side stream; one launch
   const int nb_bbox = (int)grid_for(sf.n_bb, 4), nb_priors = (int)grid_for(sf.n_sp + sf.n_lt, 64), nb_rel = (int)grid_for(sf.n_rl, 4);
   if (nb_bbox + nb_priors + nb_rel == 0) return;
   // (the bounding-box lanes are compiled per ellipsoid block size: 13 or 15 directions on the factor's 16 lanes)
@@ -1774,15 +1773,13 @@ void launch_schur_window(hipStream_t s, int64_t nwg, int has_twins, const Blocks
   else hipLaunchKernelGGL(k_schur_window<false>, dim3((unsigned)nwg), dim3(64 * kSWv), 0, s, b, pt, rd, row_of_nat, wg_bptr, bfirst, bslot, v, slot_src, wg_f0, wg_group);
 }
 void launch_backsub_apply(hipStream_t s, const BlocksDev& b, const ReprojDev& rp, const PointDev& pt, const ReducedDev& rd, const double* points,
-                          double* points_cand, const double* poses, const double* objects, double* poses_cand, double* objects_cand, PoseCache* pc_cand, double* scal) {
-  // lanes per feature: enough that the features' sightings spread over the chip, no more than a feature has sightings to hand out.
+                          double* points_cand, const double* poses, const double* objects, double* poses_cand, double* objects_cand, PoseCache* pc_cand, double* scal,
+                          int lanes) {
+  // lanes per feature (unless the caller chose them): enough that the features' sightings spread over the chip, no more than a feature has sightings to hand out.
   // Measured on 300 k features x 10 sightings (us): 1 lane 169, 2 133, 4 120, 8 116, 16 146, 32 156 -- past 8 the wavefronts' record lines
   // push each other out of the 32 KB vector cache between the nine loads of a record.
-  const char* env = getenv("OBVI_BACKSUB_LANES");   // per launch: the tests flip it inside one process
-  const int forced = env ? atoi(env) : 0;
   const int64_t per = b.L > 0 ? rp.n / b.L : 0;
-  int G = per >= 32 ? 8 : per >= 8 ? 4 : per >= 4 ? 2 : 1;
-  if (forced == 1 || forced == 2 || forced == 4 || forced == 8 || forced == 16 || forced == 32) G = forced;
+  const int G = lanes > 0 ? lanes : per >= 32 ? 8 : per >= 8 ? 4 : per >= 4 ? 2 : 1;
   const int n_point_blocks = (int)std::min<int64_t>(grid_for(b.L * G, kBlock), 2048);   // 8 per CU, each walks its share (flat between 512 and 2048)
   const unsigned grid = (unsigned)n_point_blocks + grid_for(b.P + b.O, kBlock);
   if (grid == 0) return;

@@ -125,12 +125,12 @@ class DevBuf {
 // index never travels from one job to the next and nothing of a finished job is touched after run() has returned.
 class HostPool {
  public:
-  explicit HostPool(int workers) {
+  explicit HostPool(int workers, bool near_caller = false) {
     for (int i = 0; i < workers; ++i) {
       try { threads_.emplace_back([this] { work(); }); }
       catch (const std::system_error&) { break; }   // fewer workers: the caller takes the rest itself
     }
-    keep_near_caller();
+    if (near_caller) keep_near_caller();
   }
   ~HostPool() {
     { std::lock_guard<std::mutex> lock(m_); stop_ = true; gen_.fetch_add(1, std::memory_order_release); }
@@ -171,8 +171,6 @@ class HostPool {
   // must not change thread placement behind its host's back, so this is opt-in: OBVI_HOST_AFFINITY=1 (run_offline_ba sets it for itself).
   void keep_near_caller() {
 #if defined(__linux__)
-    const char* v = std::getenv("OBVI_HOST_AFFINITY");
-    if (v == nullptr || std::atoi(v) != 1) return;
     const int cpu = sched_getcpu();
     cpu_set_t allowed;
     if (cpu < 0 || threads_.empty() || sched_getaffinity(0, sizeof(allowed), &allowed) != 0) return;

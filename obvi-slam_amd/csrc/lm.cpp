@@ -37,11 +37,9 @@ void submit_step(obvi_ba_handle* h, double radius, bool first_iter, bool solve, 
   // Schur complement (everything they share is accumulated with atomics), so they run beside them on the side stream.
   // With a multi-GPU exchange the first collective (the shared objects' blocks) rides on the side stream too: it needs the pose pass and the
   // small factors, and only the diagonal-block kernel behind it needs its result.  Not in an instrumented solve.
-  static const bool side_ok = !std::getenv("OBVI_SIDE") || std::atoi(std::getenv("OBVI_SIDE")) != 0;   // tuning knob
-  static const int side_max_solvers = std::getenv("OBVI_SIDE_MAX_SOLVERS") ? std::atoi(std::getenv("OBVI_SIDE_MAX_SOLVERS")) : 2;   // tuning knob (see g_active_solves)
-  const int64_t fork_early_below = std::getenv("OBVI_FORK_EARLY_BELOW") ? std::atoll(std::getenv("OBVI_FORK_EARLY_BELOW")) : 400000;   // tuning knob (observations); read per step: the tests flip it
-  const bool crowded_window = h->n_rp < fork_early_below && g_active_solves.load(std::memory_order_relaxed) > side_max_solvers;
-  const bool side = h->profiling < 2 && side_ok && !h->deterministic && !crowded_window;   // deterministic mode: one stream, so that the kernels that add to the same tiles do so in a fixed order
+  const int64_t fork_early_below = h->knobs.fork_early_below;   // (observations)
+  const bool crowded_window = h->n_rp < fork_early_below && g_active_solves.load(std::memory_order_relaxed) > h->knobs.side_max_solvers;   // (see g_active_solves)
+  const bool side = h->profiling < 2 && h->knobs.side && !h->deterministic && !crowded_window;   // deterministic mode: one stream, so that the kernels that add to the same tiles do so in a fixed order
   hipStream_t s2 = side ? h->stream2 : s;
   // the point pass first, alone: it and the pose-side pass stream the same observation arrays and are both HBM-bound (side by side the
   // point pass took 0.35 ms instead of 0.24); the side stream starts behind it and runs beside the Schur complement, which is bound
@@ -57,7 +55,7 @@ void submit_step(obvi_ba_handle* h, double radius, bool first_iter, bool solve, 
   };
   auto side_small_factors = [&] {
     record(h, PH_SMALL, s2);
-    launch_small_factors(s2, b, sf, h->d_cams.get(), h->d_pose.get(), h->d_obj.get(), rd, scal);
+    launch_small_factors(s2, b, sf, h->d_cams.get(), h->d_pose.get(), h->d_obj.get(), rd, scal, h->knobs.small_lanes_below);
     if (side) record_end(h, PH_SMALL, s2);
   };
   auto side_diagonal = [&] {
@@ -127,7 +125,7 @@ void submit_step(obvi_ba_handle* h, double radius, bool first_iter, bool solve, 
     h->ck_used = 0;
   }
   record(h, PH_BACKSUB);
-  if (solve) launch_backsub_apply(s, b, rp, pt, rd, h->d_point.get(), h->d_point_c.get(), h->d_pose.get(), h->d_obj.get(), h->d_pose_c.get(), h->d_obj_c.get(), h->d_pc_c.get(), scal);
+  if (solve) launch_backsub_apply(s, b, rp, pt, rd, h->d_point.get(), h->d_point_c.get(), h->d_pose.get(), h->d_obj.get(), h->d_pose_c.get(), h->d_obj_c.get(), h->d_pc_c.get(), scal, h->knobs.backsub_lanes);
   record(h, PH_APPLY);   // (the candidate poses / objects are formed in the same launch)
   record(h, PH_COST);
   if (solve) launch_cost(s, b, reproj_pose_dev(h), sf, h->d_cams.get(), h->d_pc.get(), h->d_pose.get(), h->d_point.get(), h->d_obj.get(), h->d_pc_c.get(),
@@ -138,8 +136,7 @@ void submit_step(obvi_ba_handle* h, double radius, bool first_iter, bool solve, 
     if (h->allreduce(h->allreduce_user, h->d_xbuf.get(), (SC_SUM_END - SC_COST) + h->world, 0, s)) throw HipError{hipErrorUnknown, "allreduce hook (scalars)", __FILE__, __LINE__};
     launch_pack_scalars(s, scal, h->d_xbuf.get(), h->rank, h->world, 1);
   }
-  static const bool poll_ok = !std::getenv("OBVI_POLL_SCALARS") || std::atoi(std::getenv("OBVI_POLL_SCALARS")) != 0;   // tuning knob
-  const bool poll = poll_ok && h->profiling < 1 && !keep_factor;
+  const bool poll = h->profiling < 1 && !keep_factor;
   // the clear of the next LM step does not depend on the accept / reject decision: it runs while the host takes it
   // (not when the caller goes on to use the factor that is in the tiles: covariance extraction) -- and its first workgroup behind the
   // tiles hands the scalar block to the host before it clears it

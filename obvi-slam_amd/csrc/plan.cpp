@@ -36,12 +36,14 @@ struct PlanBuilder {
   int64_t m_pad = 0;
   // Schur complement work lists
   static constexpr int32_t SR = kSchurRows, SBACK = kSchurWindowFrames - kSchurRows;
+  // points per range of the parallel passes (the 300-frame session: 256 -> 0.73-0.78 ms per window plan, 1024 -> 0.96-1.30, one range -> 1.2)
+  static constexpr int64_t kPlanGrain = 256;
   struct Pair { uint64_t key; uint32_t a, b; };
   struct Visit { int32_t chunk; uint32_t l, beg, k; bool twin; uint64_t tiles; };
   std::vector<uint8_t> mask;                   // nt x nt tiles of the reduced matrix, lower triangle
   std::vector<Pair> pairs;                     // observation pairs outside the strips (k_schur_blocks)
   std::vector<std::vector<Visit>> visits_t;    // the visits, in point order: one list per range of points (they are never merged: the counting sort reads the ranges)
-  int64_t n_window_pairs = 0, max_visits = 0;
+  int64_t n_window_pairs = 0;
   bool any_twin = false, pair_bitmap = false, slots_on_host = false;
   uint32_t zero16 = 0;
   std::vector<uint32_t> wg_bptr, bfirst, bslot, visits, slot_src, plan_wg_ptr, plan_wg_slot0, blk_row, blk_col, blk_ptr, pair_a, pair_b;
@@ -57,7 +59,7 @@ struct PlanBuilder {
   double flops = 0.0;
   int64_t n_products = 0;
 
-  const bool stage_times = std::getenv("OBVI_DEBUG_PREPARE") != nullptr;
+  const bool stage_times = h->knobs.debug_prepare;
   std::chrono::steady_clock::time_point t_prev = std::chrono::steady_clock::now();
   void stage(const char* name) {
     if (!stage_times) return;
@@ -65,7 +67,6 @@ struct PlanBuilder {
     std::fprintf(stderr, "prepare: %-28s %8.2f ms\n", name, std::chrono::duration<double, std::milli>(t - t_prev).count());
     t_prev = t;
   }
-  static int env_int(const char* name, int dflt) { const char* v = std::getenv(name); return v ? std::atoi(v) : dflt; }
   void mark(int64_t row, int dr, int64_t col, int dc) {   // the tiles a (dr x dc) block at (row, col) touches
     const int t0 = (int)(row / kTile), t1 = (int)((row + dr - 1) / kTile), c0 = (int)(col / kTile), c1 = (int)((col + dc - 1) / kTile);
     for (int ti = t0; ti <= t1; ++ti) for (int tj = c0; tj <= c1; ++tj) if (ti >= tj) mask[(size_t)ti * nt + tj] = 1;
@@ -76,7 +77,7 @@ struct PlanBuilder {
     std::vector<uint8_t> pose_used(P, 0), obj_used(O, 0), point_used(L, 0);
     nres = 0;
     {   // ranges of observations on the host threads: the flags are idempotent byte stores of 1 (relaxed atomics: ranges share poses, and a point at a range's edge)
-      const int parts = (int)std::max<int64_t>(1, std::min<int64_t>(host_threads(), h->n_rp / 65536));
+      const int parts = (int)std::max<int64_t>(1, std::min<int64_t>(h->knobs.host_threads, h->n_rp / 65536));
       std::vector<int64_t> nres_t(parts, 0);
       std::vector<std::vector<uint8_t>> pose_used_t(parts);   // per range: every range sees every pose (sixteen threads storing into the same P bytes were slower than one)
       parallel_ranges(h->n_rp, parts, [&](int part, int64_t a0, int64_t a1) {
@@ -138,7 +139,7 @@ struct PlanBuilder {
       std::vector<int32_t> reach(nPv);
       for (int64_t f = 0; f < nPv; ++f) reach[f] = (int32_t)f;
       {   // ranges of points on the host threads, every range with a reach array of its own (nPv integers), joined by maximum
-        const int parts = (int)std::max<int64_t>(1, std::min<int64_t>(host_threads(), L / 4096));
+        const int parts = (int)std::max<int64_t>(1, std::min<int64_t>(h->knobs.host_threads, L / 4096));
         std::vector<std::vector<int32_t>> reach_t(parts);
         parallel_ranges(L, parts, [&](int part, int64_t l0, int64_t l1) {
           std::vector<int32_t>& r = reach_t[part];
@@ -170,10 +171,10 @@ struct PlanBuilder {
       //      covers the frame range [lo,hi) of its subtree
       struct Node { int32_t lo, hi, p0, p1, left, right; };
       std::vector<Node> nodes;
-      const int32_t G = std::getenv("OBVI_ND_G") ? std::atoi(std::getenv("OBVI_ND_G")) : 4;   // cut granularity in poses (tuning knob)
-      const int32_t kLeaf = std::getenv("OBVI_ND_LEAF") ? std::atoi(std::getenv("OBVI_ND_LEAF")) : 64;   // tuning knob (poses per leaf)
-      const bool balance = !std::getenv("OBVI_ND_BALANCE") || std::atoi(std::getenv("OBVI_ND_BALANCE")) != 0;   // tuning knob
-      const double sep_frac = std::getenv("OBVI_ND_SEPFRAC") ? std::atof(std::getenv("OBVI_ND_SEPFRAC")) : 0.5;   // tuning knob: a range is cut only if the separator is at most this part of it
+      const int32_t G = h->knobs.nd_g;   // cut granularity in poses
+      const int32_t kLeaf = h->knobs.nd_leaf;   // poses per leaf
+      const bool balance = h->knobs.nd_balance;
+      constexpr double sep_frac = 0.5;   // a range is cut only if the separator is at most this part of it
       std::function<int32_t(int32_t, int32_t)> build = [&](int32_t lo, int32_t hi) -> int32_t {
         auto leaf = [&]() { nodes.push_back({lo, hi, lo, hi, -1, -1}); return (int32_t)nodes.size() - 1; };
         if (hi - lo <= kLeaf) return leaf();
@@ -236,13 +237,13 @@ struct PlanBuilder {
       for (size_t n = 0; n < nodes.size(); ++n) {
         const int64_t r0 = row;
         place_node(nodes[n].p0, nodes[n].p1, node_objs[n]);
-        if (std::getenv("OBVI_DEBUG_PLAN")) std::fprintf(stderr, "node %zu: frames [%d,%d) of subtree [%d,%d) %s objects %zu rows %lld tiles %lld\n", n, nodes[n].p0, nodes[n].p1, nodes[n].lo, nodes[n].hi,
+        if (h->knobs.debug_plan) std::fprintf(stderr, "node %zu: frames [%d,%d) of subtree [%d,%d) %s objects %zu rows %lld tiles %lld\n", n, nodes[n].p0, nodes[n].p1, nodes[n].lo, nodes[n].hi,
                                                          nodes[n].left < 0 ? "leaf" : "separator", node_objs[n].size(), (long long)(row - ((r0 + kTile - 1) / kTile) * kTile), (long long)((row + kTile - 1) / kTile - (r0 + kTile - 1) / kTile));
       }
       place_node(0, 0, node_objs[nodes.size()]);
       h->tail_t0 = -1;
       h->h_shared_ov.clear();
-      if (tail_objs.size() > 1 && (int64_t)h->h_obj_xy.size() == 2 * O && (!std::getenv("OBVI_TAIL_SPATIAL") || std::atoi(std::getenv("OBVI_TAIL_SPATIAL")) != 0)) {
+      if (tail_objs.size() > 1 && (int64_t)h->h_obj_xy.size() == 2 * O && h->knobs.tail_spatial) {
         // Order of the shared tail (round 5).  Every rank must lay the shared objects out in the SAME order (the tail's tiles are summed across ranks), so the
         // order can only depend on what all ranks share: the objects' index and their uploaded values.  Object-index order (rounds 2-4) is arbitrary with
         // respect to the trajectory, so every pose tile column coupled with every object tile row of the tail (9 objects to a row: each row holds one that
@@ -322,13 +323,12 @@ struct PlanBuilder {
     n_window_pairs = 0; any_twin = false;
     // pose pairs that share a point: collected in a bitmap (one store per pair of sightings) and turned into tile marks once per
     // pose pair afterwards -- a point contributes k (k + 1) / 2 pairs and most of them repeat
-    pair_bitmap = h->nPv <= env_int("OBVI_PAIR_BITMAP_MAX", 8192);   // 64 MB at most; beyond it the tile marks are made pair by pair (tuning knob)
+    pair_bitmap = h->nPv <= h->knobs.pair_bitmap_max;   // 64 MB at most; beyond it the tile marks are made pair by pair
     std::vector<uint8_t> pose_pair(pair_bitmap ? (size_t)h->nPv * (size_t)h->nPv : 0, 0);
     {
       // points are independent: ranges of points on host threads (the bitmap is shared: every writer stores the same 1), lists joined in
       // point order.  Without the bitmap the tile marks go straight into the mask: one thread.
-      const int64_t grain = std::max(1, env_int("OBVI_PLAN_GRAIN", 256));   // points per range (tuning knob)
-      const int parts = pair_bitmap ? (int)std::max<int64_t>(1, std::min<int64_t>(host_threads(), L / grain)) : 1;   // the workers exist (host_pool): a range of a few hundred points is worth handing out
+      const int parts = pair_bitmap ? (int)std::max<int64_t>(1, std::min<int64_t>(h->knobs.host_threads, L / kPlanGrain)) : 1;   // the workers exist (host_pool): a range of a few hundred points is worth handing out
       std::vector<std::vector<Pair>> pairs_t(parts);
       visits_t.assign(parts, {});
       // small windows: every range marks its pose pairs in a bitmap of its own (a few KB), merged afterwards -- sixteen threads storing
@@ -422,7 +422,7 @@ struct PlanBuilder {
       }
     }
     if (pair_bitmap)   // rows of the bitmap on the host threads: the marks are idempotent byte stores of 1 (relaxed atomics: two pose pairs may share a tile)
-      parallel_ranges(h->nPv, (int)std::max<int64_t>(1, std::min<int64_t>(host_threads(), h->nPv / 64)), [&](int, int64_t r0, int64_t r1) {
+      parallel_ranges(h->nPv, (int)std::max<int64_t>(1, std::min<int64_t>(h->knobs.host_threads, h->nPv / 64)), [&](int, int64_t r0, int64_t r1) {
         for (int64_t hi = r0; hi < r1; ++hi) {
           const uint8_t* row = &pose_pair[(size_t)hi * (size_t)h->nPv];
           const int64_t row_hi = h->h_pose_row[hi];
@@ -473,10 +473,10 @@ struct PlanBuilder {
         }
       });
     }
-    max_visits = std::max(8, env_int("OBVI_SCHUR_VISITS", 1 << 20));   // visits per workgroup (tuning knob)
+    constexpr int64_t max_visits = (int64_t)1 << 20;   // visits per workgroup
     // slices of a work list: enough workgroups to fill the device on small problems, at most max_visits visits each
     // (deterministic mode: a work list is never cut -- one workgroup, hence one writer, per strip)
-    const int64_t slice = h->deterministic ? ((int64_t)1 << 40) : std::min<int64_t>(max_visits, std::max<int64_t>(64, (int64_t)gv.size() / env_int("OBVI_SCHUR_WGS", 1536)));
+    const int64_t slice = h->deterministic ? ((int64_t)1 << 40) : std::min<int64_t>(max_visits, std::max<int64_t>(64, (int64_t)gv.size() / h->knobs.schur_wgs));
     // per workgroup: batches of visits that fit the kernel's LDS buffer.  A visit is laid out as consecutive 144-byte
     // slots: one per strip frame over the range of its row frames and of its column frames in the group (source: the Z
     // record, or the zero page for a frame the point skips), the point's (u_l, 0) tail, and -- stereo -- a second layer
@@ -557,7 +557,7 @@ struct PlanBuilder {
     // Who fills the slot tables.  Default (round 5): the DEVICE (plan_kernels.hip: one lane per visit walks the point's observations).  What is left for the
     // host is to deal the visits to batches, which needs a visit's slot COUNT only -- a function of its tile bits, its group and the twin flag.
     // OBVI_PLAN_SLOTS_ON_HOST=1: the host fills them as rounds 1-4 did (the check: both give the same tables).
-    slots_on_host = std::getenv("OBVI_PLAN_SLOTS_ON_HOST") && std::atoi(std::getenv("OBVI_PLAN_SLOTS_ON_HOST")) != 0;
+    slots_on_host = h->knobs.slots_on_host;
     auto visit_slot_count = [&](const GVisit& v) -> uint32_t {
       constexpr int kRowTile0 = SBACK * 6 / 16;
       uint32_t rows = 0;
@@ -578,7 +578,7 @@ struct PlanBuilder {
       return v.twin ? 2 * one : one;
     };
     struct BatchLists { std::vector<uint32_t> visits, slot_src, end_visit, end_slot, wg_batches, wg_slots; };
-    const int parts2 = (int)std::max<int64_t>(1, std::min<int64_t>(host_threads(), (int64_t)gv.size() / (4 * (int64_t)std::max(1, env_int("OBVI_PLAN_GRAIN", 256)))));
+    const int parts2 = (int)std::max<int64_t>(1, std::min<int64_t>(h->knobs.host_threads, (int64_t)gv.size() / (4 * kPlanGrain)));
     std::vector<BatchLists> lists_t(parts2);
     plan_visits.assign(slots_on_host ? 0 : gv.size(), PlanVisit{});
     parallel_ranges((int64_t)wgs.size(), parts2, [&](int part, int64_t g0, int64_t g1) {
@@ -698,10 +698,9 @@ struct PlanBuilder {
     for (int k = 0; k < nt; ++k) by_level[level[k]].push_back(k);
     lvl_k.clear(); trsm_ik.clear(); upd_ij.clear(); upd_kptr.assign(1, 0); upd_k.clear(); rh_i.clear(); rh_kptr.assign(1, 0); rh_k.clear(); job_signal.clear(); k_need_of.assign((size_t)nt, 0);
     upd_flag.clear();
-    const int kUpdChunk = h->deterministic ? (1 << 30) : std::max(1, env_int("OBVI_UPD_CHUNK", 2));   // products per update job (tuning knob; deterministic mode: a target's products are never split over jobs that would meet in atomics)
-    const int64_t env_slice_max = std::getenv("OBVI_SLICE_MAX") ? std::atoi(std::getenv("OBVI_SLICE_MAX")) : 512;   // tuning knob
+    const int kUpdChunk = h->deterministic ? (1 << 30) : h->knobs.upd_chunk;   // products per update job (deterministic mode: a target's products are never split over jobs that would meet in atomics)
     // a potrf workgroup applies up to this many products of the previous level to its own diagonal tile (tuning knob)
-    const size_t pre_max = (size_t)std::max(0, env_int("OBVI_PRE_MAX", 2));
+    const size_t pre_max = (size_t)h->knobs.pre_max;
     pre_of.assign((size_t)nt, {});
     h->h_lvl_k_ptr.assign(nlev + 1, 0); h->h_trsm_ptr.assign(nlev + 1, 0); h->h_upd_ptr.assign(nlev + 1, 0); h->h_rh_ptr.assign(nlev + 1, 0); h->h_crit_upd.assign(nlev + 1, 0); h->h_crit_rh.assign(nlev + 1, 0); h->h_slices.assign(nlev + 1, 1);
     flops = 0.0;
@@ -748,7 +747,7 @@ struct PlanBuilder {
         q = e;
       }
       std::stable_partition(jobs.begin(), jobs.end(), [](const Job& x) { return x.crit; });
-      const int32_t sl = (int64_t)jobs.size() + (int64_t)ik.size() <= env_slice_max ? 4 : 1;   // thin level: the device is mostly idle, split every tile product
+      const int32_t sl = (int64_t)jobs.size() + (int64_t)ik.size() <= (int64_t)h->knobs.slice_max ? 4 : 1;   // thin level: the device is mostly idle, split every tile product
       h->h_slices[l] = sl;
       h->h_crit_upd[l] = (int32_t)std::count_if(jobs.begin(), jobs.end(), [](const Job& x) { return x.crit; });
       // XCD placement on the wide levels.  Block b is observed to run on XCD b % 8, each XCD with its own L2; the tiles L_ik of a column
@@ -756,7 +755,7 @@ struct PlanBuilder {
       // fabric.  Columns of one level are independent, so every column gets the XCD its own potrf ran on (which wrote L_kk^-1), its trsm jobs take
       // block indices with that residue and so do its update jobs (after the launch's leading critical jobs and potrf workgroups):
       // operands then come out of the L2 they were written to.  Queues that run dry are filled from the others (a speed matter only).
-      static const bool xcd_place = env_int("OBVI_CHOL_XCD", 1) != 0;   // tuning knob
+      const bool xcd_place = h->knobs.chol_xcd;
       std::vector<int32_t> xcd_of(nt, 0);
       {   // ... the XCD its potrf ran on: workgroup (leading critical jobs of the previous level's launch + rank) of that launch
         int32_t r = l > 0 ? h->h_slices[l - 1] * h->h_crit_upd[l - 1] + h->h_crit_rh[l - 1] : 0;
@@ -812,7 +811,7 @@ struct PlanBuilder {
       h->h_trsm_ptr[l + 1] = (int32_t)(trsm_ik.size() / 2);
       h->h_upd_ptr[l + 1] = (int32_t)(upd_ij.size() / 2);
       h->h_rh_ptr[l + 1] = (int32_t)rh_i.size();
-      if (std::getenv("OBVI_DEBUG_PLAN")) std::fprintf(stderr, "level %d: columns %zu (first %d) trsm %zu update jobs %zu (critical %d) products %zu slices %d\n", l, by_level[l].size(), by_level[l].empty() ? -1 : by_level[l][0], ik.size(), jobs.size(), h->h_crit_upd[l], trips.size(), sl);
+      if (h->knobs.debug_plan) std::fprintf(stderr, "level %d: columns %zu (first %d) trsm %zu update jobs %zu (critical %d) products %zu slices %d\n", l, by_level[l].size(), by_level[l].empty() ? -1 : by_level[l][0], ik.size(), jobs.size(), h->h_crit_upd[l], trips.size(), sl);
     }
   }
 
@@ -823,7 +822,7 @@ struct PlanBuilder {
     bw_kj.clear(); bw_chains.clear();
     // levels per launch (tuning knob; 1: one level per launch; chains of at most 7): four, or the whole tree when it has at most eight levels
     // (a sliding window: one launch instead of two)
-    const int bw_levels = std::max(1, std::min(8, env_int("OBVI_BACKWARD_LEVELS", nlev <= 8 ? 8 : 4)));
+    const int bw_levels = h->knobs.backward_levels > 0 ? h->knobs.backward_levels : nlev <= 8 ? 8 : 4;
     h->h_bw_ptr.assign(1, 0);
     {
       int top = nlev - 1;             // the levels are grouped from the top
@@ -865,7 +864,7 @@ struct PlanBuilder {
       if (row_j.empty()) row_j.push_back(0);
       h->d_row_ptr.upload(row_ptr, h->stream); h->d_row_j.upload(row_j, h->stream);
       // levels whose rows are long (separators near the root) spread a row over several workgroups: about 8 tiles each, at most 16
-      const int row_tiles = std::max(1, std::getenv("OBVI_COV_ROW_TILES") ? std::atoi(std::getenv("OBVI_COV_ROW_TILES")) : 8);   // tuning knob
+      const int row_tiles = h->knobs.cov_row_tiles;
       h->h_row_split.assign(nlev, 1);
       for (int l = 0; l < nlev; ++l) {
         int longest = 0;
@@ -1003,8 +1002,6 @@ void prepare_plan(obvi_ba_handle* h) {
 // of a pose / object that dropped out become padding rows (identity).  Only the reduced-program bookkeeping is redone: O(factors).
 // Returns false when the new state is not a subset (the caller then rebuilds the plan).
 bool prepare_masks(obvi_ba_handle* h) {
-  static const bool keep = !std::getenv("OBVI_KEEP_PLAN") || std::atoi(std::getenv("OBVI_KEEP_PLAN")) != 0;   // 0: always rebuild (parity runs)
-  if (!keep) return false;
   const int64_t P = h->P, L = h->L, O = h->O;
   if ((int64_t)h->plan_pose_vid.size() != P || (int64_t)h->plan_obj_vid.size() != O || (int64_t)h->plan_point_var.size() != L) return false;
   auto subset = [](const std::vector<uint8_t>& now, const std::vector<uint8_t>& plan) {

@@ -133,8 +133,7 @@ int obvi_ba_set_reproj(obvi_ba_handle* h, int64_t n, const uint32_t* pose_idx, c
   // (a sliding window is bound by its launches, and its host time matters more: it keeps the caller's numbering).  OBVI_POINT_RENUMBER_MIN: observations from which on
   // (default 2^18; 0: never).
   {
-    const char* env = std::getenv("OBVI_POINT_RENUMBER_MIN");
-    const int64_t min_obs = env ? std::atoll(env) : ((int64_t)1 << 18);
+    const int64_t min_obs = h->knobs.point_renumber_min;
     std::vector<uint32_t> old_of_new;
     bool identity = true;
     if (min_obs > 0 && n >= min_obs && h->L > 1) {
@@ -185,7 +184,7 @@ int obvi_ba_set_reproj(obvi_ba_handle* h, int64_t n, const uint32_t* pose_idx, c
   for (int64_t i = 0; i < n; ++i) perm[cur[pidx[i]]++] = (uint32_t)i;
   // ranges of points / observations on the host's worker threads -- from a few hundred thousand observations on: a window's 50 k are
   // 0.6 ms on one thread and 0.85-1.3 ms on 2-16 (waking the workers, 256 cores on two sockets passing cache lines around)
-  const int threads = (int)std::max<int64_t>(1, std::min<int64_t>(host_threads(), n / 131072));
+  const int threads = (int)std::max<int64_t>(1, std::min<int64_t>(h->knobs.host_threads, n / 131072));
   parallel_ranges(h->L, threads, [&](int, int64_t l0, int64_t l1) {
     auto before = [&](uint32_t x, uint32_t y) { return pose_idx[x] < pose_idx[y] || (pose_idx[x] == pose_idx[y] && x < y); };
     for (int64_t l = l0; l < l1; ++l)

@@ -175,7 +175,7 @@ inline bool runFullOptimization(std::optional<OptimizationLogger>& opt_logger, c
   runner.setExtractLongTermMap(extract_long_term_map);
   runner.setLongTermMapTunableParams(config.ltm_tunable_params_);
   const bool ok = runner.runOptimization(problem_data, config.optimization_factors_enabled_params_, opt_logger, output_results, start_at_frame, add_data_for_starting_frame);
-  if (std::getenv("OBVI_HOST_TIMING")) runner.printTiming(std::cerr);
+  if (obvi::host_knobs().timing) runner.printTiming(std::cerr);
   if (hooks != nullptr) hooks->factors_left_out_ = runner.factorsLeftOutByTheCreator();
   output_results.records_ = runner.records();
   output_results.post_session_merge_rounds_ = runner.mergeRounds();

@@ -417,7 +417,7 @@ using namespace vslam_types_refactor;   // NOLINT (the reference's optimiser hea
 typedef ObjectAndReprojectionFeaturePoseGraph PoseGraphType;
 
 // One persistent host thread for work that runs BESIDE a solve (solveOptimization's `beside` hooks): post() hands it a job, wait() returns when the job has
-// ended.  Between jobs the thread spins for a while before it sleeps (OBVI_HOST_BESIDE_SPIN_US, default 4000): in a session a job arrives every few
+// ended.  Between jobs the thread spins for a while before it sleeps (4 ms): in a session a job arrives every few
 // milliseconds, and a thread that slept wakes up on a core that has gone idle -- measured on the 300-frame session, a thread created per job ran the same work
 // (frame data, window build, upload, symbolic phase) in 3.3 ms instead of 1.9.
 class BesideThread {
@@ -452,7 +452,7 @@ class BesideThread {
  private:
   enum { kIdle = 0, kPosted = 1, kDone = 2 };
   void loop() {
-    static const long spin_us = std::getenv("OBVI_HOST_BESIDE_SPIN_US") ? std::atol(std::getenv("OBVI_HOST_BESIDE_SPIN_US")) : 4000;
+    constexpr long spin_us = 4000;
     for (;;) {
       const auto t0 = std::chrono::steady_clock::now();
       while (state_.load(std::memory_order_acquire) != kPosted && std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() < spin_us) {
@@ -529,7 +529,7 @@ class ObjectPoseGraphOptimizer {
       std::shared_ptr<PoseGraphType>& pose_graph, obvi::Problem* problem, std::optional<OptimizationLogger>& opt_logger,
       const FactorInfoSet& excluded_feature_factor_types_and_ids = {}) {
     residual_params_ = residual_params;
-    const bool timing_ = std::getenv("OBVI_HOST_TIMING") != nullptr && std::getenv("OBVI_HOST_TIMING")[0] == '2';
+    const bool timing_ = obvi::host_knobs().timing == 2;
     auto t_last_ = std::chrono::steady_clock::now();
     auto lap_ = [&](const char* what) {
       if (!timing_) return;
@@ -697,7 +697,7 @@ class ObjectPoseGraphOptimizer {
       bool ascending = true, first = true; FeatureFactorId last_id = 0;
       // A global-BA frame flattens millions of records: the frames' spans are then written by ranges of spans on host threads (each span's
       // share of the arrays is known after a counting pass: same arrays, same order); a window's few ten thousand go the plain way.
-      const unsigned hw = std::getenv("OBVI_HOST_BUILD_THREADS") ? (unsigned)std::atoi(std::getenv("OBVI_HOST_BUILD_THREADS")) : std::thread::hardware_concurrency();   // (knob: 1 = the plain loop)
+      const unsigned hw = obvi::host_knobs().build_threads;   // (1 = the plain loop)
       const size_t n_threads = total >= ((size_t)1 << 18) && hw > 1 ? std::min<size_t>({(size_t)8, (size_t)hw, spans.size()}) : 1;
       if (n_threads > 1) {
         std::vector<size_t> kept_of(spans.size(), 0), at(spans.size() + 1, 0);
@@ -1111,7 +1111,7 @@ inline bool runPgoPlusEllipsoids(const FrameId& max_frame_id, const Optimization
                                  const pose_graph_optimization::PoseGraphPlusObjectsOptimizationParams& pgo_solver_params, const bool& final_run,
                                  std::optional<OptimizationLogger>& opt_logger, std::shared_ptr<PoseGraphType>& pose_graph, int device_id = 0,
                                  const int& attempt_num = 0) {
-  const bool timing = std::getenv("OBVI_HOST_TIMING") != nullptr;
+  const bool timing = obvi::host_knobs().timing != 0;
   auto t_last = std::chrono::steady_clock::now();
   auto lap = [&](const char* what) {
     if (!timing) return;
@@ -1172,7 +1172,7 @@ inline bool runPgoPlusEllipsoids(const FrameId& max_frame_id, const Optimization
   // STRUCTURE depends on nothing the pose-graph solve computes: a second thread builds it on a problem (and device handle) of its own while that solve runs; the
   // values -- poses from the solve, features moved along with their first frame -- are handed over before it is solved (solveOptimization: obvi_ba_update_state).
   // OBVI_HOST_PLAN_AHEAD=0: one after the other on the stage's one problem.
-  static const bool plan_ahead = !std::getenv("OBVI_HOST_PLAN_AHEAD") || std::atoi(std::getenv("OBVI_HOST_PLAN_AHEAD")) != 0;
+  const bool plan_ahead = obvi::host_knobs().plan_ahead;
   const bool vf_beside = plan_ahead && pgo_solver_params.enable_visual_feats_only_opt_post_pgo_ && !problem.dryRun();
   OptimizationScopeParams scope_vf = optimization_scope_params;
   scope_vf.fix_poses_ = true; scope_vf.fix_objects_ = true; scope_vf.include_object_factors_ = false;

@@ -7,6 +7,8 @@
 
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
+#include <thread>
 #include <unordered_set>
 
 #include "obvi_types.h"
@@ -121,4 +123,34 @@ inline FrameId provideOptimizationWindow(const FrameId& max_frame_to_opt, const 
   return max_frame_to_opt - p.local_ba_window_size_;
 }
 }  // namespace vslam_types_refactor
+
+namespace obvi {
+// The host mirror's OBVI_HOST_* switches, read once per process at the first call.  run_offline_ba's main may set
+// OBVI_HOST_PLAN_AHEAD itself: it does so before anything asks.
+struct HostKnobs {
+  bool plan_ahead = true;             // OBVI_HOST_PLAN_AHEAD: the next window / the stage's features-only problem is built beside the running solve
+  bool select_on_host = false;        // OBVI_HOST_SELECT_ON_HOST: outlier selection the reference's way
+  bool phase2_rebuild = false;        // OBVI_HOST_PHASE2_REBUILD: phase II always rebuilds the problem
+  bool phase2_check = false;          // OBVI_HOST_PHASE2_CHECK: both phase-II routes, compared window by window
+  bool phase2_check_verbose = false;  // OBVI_HOST_PHASE2_CHECK_VERBOSE (set at all): ... with every object that differs
+  int timing = 0;                     // OBVI_HOST_TIMING: 0 unset, 1 stage times, 2 (a value starting with '2') also the parts of every build
+  unsigned build_threads = 0;         // OBVI_HOST_BUILD_THREADS: threads that flatten a big build (unset: the hardware threads; 1 = the plain loop)
+};
+inline const HostKnobs& host_knobs() {
+  static const HostKnobs knobs = [] {
+    HostKnobs k;
+    auto flag = [](const char* name, bool& field) { if (const char* v = std::getenv(name)) field = std::atoi(v) != 0; };
+    flag("OBVI_HOST_PLAN_AHEAD", k.plan_ahead);
+    flag("OBVI_HOST_SELECT_ON_HOST", k.select_on_host);
+    flag("OBVI_HOST_PHASE2_REBUILD", k.phase2_rebuild);
+    flag("OBVI_HOST_PHASE2_CHECK", k.phase2_check);
+    k.phase2_check_verbose = std::getenv("OBVI_HOST_PHASE2_CHECK_VERBOSE") != nullptr;
+    if (const char* v = std::getenv("OBVI_HOST_TIMING")) k.timing = v[0] == '2' ? 2 : 1;
+    const char* threads = std::getenv("OBVI_HOST_BUILD_THREADS");
+    k.build_threads = threads ? (unsigned)std::atoi(threads) : std::thread::hardware_concurrency();
+    return k;
+  }();
+  return knobs;
+}
+}  // namespace obvi
 #endif  // OBVI_HOST_PARAMS_H_

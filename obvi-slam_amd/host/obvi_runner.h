@@ -215,8 +215,7 @@ class OfflineProblemRunner<OutputProblemData> {
       // a visualization callback), not across a global-BA frame (that iteration starts with other problems), not with the phase-II cross-check.
       ahead_job_ = nullptr;
       const FrameId ahead_frame = next_frame_id + 1;
-      static const bool phase_two_check = std::getenv("OBVI_HOST_PHASE2_CHECK") && std::atoi(std::getenv("OBVI_HOST_PHASE2_CHECK")) != 0;
-      if (planAheadEnabled() && !phase_two_check && ahead_frame <= max_frame_id && !frame_data_adder_ && !visual_feature_adder_ && !visualization_callback_ && !factor_hooks_set_ && !gba_checker_(ahead_frame)) {
+      if (obvi::host_knobs().plan_ahead && !obvi::host_knobs().phase2_check && ahead_frame <= max_frame_id && !frame_data_adder_ && !visual_feature_adder_ && !visualization_callback_ && !factor_hooks_set_ && !gba_checker_(ahead_frame)) {
         obvi::Problem* ahead_problem = &problem_objects[1 - current];
         ahead_job_ = [this, &problem_data, &pose_graph, ahead_frame, ahead_problem, scope]() {
           const auto t0 = std::chrono::steady_clock::now();
@@ -396,7 +395,7 @@ class OfflineProblemRunner<OutputProblemData> {
         // depends on what the stage computes: a second thread does it on this problem's handle while the stage runs on another one (the session's second
         // problem object parked its handle for that: runOptimization); the values are handed over afterwards.  The stage reads the graph's structure and
         // writes block values; the build reads structure only.
-        const bool plan_beside_stage = planAheadEnabled() && run_visual_feature_opt && !planned_ahead && !problem.dryRun() && !factor_hooks_set_;
+        const bool plan_beside_stage = obvi::host_knobs().plan_ahead && run_visual_feature_opt && !planned_ahead && !problem.dryRun() && !factor_hooks_set_;
         if (plan_beside_stage) {
           stage_beside_thread_.post([this, &scope, &pose_graph, &problem]() {
             const auto t0 = std::chrono::steady_clock::now();
@@ -463,7 +462,7 @@ class OfflineProblemRunner<OutputProblemData> {
     // by the value.  obvi_ba_select_outliers makes the same selection on the device (K8; same de-duplication of equal values,
     // tests/test_gpu_parity.py::test_two_phase_outlier_rejection) and hands back one byte per factor instead of every residual.
     // OBVI_HOST_SELECT_ON_HOST=1: the literal host route.
-    static const bool select_on_host = std::getenv("OBVI_HOST_SELECT_ON_HOST") && std::atoi(std::getenv("OBVI_HOST_SELECT_ON_HOST")) != 0;
+    const bool select_on_host = obvi::host_knobs().select_on_host;
     const bool device_selection = two_phase && !select_on_host;
     const bool ok1 = (two_phase && !device_selection) ? optimizer_.solveOptimization(&problem, iteration_params.phase_one_opt_params_, opt_logger, &residual_block_ids, &residuals)
                                                       : optimizer_.solveOptimization(&problem, iteration_params.phase_one_opt_params_, opt_logger, nullptr, nullptr, nullptr, nullptr, /*keep_for_phase_two=*/two_phase,
@@ -527,20 +526,18 @@ class OfflineProblemRunner<OutputProblemData> {
       restoreValues(pose_graph_copy);                                                            // :811
       // :812-:830 rebuild the problem with the excluded factors.  The same selection is made on the problem phase I left on the device
       // whenever the rebuild would only remove things (OBVI_HOST_PHASE2_REBUILD=1: always rebuild, as the reference does)
-      static const bool always_rebuild = std::getenv("OBVI_HOST_PHASE2_REBUILD") && std::atoi(std::getenv("OBVI_HOST_PHASE2_REBUILD")) != 0;
+      const bool always_rebuild = obvi::host_knobs().phase2_rebuild;
       pose_graph_optimizer::ObjectPoseGraphOptimizer::PhaseTwoMasks masks;
       bool ok2;
       const bool have_masks = !always_rebuild && optimizer_.excludeFromBuiltProblem(scope, pose_graph, excluded, problem, &masks, device_selection ? &keep_rp : nullptr, device_selection ? &keep_bb : nullptr);
-      static const bool check_rebuild = std::getenv("OBVI_HOST_PHASE2_CHECK") && std::atoi(std::getenv("OBVI_HOST_PHASE2_CHECK")) != 0;
-      if (device_selection && (!have_masks || check_rebuild)) materialise_excluded();
+      if (device_selection && (!have_masks || obvi::host_knobs().phase2_check)) materialise_excluded();
       if (have_masks) {
         optimizer_.setPhaseTwoLogCounts(masks, opt_logger);
         ok2 = optimizer_.solveOptimization(&problem, iteration_params.phase_two_opt_params_, opt_logger, nullptr, nullptr, nullptr, &masks, false, &beside_last);
         ++n_phase_two_masked_;
         // OBVI_HOST_PHASE2_CHECK=1 (tests): the same phase II the reference's way -- rebuild with the excluded set, upload, solve -- on a
         // scratch handle from the same start values, window by window; the session goes on with the masked result
-        static const bool check = std::getenv("OBVI_HOST_PHASE2_CHECK") && std::atoi(std::getenv("OBVI_HOST_PHASE2_CHECK")) != 0;
-        if (check && ok2) {
+        if (obvi::host_knobs().phase2_check && ok2) {
           const obvi::SolverSummary fast = optimizer_.lastSummary();
           const ValueSnapshot fast_values = snapshotValues(problem.flat);
           restoreValues(pose_graph_copy);
@@ -573,7 +570,7 @@ class OfflineProblemRunner<OutputProblemData> {
               if (k == 0) check_.max_value_diff = std::max(check_.max_value_diff, d);   // poses
               else if (k == 1) { check_.points++; if (d > 1e-2) check_.points_apart++; }   // features: a few are barely constrained in depth and amplify any flipped iteration
               else if (std::fabs(it->second[4] - it->second[5]) < 0.1 * std::max(it->second[4], it->second[5])) { /* dx ~ dy: yaw, and with it the centre, float */ }
-              else { check_.objects++; if (d > 1e-2) { check_.objects_apart++; if (std::getenv("OBVI_HOST_PHASE2_CHECK_VERBOSE")) { std::cerr << "object apart at frame " << next_frame_id << ":"; for (int c = 0; c < 7; ++c) std::cerr << " " << it->second[c] << "/" << ref_values.values[k][7 * i + c]; std::cerr << std::endl; } } }             // objects: one whose boxes are (nearly) all in the constant invalid-ellipse branch floats
+              else { check_.objects++; if (d > 1e-2) { check_.objects_apart++; if (obvi::host_knobs().phase2_check_verbose) { std::cerr << "object apart at frame " << next_frame_id << ":"; for (int c = 0; c < 7; ++c) std::cerr << " " << it->second[c] << "/" << ref_values.values[k][7 * i + c]; std::cerr << std::endl; } } }             // objects: one whose boxes are (nearly) all in the constant invalid-ellipse branch floats
             }
           restoreValues(pose_graph_copy);   // blocks the rebuilt problem does not hold keep their start values in both routes
           restoreValues(fast_values);
@@ -635,7 +632,6 @@ class OfflineProblemRunner<OutputProblemData> {
   std::atomic<bool> ahead_graph_done_{true};
   double time_stage_beside_ms_ = 0, time_stage_beside_wait_ms_ = 0; size_t n_stage_beside_ = 0;
   double time_ahead_ms_ = 0, time_ahead_add_ms_ = 0, time_ahead_build_ms_ = 0, time_ahead_upload_ms_ = 0; size_t n_ahead_ = 0;
-  static bool planAheadEnabled() { static const bool on = !std::getenv("OBVI_HOST_PLAN_AHEAD") || std::atoi(std::getenv("OBVI_HOST_PLAN_AHEAD")) != 0; return on; }
   std::vector<OptimizationRecord> records_;
   double time_build_ms_ = 0, time_copy_ms_ = 0, time_add_ms_ = 0, time_select_ms_ = 0, time_pgo_ms_ = 0; size_t n_pgo_ = 0; size_t n_iterations_ = 0, n_phase_two_masked_ = 0, n_phase_two_rebuilt_ = 0;
   struct PhaseTwoCheck { size_t windows = 0, failures = 0, iteration_mismatches = 0, size_mismatches = 0, points = 0, points_apart = 0, objects = 0, objects_apart = 0; double max_initial_cost_rel = 0, max_final_cost_rel = 0, max_value_diff = 0; } check_;

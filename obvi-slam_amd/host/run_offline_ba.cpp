@@ -293,8 +293,7 @@ int main(int argc, char** argv) {
     if (4u * (unsigned)sessions_in_process > cpus) setenv("OBVI_HOST_PLAN_AHEAD", "0", 1);
   }
   if (!dump && !front_end_only) {
-    const bool plan_ahead = !std::getenv("OBVI_HOST_PLAN_AHEAD") || std::atoi(std::getenv("OBVI_HOST_PLAN_AHEAD")) != 0;
-    for (int k = 0; k < sessions_in_process * (plan_ahead ? 3 : 1) && k < 8; ++k)   // (planned ahead: the session's two problems + the pose-graph stage's)
+    for (int k = 0; k < sessions_in_process * (obvi::host_knobs().plan_ahead ? 3 : 1) && k < 8; ++k)   // (planned ahead: the session's two problems + the pose-graph stage's)
       obvi::HandlePool::instance().warm(obvi::makeHandleOptions(device));
   }
   OfflineProblemData data;
@@ -549,7 +548,7 @@ int main(int argc, char** argv) {
   if (front_end) { std::cerr << "front_end "; front_end_report(std::cerr); std::cerr << std::endl; front_end.reset(); obvi_ba_destroy(front_end_handle); }
   const auto t_run1 = std::chrono::steady_clock::now();
   IterationLoggerFactory::getInstance().writeAllIterationLoggerStates();                                                     // offline_object_visual_slam_main.cpp:1108
-  if (std::getenv("OBVI_HOST_TIMING"))
+  if (obvi::host_knobs().timing)
     std::cerr << "driver: scene load + setup " << std::chrono::duration<double, std::milli>(t_run0 - t_main0).count() << " ms, runFullOptimization "
               << std::chrono::duration<double, std::milli>(t_run1 - t_run0).count() << " ms" << std::endl;
   obvi::HandlePool::instance().drain();

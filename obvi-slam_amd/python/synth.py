@@ -138,11 +138,13 @@ def odom_cov(t, aa, m_tt, m_tr, m_rt, m_rr):
 
 
 def make_problem(P, L, O=0, seed=20241008, outlier_frac=0.05, const_poses=1, pixel_noise=1.0,
-                 point_noise=0.1, with_relpose=True, min_obj_obs=10, object_classes=None, bbox_noise=30.0, stereo=False, object_seed=None, min_parallax_deg=0.0):
+                 point_noise=0.1, with_relpose=True, min_obj_obs=10, object_classes=None, bbox_noise=30.0, stereo=False, object_seed=None, min_parallax_deg=0.0,
+                 sort_points=False):
     """Returns a dict of flat arrays accepted by upload(); 'gt_*' hold the ground truth.
     min_parallax_deg > 0 (the "w" problems, make_well_posed): only features whose rays from the first and the last frame of their track meet at that angle or
     more are kept -- the camera looks along the direction of travel, so a feature near the optical axis 15 m ahead has no observable depth and LM walks
-    it to infinity at its own pace (the 600-m features of profiles/r05_end_state_config3.txt).  0 = the generator of rounds 1-5, same random stream."""
+    it to infinity at its own pace (the 600-m features of profiles/r05_end_state_config3.txt).  0 = the generator of rounds 1-5, same random stream.
+    sort_points: feature ids in the order of their first sighting instead of the generator's random ones (round-6 experiment, profiles/EXPERIMENTS.md)."""
     rng = np.random.Generator(np.random.MT19937(seed))
     rp = RESIDUAL_PARAMS
     pos, R = _trajectory(P, rng)
@@ -218,8 +220,7 @@ def make_problem(P, L, O=0, seed=20241008, outlier_frac=0.05, const_poses=1, pix
                 rp_pose=obs_pose, rp_point=obs_point, rp_cam=obs_cam, rp_pixel=obs_pix,
                 rp_sigma=rp["reproj_sigma"], rp_huber=rp["reproj_huber"], rp_is_outlier=is_out)
     prob["pose_const"][:const_poses] = 1
-    import os as _os
-    if _os.environ.get("OBVI_SYNTH_SORT_POINTS"):
+    if sort_points:
         # experiment (round 6): feature ids in the order of first sighting, as a front end that numbers features when it first sees them hands them over
         # (the generator's ids are random with respect to the trajectory)
         firstf = np.full(len(points), P, np.int64); np.minimum.at(firstf, obs_point.astype(np.int64), obs_pose.astype(np.int64))

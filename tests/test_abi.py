@@ -106,3 +106,39 @@ def test_host_pool_hands_every_part_out_exactly_once(tmp_path):
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-pthread", "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-o", exe, os.path.join(helpers.ROOT, "tests", "hostpool_stress.cpp")])
     out = subprocess.run([exe, "20000"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout + out.stderr
+
+
+def _function_body(src, signature):
+    """The definition of the C++ function that starts with `signature`, up to its matching closing brace."""
+    start = src.index(signature)
+    depth = 0
+    for j in range(src.index("{", start), len(src)):
+        depth += {"{": 1, "}": -1}.get(src[j], 0)
+        if depth == 0:
+            return src[start:j + 1]
+    raise AssertionError("unbalanced braces after " + signature)
+
+
+def test_knobs_are_read_in_one_place_and_documented():
+    """The library reads its environment in read_knobs() and process_knobs() alone (abi.cpp; obvi_rccl.cpp reads the rendezvous names), the host
+    mirror's headers in host_knobs() alone (obvi_params.h), and INTEGRATION.md section 5 lists exactly the OBVI_* names these functions read."""
+    import re
+    csrc = os.path.join(helpers.ROOT, "obvi-slam_amd", "csrc")
+    host = os.path.join(helpers.ROOT, "obvi-slam_amd", "host")
+    readers = {os.path.join(csrc, "abi.cpp"): ("Knobs read_knobs()", "const ProcessKnobs& process_knobs()"),
+               os.path.join(host, "obvi_params.h"): ("inline const HostKnobs& host_knobs()",)}
+    sources = [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".cpp", ".hip", ".h")) and f != "obvi_rccl.cpp"]
+    sources += [os.path.join(host, f) for f in sorted(os.listdir(host)) if f.endswith(".h")]
+    read = set()
+    for path in sources:
+        src = open(path).read()
+        for signature in readers.get(path, ()):
+            body = _function_body(src, signature)
+            read |= set(re.findall(r'"(OBVI_[A-Z0-9_]+)"', body))
+            src = src.replace(body, "")
+        assert "getenv" not in src, path
+    text = open(os.path.join(helpers.ROOT, "INTEGRATION.md")).read()
+    section = text[text.index("## 5. "):text.index("## 6. ")]
+    first_cells = [line.split("|")[1] for line in section.splitlines() if line.startswith("| `OBVI_")]
+    table = set(re.findall(r"`(OBVI_[A-Z0-9_]+)`", "\n".join(first_cells))) - {"OBVI_RCCL_JOB", "OBVI_BA_LIBRARY"}
+    assert read == table, (sorted(read - table), sorted(table - read))
