@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "ba_math.h"
@@ -55,8 +56,8 @@ enum Scalar {
 // Deterministic mode (obvi_ba_options.deterministic).  The sums a solve's decisions are taken from -- costs, |g|^2, |x|^2, |delta|^2, the
 // model cost change -- are then not added to the scalar block with fp64 atomics (whose order changes from run to run): workgroup b of
 // a kernel stores its partial sum at scal[SC_COUNT + slot * stride + b], and a one-workgroup-per-slot kernel behind it adds them up
-// in a fixed order (launch_det_reduce, which refuses a grid larger than the stride).  stride = BlocksDev.deterministic, the room the
-// handle gave the slots for the problem it holds (ensure_det_slots in ba_handle.h: the largest grid, a power of two >= 4096).
+// in a fixed order (launch_reducing in ba_kernels.hip, which refuses a grid larger than the stride before the kernel).  stride = BlocksDev.deterministic,
+// the room the handle gave the slots for the problem it holds (ensure_det_slots in ba_handle.h: det_slots_needed below, rounded up to OBVI_DET_MIN_STRIDE x 2^k).
 // What stays atomic in this mode, and why the result is still the same from run to run:
 //   - counters (failed pivots, non-finite entries: small integers) and the gradient maximum (integer max): exact in any order;
 //   - the fp64 adds into the reduced system's tiles, right-hand side and diagonal (k_schur_window, k_schur_blocks, k_reduced_diag, the
@@ -72,7 +73,26 @@ inline __host__ __device__ int det_slot_of(int sc) {
 inline __host__ __device__ int det_scalar_of(int slot) {
   return slot == 0 ? SC_COST : slot == 1 ? SC_COST_CAND : slot == 2 ? SC_GSQ : slot == 3 ? SC_XSQ : slot == 4 ? SC_STEPSQ : slot == 5 ? SC_MODEL_CHANGE : SC_COST_FIXED;
 }
-void launch_det_reduce(hipStream_t s, double* scal, int64_t nblocks, uint32_t scalar_mask /* bit sc: scalar sc was written by the kernel */, int stride);
+// The grid of every kernel that leaves partial sums, defined once: its launcher in ba_kernels.hip launches it, det_slots_needed sizes the slots by it.
+// A grid made of parts adds up over them: with the other parts' counts at 0 it is one part's workgroups (the boundaries the launchers hand the kernels).
+constexpr int kBaBlock = 256;   // threads per workgroup of the ba_kernels.hip kernels (kBlock there) but k_small_lin_lanes and k_eval_small (64)
+inline int64_t blocks_of(int64_t n, int64_t per) { return (n + per - 1) / per; }
+inline int64_t point_pass_grid(int64_t n_waves) { return blocks_of(n_waves, kBaBlock / 64); }   // k_point_pass: a wavefront per piece of the observation list
+inline int64_t point_pass_long_grid(int64_t n_long) { return blocks_of(n_long, kBaBlock); }     // k_point_pass_long: a thread per long-track point
+inline int64_t small_lin_grid(int64_t n_bb, int64_t n_priors, int64_t n_rl) { return blocks_of(n_bb, 4) + blocks_of(n_priors, 64) + blocks_of(n_rl, 4); }   // k_small_lin_lanes: 16 lanes per box / relative pose, one per prior
+inline int64_t reduced_diag_grid(int64_t P, int64_t O, int64_t od) { return blocks_of((od > 8 ? 16 : 8) * (P + O), kBaBlock); }   // k_reduced_diag: 8 threads per diagonal block, 16 if od > 8
+// k_backsub_apply: `lanes` per feature on at most 2048 workgroups (8 per CU), then a thread per pose / object
+inline int64_t backsub_grid(int64_t L, int64_t P, int64_t O, int lanes) { return std::min<int64_t>(blocks_of(L * lanes, kBaBlock), 2048) + blocks_of(P + O, kBaBlock); }
+inline int64_t cost_grid(int64_t P, int64_t n_obs, int64_t n_small) { return (n_obs > 0 ? P : 0) + blocks_of(n_small, kBaBlock); }   // k_cost: a workgroup per pose, a thread per small factor
+inline int64_t eval_reproj_grid(int64_t n_obs) { return blocks_of(n_obs, kBaBlock); }   // k_eval_reproj, k_eval_small: a thread per factor
+inline int64_t eval_small_grid(int64_t n_small) { return blocks_of(n_small, 64); }
+// the largest of those grids (launch_backsub_apply takes at most 32 lanes per feature), at least 1 for an empty problem: the stride is also the mode's flag
+struct DetCounts { int64_t P, L, O, od, n_rp, n_point_waves, n_long_points, n_bb, n_sp, n_lt, n_rl; };
+inline int64_t det_slots_needed(const DetCounts& c) {
+  const int64_t ns = c.n_bb + c.n_sp + c.n_lt + c.n_rl;
+  return std::max<int64_t>({1, point_pass_grid(c.n_point_waves), point_pass_long_grid(c.n_long_points), small_lin_grid(c.n_bb, c.n_sp + c.n_lt, c.n_rl),
+                            reduced_diag_grid(c.P, c.O, c.od), backsub_grid(c.L, c.P, c.O, 32), cost_grid(c.P, c.n_rp, ns), eval_reproj_grid(c.n_rp), eval_small_grid(ns)});
+}
 
 struct ReprojDev {          // observations sorted by (point, pose): CSC by point
   int64_t n;

@@ -507,14 +507,12 @@ inline void bake_bbox(obvi_ba_handle* h) {
 // ---------------------------------------------------------------------------------------
 inline bool prepare_masks(obvi_ba_handle* h);
 inline void prepare_plan(obvi_ba_handle* h);
-// Deterministic mode: room behind the scalar block for one partial sum per workgroup of the largest grid that leaves any (ba_device.h;
-// the grids are those of the launchers at the end of ba_kernels.hip, launch_det_reduce refuses a larger one).  The block is reallocated
-// when the problem outgrows it -- only between API calls: every call clears the scalars before its first launch.
+// Deterministic mode: room behind the scalar block for one partial sum per workgroup of the largest grid that leaves any (det_slots_needed:
+// the grids are defined in ba_device.h, the launchers in ba_kernels.hip launch exactly those and refuse one larger than the slots).  The block is
+// reallocated when the problem outgrows it -- only between API calls: every call clears the scalars before its first launch.
 inline void ensure_det_slots(obvi_ba_handle* h) {
   if (!h->deterministic) return;
-  const int64_t small = (h->n_bb + 3) / 4 + (h->n_sp + h->n_lt + 63) / 64 + (h->n_rl + 3) / 4, ns = h->n_bb + h->n_sp + h->n_lt + h->n_rl;
-  int64_t need = std::max<int64_t>({(h->n_point_waves + 3) / 4, (h->n_long_points + 255) / 256, small, (8 * (h->P + h->O) + 255) / 256, 2048 + (h->P + h->O + 255) / 256,
-                                    h->P + (ns + 255) / 256, (h->n_rp + 255) / 256, (ns + 63) / 64});
+  const int64_t need = det_slots_needed({h->P, h->L, h->O, h->od, h->n_rp, h->n_point_waves, h->n_long_points, h->n_bb, h->n_sp, h->n_lt, h->n_rl});
   if (need > kDetMaxStride) throw HipError{hipErrorInvalidValue, "deterministic mode: the problem needs more partial-sum slots than kDetMaxStride", __FILE__, __LINE__};
   if (need <= h->det_stride) return;
   int64_t stride = h->knobs.det_min_stride;   // (the tests start small to see the block grow)

@@ -17,7 +17,7 @@
 namespace obvi {
 namespace {
 
-constexpr int kBlock = 256;
+constexpr int kBlock = kBaBlock;
 
 __device__ __forceinline__ void atomic_add_f64(double* p, double v) { unsafeAtomicAdd(p, v); }
 
@@ -1680,14 +1680,19 @@ __global__ void __launch_bounds__(kBlock) k_pack_tail(ReducedDev rd, int32_t t0,
 }
 
 inline unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
+// a kernel that leaves partial sums (its grid: ba_device.h): launch(grid) enqueues it; in deterministic mode the grid is checked against
+// the slots' room first, and k_det_reduce adds up the scalars in scalar_mask (bit sc: scalar sc) behind it
+template <class Launch>
+void launch_reducing(hipStream_t s, const BlocksDev& b, double* scal, int64_t grid, uint32_t scalar_mask, Launch&& launch) {
+  if (grid <= 0) return;
+  if (b.deterministic && grid > b.deterministic) throw std::logic_error("deterministic mode: a grid larger than the partial-sum slots (det_slots_needed() in ba_device.h undercounts)");
+  launch(dim3((unsigned)grid));
+  if (b.deterministic) hipLaunchKernelGGL(k_det_reduce, dim3(kDetSlots), dim3(kBlock), 0, s, scal, grid, scalar_mask, b.deterministic);
+}
 
 }  // namespace
 
 // =========================================================================================
-void launch_det_reduce(hipStream_t s, double* scal, int64_t nblocks, uint32_t scalar_mask, int stride) {
-  if (nblocks > stride) throw std::logic_error("deterministic mode: a grid larger than the partial-sum slots (ensure_det_slots() in ba_handle.h undercounts)");
-  if (nblocks > 0) hipLaunchKernelGGL(k_det_reduce, dim3(kDetSlots), dim3(kBlock), 0, s, scal, nblocks, scalar_mask, stride);
-}
 #define OBVI_SC(x) (1u << (x))
 void launch_reproj_gather(hipStream_t s, int64_t n, const uint32_t* perm, const uint32_t* rq_src, const uint32_t* rp_point, const uint16_t* raw_cam,
                           const double2* raw_pixel, const double* raw_sigma, double sigma_scalar, uint16_t* cam, double2* pixel, double* sigma,
@@ -1701,14 +1706,11 @@ void launch_pose_cache(hipStream_t s, int64_t P, const double* poses, PoseCache*
 void launch_point_pass(hipStream_t s, const BlocksDev& b, const ReprojDev& rp, const DevCam* cams, const PoseCache* pc, const double* points,
                        const ReducedDev& rd, const PointDev& pt, double radius, int first_iter, double* scal, const uint32_t* wave_obs, int64_t n_waves,
                        const uint32_t* long_points, int64_t n_long) {
-  if (n_waves > 0) {
-    hipLaunchKernelGGL(k_point_pass, dim3(grid_for(n_waves, kBlock / 64)), dim3(kBlock), 0, s, b, rp, cams, pc, points, rd, pt, radius, first_iter, scal, wave_obs, n_waves);
-    if (b.deterministic) launch_det_reduce(s, scal, grid_for(n_waves, kBlock / 64), OBVI_SC(SC_COST) | OBVI_SC(SC_GSQ) | OBVI_SC(SC_XSQ), b.deterministic);
-  }
-  if (n_long > 0) {
-    hipLaunchKernelGGL(k_point_pass_long, dim3(grid_for(n_long, kBlock)), dim3(kBlock), 0, s, b, rp, cams, pc, points, rd, pt, radius, first_iter, scal, long_points, n_long);
-    if (b.deterministic) launch_det_reduce(s, scal, grid_for(n_long, kBlock), OBVI_SC(SC_COST) | OBVI_SC(SC_GSQ) | OBVI_SC(SC_XSQ), b.deterministic);
-  }
+  const uint32_t sums = OBVI_SC(SC_COST) | OBVI_SC(SC_GSQ) | OBVI_SC(SC_XSQ);
+  launch_reducing(s, b, scal, point_pass_grid(n_waves), sums, [&](dim3 g) {
+    hipLaunchKernelGGL(k_point_pass, g, dim3(kBlock), 0, s, b, rp, cams, pc, points, rd, pt, radius, first_iter, scal, wave_obs, n_waves); });
+  launch_reducing(s, b, scal, point_pass_long_grid(n_long), sums, [&](dim3 g) {
+    hipLaunchKernelGGL(k_point_pass_long, g, dim3(kBlock), 0, s, b, rp, cams, pc, points, rd, pt, radius, first_iter, scal, long_points, n_long); });
 }
 void launch_pose_pass(hipStream_t s, const BlocksDev& b, const ReprojPoseDev& rq, const DevCam* cams, const PoseCache* pc, const double* points,
                       const ReducedDev& rd) {
@@ -1728,15 +1730,16 @@ void launch_pose_pass(hipStream_t s, const BlocksDev& b, const ReprojPoseDev& rq
 void launch_small_factors(hipStream_t s, const BlocksDev& b, const SmallFactorsDev& sf, const DevCam* cams, const double* poses,
                           const double* objects, const ReducedDev& rd, double* scal, int64_t lanes_below) {
   // few factors (below lanes_below: a sliding window): 16 lanes per factor, the latency of a handful of wavefronts is the whole side stream; one launch
-  const int nb_bbox = (int)grid_for(sf.n_bb, 4), nb_priors = (int)grid_for(sf.n_sp + sf.n_lt, 64), nb_rel = (int)grid_for(sf.n_rl, 4);
-  if (nb_bbox + nb_priors + nb_rel == 0) return;
+  const int64_t grid = small_lin_grid(sf.n_bb, sf.n_sp + sf.n_lt, sf.n_rl);
+  const int nb_bbox = (int)small_lin_grid(sf.n_bb, 0, 0), nb_priors = (int)small_lin_grid(0, sf.n_sp + sf.n_lt, 0);
+  if (grid == 0) return;
   // (the bounding-box lanes are compiled per ellipsoid block size: 13 or 15 directions on the factor's 16 lanes)
-#define OBVI_SMALL_LIN(STORE) do { if (b.od == 9) hipLaunchKernelGGL((k_small_lin_lanes<STORE, 9>), dim3(nb_bbox + nb_priors + nb_rel), dim3(64), 0, s, b, sf, cams, poses, objects, rd, scal, nb_bbox, nb_priors); \
-                                   else hipLaunchKernelGGL((k_small_lin_lanes<STORE, 7>), dim3(nb_bbox + nb_priors + nb_rel), dim3(64), 0, s, b, sf, cams, poses, objects, rd, scal, nb_bbox, nb_priors); } while (0)
+#define OBVI_SMALL_LIN(STORE) launch_reducing(s, b, scal, grid, OBVI_SC(SC_COST), [&](dim3 g) { \
+    if (b.od == 9) hipLaunchKernelGGL((k_small_lin_lanes<STORE, 9>), g, dim3(64), 0, s, b, sf, cams, poses, objects, rd, scal, nb_bbox, nb_priors); \
+    else hipLaunchKernelGGL((k_small_lin_lanes<STORE, 7>), g, dim3(64), 0, s, b, sf, cams, poses, objects, rd, scal, nb_bbox, nb_priors); })
   if (b.deterministic) {
     // no fp64 atomics on the diagonal blocks: every factor leaves its blocks in a scratch slot, the gathers add them per target in list order
     OBVI_SMALL_LIN(true);
-    launch_det_reduce(s, scal, nb_bbox + nb_priors + nb_rel, OBVI_SC(SC_COST), b.deterministic);
     if (sf.n_bb > 0) hipLaunchKernelGGL(k_bbox_gather, dim3((unsigned)b.O + grid_for(b.P, kBlock / 64)), dim3(kBlock), 0, s, b, sf, rd);
     if (sf.n_sp + sf.n_lt + sf.n_rl > 0) hipLaunchKernelGGL(k_small_gather, dim3(grid_for(b.O + b.P, kBlock / 64)), dim3(kBlock), 0, s, b, sf, rd);
     return;
@@ -1754,11 +1757,8 @@ void launch_small_factors(hipStream_t s, const BlocksDev& b, const SmallFactorsD
 }
 void launch_reduced_diag(hipStream_t s, const BlocksDev& b, const double* poses, const double* objects, const ReducedDev& rd, double radius,
                          int first_iter, double* scal) {
-  if (b.P + b.O > 0) {
-    const int per = b.od > 8 ? 16 : 8;   // threads per diagonal block
-    hipLaunchKernelGGL(k_reduced_diag, dim3(grid_for(per * (b.P + b.O), kBlock)), dim3(kBlock), 0, s, b, poses, objects, rd, radius, first_iter, scal);
-    if (b.deterministic) launch_det_reduce(s, scal, grid_for(per * (b.P + b.O), kBlock), OBVI_SC(SC_GSQ) | OBVI_SC(SC_XSQ), b.deterministic);
-  }
+  launch_reducing(s, b, scal, reduced_diag_grid(b.P, b.O, b.od), OBVI_SC(SC_GSQ) | OBVI_SC(SC_XSQ), [&](dim3 g) {
+    hipLaunchKernelGGL(k_reduced_diag, g, dim3(kBlock), 0, s, b, poses, objects, rd, radius, first_iter, scal); });
 }
 void launch_schur_blocks(hipStream_t s, int64_t nblk, const uint32_t* blk_row, const uint32_t* blk_col, const uint32_t* blk_ptr,
                          const uint32_t* pair_a, const uint32_t* pair_b, const uint32_t* obs_point, const PointDev& pt, const ReducedDev& rd) {
@@ -1780,13 +1780,11 @@ void launch_backsub_apply(hipStream_t s, const BlocksDev& b, const ReprojDev& rp
   // push each other out of the 32 KB vector cache between the nine loads of a record.
   const int64_t per = b.L > 0 ? rp.n / b.L : 0;
   const int G = lanes > 0 ? lanes : per >= 32 ? 8 : per >= 8 ? 4 : per >= 4 ? 2 : 1;
-  const int n_point_blocks = (int)std::min<int64_t>(grid_for(b.L * G, kBlock), 2048);   // 8 per CU, each walks its share (flat between 512 and 2048)
-  const unsigned grid = (unsigned)n_point_blocks + grid_for(b.P + b.O, kBlock);
-  if (grid == 0) return;
-#define OBVI_BACKSUB(GG) hipLaunchKernelGGL(k_backsub_apply<GG>, dim3(grid), dim3(kBlock), 0, s, b, rp, pt, rd, points, points_cand, poses, objects, poses_cand, objects_cand, pc_cand, n_point_blocks, scal)
-  switch (G) { case 32: OBVI_BACKSUB(32); break; case 16: OBVI_BACKSUB(16); break; case 8: OBVI_BACKSUB(8); break; case 4: OBVI_BACKSUB(4); break; case 2: OBVI_BACKSUB(2); break; default: OBVI_BACKSUB(1); }
+  const int n_point_blocks = (int)backsub_grid(b.L, 0, 0, G);   // each walks its share (flat between 512 and 2048)
+#define OBVI_BACKSUB(GG) hipLaunchKernelGGL(k_backsub_apply<GG>, g, dim3(kBlock), 0, s, b, rp, pt, rd, points, points_cand, poses, objects, poses_cand, objects_cand, pc_cand, n_point_blocks, scal)
+  launch_reducing(s, b, scal, backsub_grid(b.L, b.P, b.O, G), OBVI_SC(SC_STEPSQ) | OBVI_SC(SC_MODEL_CHANGE), [&](dim3 g) {
+    switch (G) { case 32: OBVI_BACKSUB(32); break; case 16: OBVI_BACKSUB(16); break; case 8: OBVI_BACKSUB(8); break; case 4: OBVI_BACKSUB(4); break; case 2: OBVI_BACKSUB(2); break; default: OBVI_BACKSUB(1); } });
 #undef OBVI_BACKSUB
-  if (b.deterministic) launch_det_reduce(s, scal, grid, OBVI_SC(SC_STEPSQ) | OBVI_SC(SC_MODEL_CHANGE), b.deterministic);
 }
 void launch_cost(hipStream_t s, const BlocksDev& b, const ReprojPoseDev& rq, const SmallFactorsDev& sf, const DevCam* cams, const PoseCache* pc_cur,
                  const double* poses_cur, const double* points_cur, const double* objects_cur, const PoseCache* pc_cand, const double* poses_cand,
@@ -1796,35 +1794,26 @@ void launch_cost(hipStream_t s, const BlocksDev& b, const ReprojPoseDev& rq, con
   const double* poses = mode == 0 ? poses_cand : poses_cur;
   const double* points = mode == 0 ? points_cand : points_cur;
   const double* objects = mode == 0 ? objects_cand : objects_cur;
-  const int n_pose_blocks = rq.n > 0 && b.P > 0 ? (int)b.P : 0;
-  const int64_t ns = sf.n_bb + sf.n_sp + sf.n_lt + sf.n_rl;
-  const unsigned grid = (unsigned)n_pose_blocks + grid_for(ns, kBlock);
-  if (grid > 0) {
-    if (b.P <= 256) hipLaunchKernelGGL(k_cost<true>, dim3(grid), dim3(kBlock), 0, s, b, rq, sf, cams, pc, poses, points, objects, mode, n_pose_blocks, scal);   // (few poses: cost_reproj_block)
-    else hipLaunchKernelGGL(k_cost<false>, dim3(grid), dim3(kBlock), 0, s, b, rq, sf, cams, pc, poses, points, objects, mode, n_pose_blocks, scal);
-    if (b.deterministic) launch_det_reduce(s, scal, grid, mode == 0 ? OBVI_SC(SC_COST_CAND) : OBVI_SC(SC_COST_FIXED), b.deterministic);
-  }
+  const int n_pose_blocks = (int)cost_grid(b.P, rq.n, 0);
+  launch_reducing(s, b, scal, cost_grid(b.P, rq.n, sf.n_bb + sf.n_sp + sf.n_lt + sf.n_rl), mode == 0 ? OBVI_SC(SC_COST_CAND) : OBVI_SC(SC_COST_FIXED), [&](dim3 g) {
+    if (b.P <= 256) hipLaunchKernelGGL(k_cost<true>, g, dim3(kBlock), 0, s, b, rq, sf, cams, pc, poses, points, objects, mode, n_pose_blocks, scal);   // (few poses: cost_reproj_block)
+    else hipLaunchKernelGGL(k_cost<false>, g, dim3(kBlock), 0, s, b, rq, sf, cams, pc, poses, points, objects, mode, n_pose_blocks, scal); });
 }
 void launch_evaluate(hipStream_t s, const BlocksDev& b, const ReprojDev& rp, const uint32_t* rp_perm, const SmallFactorsDev& sf, const DevCam* cams,
                      const PoseCache* pc, const double* poses, const double* points, const double* objects, int apply_loss, double* residuals,
                      double* sqnorm, double* scal) {
-  if (rp.n > 0) {
-    hipLaunchKernelGGL(k_eval_reproj, dim3(grid_for(rp.n, kBlock)), dim3(kBlock), 0, s, rp, rp_perm, cams, pc, points, apply_loss, residuals, sqnorm, scal, b.deterministic);
-    if (b.deterministic) launch_det_reduce(s, scal, grid_for(rp.n, kBlock), OBVI_SC(SC_COST), b.deterministic);
-  }
-  const int64_t ns = sf.n_bb + sf.n_sp + sf.n_lt + sf.n_rl;
-  if (ns > 0) {
-    double* r_bb = residuals ? residuals + 2 * rp.n : nullptr;
-    double* r_sp = residuals ? r_bb + 4 * sf.n_bb : nullptr;
-    double* r_lt = residuals ? r_sp + 3 * sf.n_sp : nullptr;
-    double* r_rl = residuals ? r_lt + sf.od * sf.n_lt : nullptr;
-    double* q_bb = sqnorm ? sqnorm + rp.n : nullptr;
-    double* q_sp = sqnorm ? q_bb + sf.n_bb : nullptr;
-    double* q_lt = sqnorm ? q_sp + sf.n_sp : nullptr;
-    double* q_rl = sqnorm ? q_lt + sf.n_lt : nullptr;
-    hipLaunchKernelGGL(k_eval_small, dim3(grid_for(ns, 64)), dim3(64), 0, s, sf, cams, poses, objects, apply_loss, r_bb, q_bb, r_sp, q_sp, r_lt, q_lt, r_rl, q_rl, scal, b.deterministic);
-    if (b.deterministic) launch_det_reduce(s, scal, grid_for(ns, 64), OBVI_SC(SC_COST), b.deterministic);
-  }
+  launch_reducing(s, b, scal, eval_reproj_grid(rp.n), OBVI_SC(SC_COST), [&](dim3 g) {
+    hipLaunchKernelGGL(k_eval_reproj, g, dim3(kBlock), 0, s, rp, rp_perm, cams, pc, points, apply_loss, residuals, sqnorm, scal, b.deterministic); });
+  double* r_bb = residuals ? residuals + 2 * rp.n : nullptr;
+  double* r_sp = residuals ? r_bb + 4 * sf.n_bb : nullptr;
+  double* r_lt = residuals ? r_sp + 3 * sf.n_sp : nullptr;
+  double* r_rl = residuals ? r_lt + sf.od * sf.n_lt : nullptr;
+  double* q_bb = sqnorm ? sqnorm + rp.n : nullptr;
+  double* q_sp = sqnorm ? q_bb + sf.n_bb : nullptr;
+  double* q_lt = sqnorm ? q_sp + sf.n_sp : nullptr;
+  double* q_rl = sqnorm ? q_lt + sf.n_lt : nullptr;
+  launch_reducing(s, b, scal, eval_small_grid(sf.n_bb + sf.n_sp + sf.n_lt + sf.n_rl), OBVI_SC(SC_COST), [&](dim3 g) {
+    hipLaunchKernelGGL(k_eval_small, g, dim3(64), 0, s, sf, cams, poses, objects, apply_loss, r_bb, q_bb, r_sp, q_sp, r_lt, q_lt, r_rl, q_rl, scal, b.deterministic); });
 }
 void launch_debug_linearize_reproj(hipStream_t s, const ReprojDev& rp, const uint32_t* rp_perm, const DevCam* cams, const PoseCache* pc,
                                    const double* points, double* r, double* J0, double* J1) {
