@@ -306,7 +306,8 @@ int obvi_ba_debug_linearize(obvi_ba_handle* h, int32_t factor_type, double* r, d
  * for the excluded ones, 1 for the kept active ones, 0 for inactive ones; active may be NULL (all). */
 int obvi_ba_debug_select(obvi_ba_handle* h, int64_t n, const double* sq, const uint8_t* active, double fraction, uint8_t* mask_out, int64_t* num_excluded);
 /* dense reduced (Schur) system at the current estimate for LM diagonal 1/radius:
- * lhs [m][m] row-major symmetric, rhs [m]; order = variable poses then variable objects. */
+ * lhs [m][m] row-major symmetric, rhs [m]; order = variable poses then variable objects.  It is the rank's own system: no
+ * collective runs, even with shared objects and an all-reduce hook set. */
 int obvi_ba_debug_reduced_system(obvi_ba_handle* h, double radius, double* lhs, double* rhs, int32_t m_cap,
                                  int32_t* m_out);
 /* structure of the reduced program after the last evaluate/solve, as doubles:

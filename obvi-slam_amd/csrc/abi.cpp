@@ -254,17 +254,9 @@ int obvi_ba_debug_reduced_system(obvi_ba_handle* h, double radius, double* lhs, 
   prepare(h);
   if (m_out) *m_out = (int32_t)h->m_canon;
   if (h->m_canon > m_cap) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "debug_reduced_system: buffer too small");
+  // the LM step's own assembly, as at a first iteration: the rank's own system (no exchange), without the parameter priors
+  QuietStep quiet(h); assemble_step(h, radius, /*first_iter=*/true, /*schur=*/true, /*exchange=*/false);
   hipStream_t s = h->stream;
-  const BlocksDev b = blocks_dev(h); const ReprojDev rp = reproj_dev(h); const SmallFactorsDev sf = small_dev(h);
-  const ReducedDev rd = reduced_dev(h); const PointDev pt = point_dev(h);
-  launch_pose_cache(s, h->P, h->d_pose.get(), h->d_pc.get(), h->reproj_variant == OBVI_REPROJECTION_ANALYTIC);
-  launch_zero_tiles(s, rd.S, rd.nt, h->d_tiles.get(), h->ntiles, h->d_is_pad.get(), step_clear(h, 0.0));
-  launch_point_pass(s, b, rp, h->d_cams.get(), h->d_pc.get(), h->d_point.get(), rd, pt, radius, 1, h->d_scal.get(), h->d_wave_obs.get(), h->n_point_waves, h->d_long_points.get(), h->n_long_points);
-  launch_pose_pass(s, b, reproj_pose_dev(h), h->d_cams.get(), h->d_pc.get(), h->d_point.get(), rd);
-  launch_small_factors(s, b, sf, h->d_cams.get(), h->d_pose.get(), h->d_obj.get(), rd, h->d_scal.get(), h->knobs.small_lanes_below);
-  launch_reduced_diag(s, b, h->d_pose.get(), h->d_obj.get(), rd, radius, 1, h->d_scal.get());
-  { launch_schur_window(s, h->nchunks, h->schur_twins, b, pt, rd, h->d_row_of_nat.get(), h->d_chunk_ptr.get(), h->d_batch_first.get(), h->d_batch_slot.get(), h->d_chunk_points.get(), h->d_slot_src.get(), h->d_chunk_f0.get(), h->d_chunk_group.get());
-    launch_schur_blocks(s, h->nblk, h->d_blk_row.get(), h->d_blk_col.get(), h->d_blk_ptr.get(), h->d_pair_a.get(), h->d_pair_b.get(), rp.point, pt, rd); }
   const int64_t mc = h->m_canon, nt = h->nt;
   std::vector<double> tiles((size_t)nt * nt * kTile * kTile), hr((size_t)nt * kTile);
   std::vector<int32_t> tl((size_t)2 * h->ntiles);
@@ -303,13 +295,8 @@ int obvi_ba_object_covariances(obvi_ba_handle* h, int64_t n_pairs, const uint32_
   if (h->allreduce != nullptr && !h->h_shared_ov.empty()) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "object_covariances: not available with objects shared across ranks");
   // the undamped reduced system S = J_c^T J_c - (Schur complement of the features) at the current point, factorised: one
   // LM step's linearisation and factorisation with the trust-region radius at infinity (its candidate point is not used)
-  struct QuietStep {   // no phase events for this step; the caches of the LM loop do not survive it (also when a launch throws)
-    obvi_ba_handle* h; int profiling;
-    explicit QuietStep(obvi_ba_handle* hh) : h(hh), profiling(hh->profiling) { h->profiling = 0; h->pc_valid = false; h->tiles_cleared = false; }
-    ~QuietStep() { h->profiling = profiling; h->pc_valid = false; h->tiles_cleared = false; }
-  };
   upload_parameter_prior_diagonals(h);
-  { QuietStep quiet(h); h->use_extra = !h->h_pp_kind.empty(); try { submit_step(h, 1e300, true, true, /*keep_factor=*/true); } catch (...) { h->use_extra = false; throw; } h->use_extra = false; }
+  { QuietStep quiet(h, /*use_extra=*/!h->h_pp_kind.empty()); submit_step(h, 1e300, true, true, /*keep_factor=*/true); }
   if (h->h_scal[SC_CHOL_FAIL] != 0.0 || h->h_scal[SC_NONFINITE] != 0.0 || !std::isfinite(h->h_scal[SC_STEPSQ]))
     return fail(h, OBVI_ERR_NUMERICAL, "object_covariances: the normal equations are rank deficient at the current estimate");
   hipStream_t s = h->stream;
@@ -365,11 +352,7 @@ int obvi_ba_column_sqnorms(obvi_ba_handle* h, double* pose6, double* point3, dou
   { const int vrc = validate_indices(h); if (vrc != OBVI_OK) return vrc; }
   prepare(h);
   // one linearisation as at iteration 0: the Jacobi scale it stores is s = 1 / (1 + sqrt(c)), c the squared column norm
-  {
-    struct Quiet { obvi_ba_handle* h; int profiling; explicit Quiet(obvi_ba_handle* hh) : h(hh), profiling(hh->profiling) { h->profiling = 0; h->pc_valid = false; h->tiles_cleared = false; }
-                   ~Quiet() { h->profiling = profiling; h->pc_valid = false; h->tiles_cleared = false; } } quiet(h);
-    if (h->num_params > 0) submit_step(h, 1e300, true, false);
-  }
+  { QuietStep quiet(h); if (h->num_params > 0) submit_step(h, 1e300, true, false); }
   std::vector<double> sc((size_t)h->m_canon + 1), sl((size_t)3 * h->L + 1);
   std::vector<int32_t> pose_vid((size_t)h->P + 1), obj_vid((size_t)h->O + 1);
   std::vector<uint8_t> point_var((size_t)h->L + 1);

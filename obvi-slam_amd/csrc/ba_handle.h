@@ -4,7 +4,7 @@
 //   abi.cpp     lifetime, evaluate, debug / profiling hooks, covariances, outlier selection, state, multi-GPU switches
 //   upload.cpp  obvi_ba_set_* (parameter blocks, factors, masks)
 //   plan.cpp    the symbolic phase: reduced program, elimination order, Schur work lists, tile plan (prepare_plan), mask-only re-plan
-//   lm.cpp      one LM step on the device (submit_step) and the trust-region loop (obvi_ba_solve)
+//   lm.cpp      one LM step on the device (submit_step: assemble, factor, trial point, publish and wait) and the trust-region loop (obvi_ba_solve)
 #ifndef OBVI_BA_HANDLE_H_
 #define OBVI_BA_HANDLE_H_
 #include "../../include/obvi_ba.h"
@@ -221,7 +221,7 @@ struct obvi_ba_handle {
   // ---- parameter priors (covariance extraction only) ----
   std::vector<uint8_t> h_pp_kind, h_pp_param; std::vector<uint32_t> h_pp_block; std::vector<double> h_pp_mean, h_pp_std;
   DevBuf<double> d_extra_c, d_extra_l;
-  bool use_extra = false;                // the next submit_step adds d_extra_c / d_extra_l to the diagonal (obvi_ba_object_covariances)
+  bool use_extra = false;                // the step adds d_extra_c / d_extra_l to the diagonal (obvi_ba_object_covariances, through QuietStep)
   // ---- last solve ----
   std::vector<obvi_iteration_summary> iterations;
   obvi_allreduce_fn allreduce = nullptr;
@@ -545,6 +545,14 @@ void prepare_plan(obvi_ba_handle* h);
 bool prepare_masks(obvi_ba_handle* h);
 // ---- lm.cpp
 void submit_step(obvi_ba_handle* h, double radius, bool first_iter, bool solve, bool keep_factor = false);
+void assemble_step(obvi_ba_handle* h, double radius, bool first_iter, bool schur, bool exchange);
+// A step outside the LM loop (covariances, column norms, the debug system): no phase events, the LM loop's caches do not survive it, and the
+// parameter priors' diagonals are added (`use_extra`) for this step only -- also when a launch throws.
+struct QuietStep {
+  obvi_ba_handle* h; const int profiling;
+  explicit QuietStep(obvi_ba_handle* hh, bool use_extra = false) : h(hh), profiling(hh->profiling) { h->profiling = 0; h->use_extra = use_extra; h->pc_valid = h->tiles_cleared = false; }
+  ~QuietStep() { h->profiling = profiling; h->use_extra = h->pc_valid = h->tiles_cleared = false; }
+};
 
 inline double scal_gmax(const obvi_ba_handle* h) { double v; std::memcpy(&v, &h->h_scal[SC_GMAX_BITS], sizeof(v)); return v; }
 

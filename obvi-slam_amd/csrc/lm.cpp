@@ -14,25 +14,15 @@ namespace obvi_lib {
 static std::atomic<int> g_active_solves{0};
 struct ActiveSolve { ActiveSolve() { g_active_solves.fetch_add(1, std::memory_order_relaxed); } ~ActiveSolve() { g_active_solves.fetch_sub(1, std::memory_order_relaxed); } };
 
-// One LM step on the device: linearise at the current point, assemble and solve the damped reduced
-// system, form the candidate, evaluate it.  `solve` false: linearisation only (gradient norms).
-void submit_step(obvi_ba_handle* h, double radius, bool first_iter, bool solve, bool keep_factor) {
-  ApiTimer api_timer_("  LM step (submit + wait)");
-  const double t_submit0 = api_times() ? wall_s() : 0.0;
-  hipStream_t s = h->stream;
-  const BlocksDev b = blocks_dev(h);
-  const ReprojDev rp = reproj_dev(h);
-  const SmallFactorsDev sf = small_dev(h);
-  const ReducedDev rd = reduced_dev(h);
-  const PointDev pt = point_dev(h);
-  double* scal = h->d_scal.get();
-  const double fixed = h->h_scal[SC_COST_FIXED];
+// Stage 1 of an LM step, up to the join: linearise and assemble the damped reduced system (`schur` false: no Schur complement; `exchange`: sum the shared objects' blocks)
+void assemble_step(obvi_ba_handle* h, double radius, bool first_iter, bool schur, bool exchange) {
+  hipStream_t s = h->stream; double* scal = h->d_scal.get();
+  const BlocksDev b = blocks_dev(h); const ReprojDev rp = reproj_dev(h); const ReducedDev rd = reduced_dev(h); const PointDev pt = point_dev(h);
   record(h, PH_POSE_CACHE);
   if (!h->pc_valid) launch_pose_cache(s, h->P, h->d_pose.get(), h->d_pc.get(), h->reproj_variant == OBVI_REPROJECTION_ANALYTIC);
   h->pc_valid = true;
-  if (!h->tiles_cleared) launch_zero_tiles(s, rd.S, rd.nt, h->d_tiles.get(), h->ntiles, h->d_is_pad.get(), step_clear(h, fixed));
+  if (!h->tiles_cleared) launch_zero_tiles(s, rd.S, rd.nt, h->d_tiles.get(), h->ntiles, h->d_is_pad.get(), step_clear(h, h->h_scal[SC_COST_FIXED]));
   h->tiles_cleared = false;
-  const bool exchange = h->allreduce != nullptr && !h->h_shared_ov.empty();
   // Fork: the pose-side pass, the small factor families and the diagonal blocks do not depend on the point pass or the
   // Schur complement (everything they share is accumulated with atomics), so they run beside them on the side stream.
   // With a multi-GPU exchange the first collective (the shared objects' blocks) rides on the side stream too: it needs the pose pass and the
@@ -55,7 +45,7 @@ void submit_step(obvi_ba_handle* h, double radius, bool first_iter, bool solve, 
   };
   auto side_small_factors = [&] {
     record(h, PH_SMALL, s2);
-    launch_small_factors(s2, b, sf, h->d_cams.get(), h->d_pose.get(), h->d_obj.get(), rd, scal, h->knobs.small_lanes_below);
+    launch_small_factors(s2, b, small_dev(h), h->d_cams.get(), h->d_pose.get(), h->d_obj.get(), rd, scal, h->knobs.small_lanes_below);
     if (side) record_end(h, PH_SMALL, s2);
   };
   auto side_diagonal = [&] {
@@ -71,7 +61,7 @@ void submit_step(obvi_ba_handle* h, double radius, bool first_iter, bool solve, 
   };
   auto main_schur_window = [&] {
     record(h, PH_SCHUR);
-    if (solve) launch_schur_window(s, h->nchunks, h->schur_twins, b, pt, rd, h->d_row_of_nat.get(), h->d_chunk_ptr.get(), h->d_batch_first.get(), h->d_batch_slot.get(), h->d_chunk_points.get(), h->d_slot_src.get(), h->d_chunk_f0.get(), h->d_chunk_group.get());
+    if (schur) launch_schur_window(s, h->nchunks, h->schur_twins, b, pt, rd, h->d_row_of_nat.get(), h->d_chunk_ptr.get(), h->d_batch_first.get(), h->d_batch_slot.get(), h->d_chunk_points.get(), h->d_slot_src.get(), h->d_chunk_f0.get(), h->d_chunk_group.get());
   };
   auto schur_blocks_on = [&](hipStream_t st) {
     launch_schur_blocks(st, h->nblk, h->d_blk_row.get(), h->d_blk_col.get(), h->d_blk_ptr.get(), h->d_pair_a.get(), h->d_pair_b.get(), rp.point, pt, rd);
@@ -87,7 +77,7 @@ void submit_step(obvi_ba_handle* h, double radius, bool first_iter, bool solve, 
     main_schur_window();
     side_small_factors();
     record(h, PH_SCHUR_BLOCKS);
-    if (solve) schur_blocks_on(s);   // (forked early, the side stream is not ordered behind the point pass whose Z records these pairs read: main stream)
+    if (schur) schur_blocks_on(s);   // (forked early, the side stream is not ordered behind the point pass whose Z records these pairs read: main stream)
     side_diagonal();
     OBVI_HIP(hipEventRecord(h->ev_join, s2));
   } else {
@@ -96,39 +86,46 @@ void submit_step(obvi_ba_handle* h, double radius, bool first_iter, bool solve, 
     side_diagonal();
     // the pairs outside every strip (loop closures, very long tracks) only need the point pass: beside the strip kernel as well (both add
     // to the tile grid with atomics)
-    if (side && solve) schur_blocks_on(s2);
+    if (side && schur) schur_blocks_on(s2);
     if (side) OBVI_HIP(hipEventRecord(h->ev_join, s2));
     main_schur_window();
     record(h, PH_SCHUR_BLOCKS);
-    if (solve && !side) schur_blocks_on(s);
+    if (schur && !side) schur_blocks_on(s);
   }
   if (side) OBVI_HIP(hipStreamWaitEvent(s, h->ev_join, 0));   // join
-  record(h, PH_CHOL);
-  if (solve && h->m > 0) {
-    const CholPlan plan = chol_plan(h);
-    CholTimers timers{&h->ck_pool, &h->ck_tags, 0};
-    CholTimers* tm = h->profiling >= 2 ? &timers : nullptr;
-    if (exchange && h->tail_level0 >= 0) {
-      launch_cholesky_factor(s, plan, 0, h->tail_level0, rd.S, h->d_Linv.get(), rd.rhs, scal, tm);
-      // (2) the rank's own blocks are eliminated: sum the Schur complement onto the shared objects
-      const int64_t ntail = h->nt - h->tail_t0;
-      launch_pack_tail(s, rd, h->tail_t0, h->d_xbuf.get(), 0);
-      if (h->allreduce(h->allreduce_user, h->d_xbuf.get(), ntail * (ntail + 1) / 2 * kTile * kTile + ntail * kTile, 0, s)) throw HipError{hipErrorUnknown, "allreduce hook (shared tail)", __FILE__, __LINE__};
-      launch_pack_tail(s, rd, h->tail_t0, h->d_xbuf.get(), 1);
-      launch_cholesky_factor(s, plan, h->tail_level0, plan.nlevels, rd.S, h->d_Linv.get(), rd.rhs, scal, tm);
-    } else {
-      launch_cholesky_factor(s, plan, 0, plan.nlevels, rd.S, h->d_Linv.get(), rd.rhs, scal, tm);
-    }
-    launch_cholesky_backward(s, plan, rd.S, h->d_Linv.get(), rd.rhs, rd.y, tm);
-    h->ck_used = tm ? timers.used : 0;
+}
+
+// Stage 2: the tile Cholesky and the backward substitution; `exchange`: the shared tail is summed across the ranks between the rank's levels and the tail's.
+static void factor_step(obvi_ba_handle* h, bool solve, bool exchange) {
+  record(h, PH_CHOL); h->ck_used = 0;
+  if (!solve || h->m == 0) return;
+  hipStream_t s = h->stream; const ReducedDev rd = reduced_dev(h); double* scal = h->d_scal.get();
+  const CholPlan plan = chol_plan(h);
+  CholTimers timers{&h->ck_pool, &h->ck_tags, 0};
+  CholTimers* tm = h->profiling >= 2 ? &timers : nullptr;
+  if (exchange && h->tail_level0 >= 0) {
+    launch_cholesky_factor(s, plan, 0, h->tail_level0, rd.S, h->d_Linv.get(), rd.rhs, scal, tm);
+    // (2) the rank's own blocks are eliminated: sum the Schur complement onto the shared objects
+    const int64_t ntail = h->nt - h->tail_t0;
+    launch_pack_tail(s, rd, h->tail_t0, h->d_xbuf.get(), 0);
+    if (h->allreduce(h->allreduce_user, h->d_xbuf.get(), ntail * (ntail + 1) / 2 * kTile * kTile + ntail * kTile, 0, s)) throw HipError{hipErrorUnknown, "allreduce hook (shared tail)", __FILE__, __LINE__};
+    launch_pack_tail(s, rd, h->tail_t0, h->d_xbuf.get(), 1);
+    launch_cholesky_factor(s, plan, h->tail_level0, plan.nlevels, rd.S, h->d_Linv.get(), rd.rhs, scal, tm);
   } else {
-    h->ck_used = 0;
+    launch_cholesky_factor(s, plan, 0, plan.nlevels, rd.S, h->d_Linv.get(), rd.rhs, scal, tm);
   }
+  launch_cholesky_backward(s, plan, rd.S, h->d_Linv.get(), rd.rhs, rd.y, tm);
+  h->ck_used = tm ? timers.used : 0;
+}
+
+// Stage 3: the candidate point and its cost; `exchange`: the step's scalars are summed across the ranks (also without `solve`).
+static void trial_point_step(obvi_ba_handle* h, bool solve, bool exchange) {
+  hipStream_t s = h->stream; const BlocksDev b = blocks_dev(h); double* scal = h->d_scal.get();
   record(h, PH_BACKSUB);
-  if (solve) launch_backsub_apply(s, b, rp, pt, rd, h->d_point.get(), h->d_point_c.get(), h->d_pose.get(), h->d_obj.get(), h->d_pose_c.get(), h->d_obj_c.get(), h->d_pc_c.get(), scal, h->knobs.backsub_lanes);
+  if (solve) launch_backsub_apply(s, b, reproj_dev(h), point_dev(h), reduced_dev(h), h->d_point.get(), h->d_point_c.get(), h->d_pose.get(), h->d_obj.get(), h->d_pose_c.get(), h->d_obj_c.get(), h->d_pc_c.get(), scal, h->knobs.backsub_lanes);
   record(h, PH_APPLY);   // (the candidate poses / objects are formed in the same launch)
   record(h, PH_COST);
-  if (solve) launch_cost(s, b, reproj_pose_dev(h), sf, h->d_cams.get(), h->d_pc.get(), h->d_pose.get(), h->d_point.get(), h->d_obj.get(), h->d_pc_c.get(),
+  if (solve) launch_cost(s, b, reproj_pose_dev(h), small_dev(h), h->d_cams.get(), h->d_pc.get(), h->d_pose.get(), h->d_point.get(), h->d_obj.get(), h->d_pc_c.get(),
                          h->d_pose_c.get(), h->d_point_c.get(), h->d_obj_c.get(), 0, scal);
   record(h, PH_COUNT);
   if (exchange) {   // (3) every rank must take the same decision: the sums and every rank's gradient maximum in one collective
@@ -136,18 +133,20 @@ void submit_step(obvi_ba_handle* h, double radius, bool first_iter, bool solve, 
     if (h->allreduce(h->allreduce_user, h->d_xbuf.get(), (SC_SUM_END - SC_COST) + h->world, 0, s)) throw HipError{hipErrorUnknown, "allreduce hook (scalars)", __FILE__, __LINE__};
     launch_pack_scalars(s, scal, h->d_xbuf.get(), h->rank, h->world, 1);
   }
+}
+
+// Stage 4: hand the scalar block to the host, wait for it, add up the phase / kernel times.  false: a wait time-out, the step must be submitted again.
+static bool publish_and_wait(obvi_ba_handle* h, bool keep_factor, double t_submit0) {
+  hipStream_t s = h->stream;
   const bool poll = h->profiling < 1 && !keep_factor;
+  StepClear c = step_clear(h, h->h_scal[SC_COST_FIXED]);   // (before the copy below lands in h_scal)
+  if (!poll) OBVI_HIP(hipMemcpyAsync(h->h_scal, h->d_scal.get(), sizeof(double) * SC_COUNT, hipMemcpyDeviceToHost, s));
   // the clear of the next LM step does not depend on the accept / reject decision: it runs while the host takes it
   // (not when the caller goes on to use the factor that is in the tiles: covariance extraction) -- and its first workgroup behind the
   // tiles hands the scalar block to the host before it clears it
-  if (poll) {
-    h->scal_seq += 1.0;
-    StepClear c = step_clear(h, fixed);
-    c.pub_host = h->h_scal; c.pub_seq = h->scal_seq;
-    launch_zero_tiles(s, rd.S, rd.nt, h->d_tiles.get(), h->ntiles, h->d_is_pad.get(), c); h->tiles_cleared = true;
-  } else {
-    OBVI_HIP(hipMemcpyAsync(h->h_scal, scal, sizeof(double) * SC_COUNT, hipMemcpyDeviceToHost, s));
-    if (!keep_factor) { launch_zero_tiles(s, rd.S, rd.nt, h->d_tiles.get(), h->ntiles, h->d_is_pad.get(), step_clear(h, fixed)); h->tiles_cleared = true; }
+  if (!keep_factor) {
+    if (poll) { h->scal_seq += 1.0; c.pub_host = h->h_scal; c.pub_seq = h->scal_seq; }
+    launch_zero_tiles(s, h->d_S.get(), h->nt, h->d_tiles.get(), h->ntiles, h->d_is_pad.get(), c); h->tiles_cleared = true;
   }
   if (ApiTimes* t = api_times()) t->add("    LM step: host time until everything is enqueued", 1e3 * (wall_s() - t_submit0));   // the part that threads of one process share the runtime for
   if (poll) wait_scalars(h); else sync(h);
@@ -156,19 +155,14 @@ void submit_step(obvi_ba_handle* h, double radius, bool first_iter, bool solve, 
     // cleared behind it), so the same step is submitted again on the schedule that cannot wait -- and the handle stays on it
     if (!h->fused_potrf) throw HipError{hipErrorLaunchTimeOut, "tile Cholesky: wait time-out on the two-launch schedule", __FILE__, __LINE__};
     h->fused_potrf = false; h->potrf_wait_timeouts++;
-    submit_step(h, radius, first_iter, solve, keep_factor);
-    return;
+    return false;
   }
   for (int p = 0; p < PH_COUNT && h->profiling >= 1; ++p) {   // phase timings are opt-in: a dozen event queries per LM iteration are not free
+    int q = p + 1;
+    while (q < PH_COUNT && h->phase_on_side[q]) ++q;   // next phase boundary on the main stream (a side-stream phase ends at its own event)
     float ms = 0.f;
-    if (h->phase_on_side[p]) { OBVI_HIP(hipEventElapsedTime(&ms, h->ev[p], h->ev_end[p])); }
-    else {
-      int q = p + 1;
-      while (q < PH_COUNT && h->phase_on_side[q]) ++q;   // next phase boundary on the main stream
-      OBVI_HIP(hipEventElapsedTime(&ms, h->ev[p], h->ev[q]));
-    }
-    h->phase_ms[p] += ms;
-    h->phase_launches[p] += 1;
+    OBVI_HIP(hipEventElapsedTime(&ms, h->ev[p], h->phase_on_side[p] ? h->ev_end[p] : h->ev[q]));
+    h->phase_ms[p] += ms; h->phase_launches[p] += 1;
   }
   for (int i = 1; i < h->ck_used; ++i) {   // per-kernel events of the tile Cholesky (profiling level 2)
     const int tag = h->ck_tags[i];
@@ -177,6 +171,19 @@ void submit_step(obvi_ba_handle* h, double radius, bool first_iter, bool solve, 
     OBVI_HIP(hipEventElapsedTime(&ms, h->ck_pool[i - 1], h->ck_pool[i]));
     h->ck_ms[tag] += ms; h->ck_launches[tag] += 1;
   }
+  return true;
+}
+
+// One LM step on the device: linearise at the current point, assemble and solve the damped reduced
+// system, form the candidate, evaluate it.  `solve` false: linearisation only (gradient norms).
+void submit_step(obvi_ba_handle* h, double radius, bool first_iter, bool solve, bool keep_factor) {
+  ApiTimer api_timer_("  LM step (submit + wait)");
+  const double t_submit0 = api_times() ? wall_s() : 0.0;
+  const bool exchange = h->allreduce != nullptr && !h->h_shared_ov.empty();
+  assemble_step(h, radius, first_iter, solve, exchange);
+  factor_step(h, solve, exchange);
+  trial_point_step(h, solve, exchange);
+  if (!publish_and_wait(h, keep_factor, t_submit0)) submit_step(h, radius, first_iter, solve, keep_factor);
 }
 
 }  // namespace obvi_lib

@@ -142,3 +142,19 @@ def test_knobs_are_read_in_one_place_and_documented():
     first_cells = [line.split("|")[1] for line in section.splitlines() if line.startswith("| `OBVI_")]
     table = set(re.findall(r"`(OBVI_[A-Z0-9_]+)`", "\n".join(first_cells))) - {"OBVI_RCCL_JOB", "OBVI_BA_LIBRARY"}
     assert read == table, (sorted(read - table), sorted(table - read))
+
+
+def test_only_the_lm_step_launches_the_assembly():
+    """The kernels that assemble the reduced system are launched from lm.cpp alone (assemble_step): obvi_ba_debug_reduced_system runs the
+    LM step's own stage, not a copy of its launch sequence that the parity tests would check instead of the solver's."""
+    import re
+    csrc = os.path.join(helpers.ROOT, "obvi-slam_amd", "csrc")
+    names = ("launch_point_pass", "launch_pose_pass", "launch_small_factors", "launch_reduced_diag", "launch_schur_window", "launch_schur_blocks")
+    callers = {name: set() for name in names}
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".cpp", ".hip", ".h")):
+            src = open(os.path.join(csrc, f)).read()
+            for name in names:
+                if re.search(r"(?<!void )\b%s\s*\(" % name, src):   # a call, not the declaration or the definition
+                    callers[name].add(f)
+    assert callers == {name: {"lm.cpp"} for name in names}, callers
