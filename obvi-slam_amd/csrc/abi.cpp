@@ -171,7 +171,7 @@ int obvi_ba_reset(obvi_ba_handle* h) {
   for (auto& v : h->ck_launches) v = 0;
   // fused_potrf / potrf_wait_timeouts stay: a wait time-out of the fused kernel is a property of the device and runtime (dispatch order), not of
   // the problem -- a pooled handle that learned it does not pay the on-device wait again at every reuse
-  h->dirty = true; h->mask_dirty = false;
+  h->dirty = true; h->mask_dirty = false; h->cov_valid = false;
   h->err.clear();
   return OBVI_OK;
   OBVI_API_END(h)
@@ -340,6 +340,7 @@ int obvi_ba_set_parameter_priors(obvi_ba_handle* h, int64_t n, const uint8_t* ki
   }
   h->h_pp_kind.assign(kind, kind + n); h->h_pp_block.assign(block, block + n); h->h_pp_param.assign(param, param + n);
   h->h_pp_mean.assign(mean, mean + n); h->h_pp_std.assign(std_dev, std_dev + n);
+  h->cov_valid = false;
   return OBVI_OK;
   OBVI_API_END(h)
 }
@@ -471,6 +472,7 @@ int obvi_ba_restore(obvi_ba_handle* h) {
   OBVI_HIP(hipSetDevice(h->device));
   restore_from(h, h->d_pose_s, h->d_point_s, h->d_obj_s);
   sync(h);
+  h->cov_valid = false;
   return OBVI_OK;
   OBVI_API_END(h)
 }

@@ -316,5 +316,16 @@ void launch_forward_multi(hipStream_t s, const CholPlan& plan, const double* S, 
                           const int32_t* slab_first, const int32_t* obj_row, int32_t nOv, const int32_t* row_split /* host [nlevels]: workgroups per row, or null */, int od = 7);
 void launch_cov_pairs(hipStream_t s, const double* Yt, int64_t ldt, int64_t n_pairs, const int32_t* cols, const int32_t* first_row, double* out, int od = 7);
 
+
+// ---- selected inversion (cov_kernels.hip; include/obvi_cov.h) ---------------------------
+// Sigma = (L L^T)^-1 on the tile pattern of L, in place over the factor the LM step left in S (diagonal tiles: both triangles).  Ys: scratch for the
+// Y tiles of one level (the largest level's off-diagonal tile count); ybase[k]: first scratch tile of column k inside its level.
+void launch_selected_inverse(hipStream_t s, const CholPlan& plan, double* S, const double* Linv, double* Ys, const int32_t* ybase);
+// blocks of Sigma by rows of the tile grid: desc = (first row, first column, rows, columns) per item, a negative row: zero block; item b goes to out + off[b]
+void launch_cov_gather(hipStream_t s, const double* S, int32_t nt, int64_t n, const int32_t* desc, const int64_t* off, double* out);
+// 3x3 feature blocks from Sigma and the point pass's records (Z, Ci): idx = internal feature index per item, negative: zero block; out [n][9]
+void launch_cov_points(hipStream_t s, const double* S, int32_t nt, int64_t n, const int64_t* idx, const uint32_t* point_ptr, const int32_t* yrow, const uint8_t* point_var,
+                       const double* Z, const double* Ci, double* out);
+
 }  // namespace obvi
 #endif  // OBVI_BA_DEVICE_H_

@@ -222,6 +222,17 @@ struct obvi_ba_handle {
   std::vector<uint8_t> h_pp_kind, h_pp_param; std::vector<uint32_t> h_pp_block; std::vector<double> h_pp_mean, h_pp_std;
   DevBuf<double> d_extra_c, d_extra_l;
   bool use_extra = false;                // the step adds d_extra_c / d_extra_l to the diagonal (obvi_ba_object_covariances, through QuietStep)
+  // ---- selected inversion (cov.cpp, include/obvi_cov.h) ----
+  // Sigma = S^-1 on the tile pattern overwrites the factor in d_S; it is what the obvi_cov_* getters read while cov_valid holds.  Everything that
+  // linearises, moves the estimate or changes the priors clears the flag; a change of blocks, factors or masks shows as dirty / mask_dirty.
+  bool cov_valid = false;
+  uint64_t plan_serial = 0, cov_plan_serial = ~(uint64_t)0;   // symbolic plans built so far / the plan the tables below belong to
+  std::vector<uint8_t> h_cov_mask;         // [nt][nt] lower triangle: the tile is on the pattern of L
+  std::vector<int32_t> h_cov_pose_vid;     // pose -> reduced index at the time of obvi_cov_compute (-1: constant or unused)
+  DevBuf<double> d_cov_ys, d_cov_blk;      // Y tiles of one level (allocated by the first obvi_cov_compute); gathered blocks
+  DevBuf<int32_t> d_cov_ybase, d_cov_desc;
+  DevBuf<int64_t> d_cov_off;
+  double cov_ms[2] = {};                   // the last obvi_cov_compute: linearisation + factorisation, selected inversion (wall time)
   // ---- last solve ----
   std::vector<obvi_iteration_summary> iterations;
   obvi_allreduce_fn allreduce = nullptr;
@@ -550,7 +561,7 @@ void assemble_step(obvi_ba_handle* h, double radius, bool first_iter, bool schur
 // parameter priors' diagonals are added (`use_extra`) for this step only -- also when a launch throws.
 struct QuietStep {
   obvi_ba_handle* h; const int profiling;
-  explicit QuietStep(obvi_ba_handle* hh, bool use_extra = false) : h(hh), profiling(hh->profiling) { h->profiling = 0; h->use_extra = use_extra; h->pc_valid = h->tiles_cleared = false; }
+  explicit QuietStep(obvi_ba_handle* hh, bool use_extra = false) : h(hh), profiling(hh->profiling) { h->profiling = 0; h->use_extra = use_extra; h->pc_valid = h->tiles_cleared = false; h->cov_valid = false; }
   ~QuietStep() { h->profiling = profiling; h->use_extra = h->pc_valid = h->tiles_cleared = false; }
 };
 

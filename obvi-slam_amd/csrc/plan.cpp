@@ -981,6 +981,7 @@ struct PlanBuilder {
 
   void remember_what_the_plan_was_built_for() {
     h->dirty = false; h->mask_dirty = false; h->pc_valid = false; h->tiles_cleared = false;
+    h->plan_serial++; h->cov_valid = false;
     h->plan_pose_vid = pose_vid; h->plan_obj_vid = obj_vid; h->plan_point_var = point_var; h->plan_is_pad = h->h_is_pad;
     h->plan_rp_active = h->h_rp_active; h->plan_bb_active = h->h_bb_active; h->plan_sp_active = h->h_sp_active; h->plan_lt_active = h->h_lt_active; h->plan_rl_active = h->h_rl_active;
     h->live_rows = h->m_canon;
@@ -1086,7 +1087,7 @@ bool prepare_masks(obvi_ba_handle* h) {
   h->num_params = h->live_rows + 3 * nL;
   h->num_residuals = nres;
   finish_upload(h);   // (the copies went through the pinned arena: nothing to wait for; the solve's first launches follow on the same stream)
-  h->mask_dirty = false; h->pc_valid = false; h->tiles_cleared = false;
+  h->mask_dirty = false; h->pc_valid = false; h->tiles_cleared = false; h->cov_valid = false;
   return true;
 }
 

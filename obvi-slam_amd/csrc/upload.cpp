@@ -14,6 +14,7 @@ int obvi_ba_set_cameras(obvi_ba_handle* h, int32_t n, const double* K, const dou
   }
   h->d_cams.upload(h->h_cams, h->stream);
   finish_upload(h);
+  h->cov_valid = false;
   bake_bbox(h);   // the bounding-box factors already uploaded follow the new intrinsics
   return OBVI_OK;
   OBVI_API_END(h)
@@ -81,6 +82,7 @@ int obvi_ba_update_points(obvi_ba_handle* h, int64_t n, const double* xyz) {
   h2d_async(h->d_point.get(), xyz, sizeof(double) * 3 * n, h->stream);
   points_to_internal(h, h->d_point);
   finish_upload(h);
+  h->cov_valid = false;
   return OBVI_OK;
   OBVI_API_END(h)
 }
@@ -108,7 +110,7 @@ int obvi_ba_update_state(obvi_ba_handle* h, const double* poses, const double* p
     if ((int64_t)h->h_obj_xy.size() == 2 * h->O) for (int64_t o = 0; o < h->O; ++o) { h->h_obj_xy[2 * o] = objects[h->od * o]; h->h_obj_xy[2 * o + 1] = objects[h->od * o + 1]; }
   }
   finish_upload(h);
-  h->have_snapshot = false;
+  h->have_snapshot = false; h->cov_valid = false;
   return OBVI_OK;
   OBVI_API_END(h)
 }

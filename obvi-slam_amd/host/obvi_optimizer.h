@@ -11,6 +11,9 @@
 #define OBVI_HOST_OPTIMIZER_H_
 
 #include <obvi_ba.h>
+#if !defined(OBVI_TESTS_ORACLE_ABI_SHIM_H_) && !defined(OBVI_TESTS_LOCKSTEP_SHIM_H_)
+#include <obvi_cov.h>   // (libobvi_ba.so only: the oracle-bound drivers are built without it)
+#endif
 
 #include <chrono>
 #include <atomic>
@@ -224,8 +227,53 @@ class Covariance {
     std::copy(it->second.begin(), it->second.end(), covariance_block);
     return true;
   }
+#if !defined(OBVI_TESTS_ORACLE_ABI_SHIM_H_) && !defined(OBVI_TESTS_LOCKSTEP_SHIM_H_)
+  // Frames and features (include/obvi_cov.h: selected inversion; the oracle has no such entry, so the drivers bound to it do not see this part).
+  // A block is named (kind, id): kFrame with a FrameId, kFeature with a FeatureId.  Served: (a, a) for frames and features, and (frame, frame)
+  // pairs joined by a factor or a common feature; any other pair makes Compute fail with the library's message.
+  enum BlockKind { kFrame = 0, kFeature = 1 };
+  using BlockKey = std::pair<BlockKind, uint64_t>;
+  bool Compute(const std::vector<std::pair<BlockKey, BlockKey>>& covariance_blocks, Problem* problem) {
+    keyed_.clear();
+    if (problem == nullptr || problem->handle() == nullptr) return false;
+    obvi_ba_handle* h = problem->handle();
+    const FlatProblem& fp = problem->flat;
+    auto index_of = [&](const BlockKey& k, uint32_t* out) {
+      auto find = [&](const auto& ids) { const auto it = std::lower_bound(ids.begin(), ids.end(), k.second); if (it == ids.end() || (uint64_t)*it != k.second) return false; *out = (uint32_t)(it - ids.begin()); return true; };
+      return k.first == kFrame ? find(fp.frames) : find(fp.features);
+    };
+    auto gather = [](const std::vector<double*>& ptrs, int dim) { std::vector<double> v(ptrs.size() * dim); for (size_t i = 0; i < ptrs.size(); ++i) std::copy_n(ptrs[i], dim, &v[dim * i]); return v; };
+    const std::vector<double> poses = gather(fp.pose_ptrs, 6), points = gather(fp.point_ptrs, 3), objects = gather(fp.object_ptrs, 7);
+    int rc = obvi_ba_set_poses(h, (int64_t)fp.frames.size(), poses.data(), fp.pose_const.data());
+    if (!rc) rc = obvi_ba_set_points(h, (int64_t)fp.features.size(), points.data(), fp.point_const.data());
+    if (!rc) rc = obvi_ba_set_objects(h, (int64_t)fp.objects.size(), objects.data(), fp.object_const.data());
+    if (!rc) rc = obvi_cov_compute(h);
+    for (size_t i = 0; i < covariance_blocks.size() && !rc; ++i) {
+      const BlockKey &a = covariance_blocks[i].first, &b = covariance_blocks[i].second;
+      uint32_t ia = 0, ib = 0;
+      if (!index_of(a, &ia) || !index_of(b, &ib)) { std::cerr << "Covariance::Compute: block is not a parameter block of the problem" << std::endl; return false; }
+      std::vector<double> blk;
+      if (a.first == kFeature && a == b) { blk.resize(9); rc = obvi_cov_point_blocks(h, 1, &ia, blk.data()); }
+      else if (a.first == kFrame && b.first == kFrame) { const uint8_t kind = OBVI_COV_POSE; blk.resize(36); rc = obvi_cov_cross_blocks(h, 1, &kind, &ia, &kind, &ib, blk.data(), nullptr); }
+      else { std::cerr << "Covariance::Compute: cross blocks of features are not served" << std::endl; return false; }
+      if (!rc) keyed_[covariance_blocks[i]] = blk;
+    }
+    if (rc) { std::cerr << "Covariance computation failed: " << obvi_ba_last_error(h) << std::endl; return false; }
+    return true;
+  }
+  // 6x6 (frames) or 3x3 (a feature's own block), row-major
+  bool GetCovarianceBlock(const BlockKey& a, const BlockKey& b, double* covariance_block) const {
+    const auto it = keyed_.find({a, b});
+    if (it == keyed_.end()) return false;
+    std::copy(it->second.begin(), it->second.end(), covariance_block);
+    return true;
+  }
+#endif
  private:
   std::map<std::pair<vslam_types_refactor::ObjectId, vslam_types_refactor::ObjectId>, std::vector<double>> blocks_;
+#if !defined(OBVI_TESTS_ORACLE_ABI_SHIM_H_) && !defined(OBVI_TESTS_LOCKSTEP_SHIM_H_)
+  std::map<std::pair<BlockKey, BlockKey>, std::vector<double>> keyed_;
+#endif
 };
 
 

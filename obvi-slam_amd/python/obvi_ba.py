@@ -275,6 +275,66 @@ class BundleAdjuster:
                                                       _ptr(out, C.c_double)), "object_covariances")
         return out
 
+    # ---- covariance blocks by selected inversion (include/obvi_cov.h; not in the oracle: an oracle-backed adjuster raises) ----
+    def _cov_fn(self, name):
+        try:
+            f = getattr(self._lib, self._pre + name)
+        except AttributeError:
+            raise ObviError("%s%s: this library has no selected-inversion covariance (include/obvi_cov.h is served by libobvi_ba.so only)" % (self._pre, name))
+        f.restype = C.c_int
+        return f
+
+    def covariance_compute(self):
+        """Linearise at the current estimate, factorise the undamped reduced system and invert it on the factor's tile pattern."""
+        self._check(self._cov_fn("cov_compute")(self._h), "cov_compute")
+
+    def _cov_own(self, name, idx, dim):
+        i = np.ascontiguousarray(idx, dtype=np.uint32)
+        out = np.zeros((len(i), dim, dim))
+        self._check(self._cov_fn(name)(self._h, C.c_int64(len(i)), _ptr(i, C.c_uint32), _ptr(out, C.c_double)), name)
+        return out
+
+    def pose_covariances(self, idx):
+        return self._cov_own("cov_pose_blocks", idx, 6)
+
+    def point_covariances(self, idx):
+        return self._cov_own("cov_point_blocks", idx, 3)
+
+    def object_covariance_blocks(self, idx):
+        return self._cov_own("cov_object_blocks", idx, self.od)
+
+    def _cov_pairs(self, kind_a, idx_a, kind_b, idx_b):
+        ia, ib = np.ascontiguousarray(idx_a, dtype=np.uint32), np.ascontiguousarray(idx_b, dtype=np.uint32)
+        ka = np.ascontiguousarray(np.broadcast_to(np.asarray(kind_a, dtype=np.uint8), ia.shape))
+        kb = np.ascontiguousarray(np.broadcast_to(np.asarray(kind_b, dtype=np.uint8), ib.shape))
+        return ka, ia, kb, ib
+
+    def cross_covariances(self, kind_a, idx_a, kind_b, idx_b):
+        """Cross blocks of pairs of poses (kind 0) / objects (kind 2) on the factor's tile pattern: a list of dim(a) x dim(b) arrays."""
+        ka, ia, kb, ib = self._cov_pairs(kind_a, idx_a, kind_b, idx_b)
+        dim = lambda k: np.where(k == 0, 6, self.od).astype(np.int64)
+        sz = dim(ka) * dim(kb)
+        off = np.ascontiguousarray(np.concatenate([[0], np.cumsum(sz)]).astype(np.int64))
+        out = np.zeros(int(off[-1]))
+        self._check(self._cov_fn("cov_cross_blocks")(self._h, C.c_int64(len(ia)), _ptr(ka, C.c_uint8), _ptr(ia, C.c_uint32), _ptr(kb, C.c_uint8), _ptr(ib, C.c_uint32),
+                                                     _ptr(out, C.c_double), _ptr(off, C.c_int64)), "cov_cross_blocks")
+        da, db = dim(ka), dim(kb)
+        return [out[off[i]:off[i + 1]].reshape(da[i], db[i]) for i in range(len(ia))]
+
+    def covariance_on_pattern(self, kind_a, idx_a, kind_b, idx_b):
+        """1 per pair whose cross block cross_covariances can serve."""
+        ka, ia, kb, ib = self._cov_pairs(kind_a, idx_a, kind_b, idx_b)
+        on = np.zeros(len(ia), dtype=np.uint8)
+        self._check(self._cov_fn("cov_on_pattern")(self._h, C.c_int64(len(ia)), _ptr(ka, C.c_uint8), _ptr(ia, C.c_uint32), _ptr(kb, C.c_uint8), _ptr(ib, C.c_uint32),
+                                                   _ptr(on, C.c_uint8)), "cov_on_pattern")
+        return on
+
+    def covariance_stats(self):
+        """(linearise + factorise ms, selected inversion ms, scratch bytes) of the last covariance_compute."""
+        a, b, n = C.c_double(0.0), C.c_double(0.0), C.c_int64(0)
+        self._check(self._cov_fn("cov_get_stats")(self._h, C.byref(a), C.byref(b), C.byref(n)), "cov_get_stats")
+        return a.value, b.value, n.value
+
     def set_parameter_priors(self, block_kind, block_idx, param_idx, mean, std_dev):
         """ParameterPrior factors for the covariance extraction: kind 0 pose / 1 point / 2 object; empty arrays clear them."""
         k = np.ascontiguousarray(block_kind, dtype=np.uint8); b = np.ascontiguousarray(block_idx, dtype=np.uint32)
