@@ -235,7 +235,11 @@ int obvi_ba_select_outliers(obvi_ba_handle* h, int32_t factor_type, double fract
  * GetCovarianceBlock(obj_a, obj_b) returns (long_term_object_map_extraction.cpp:419-433, .h:318-340, 499-513;
  * the independent-ellipsoids extractor asks for (o, o) pairs only).  Blocks of a constant or unobserved object are zero.
  * A rank-deficient problem (free gauge, unobserved feature) fails with OBVI_ERR_NUMERICAL, as Covariance::Compute
- * fails on it.  Computed on the device from the tile Cholesky factor of the undamped reduced system. */
+ * fails on it.  Computed on the device from the tile Cholesky factor of the undamped reduced system.
+ * With objects shared across ranks and an exchange hook (multi-GPU, below) the call is COLLECTIVE: every member of the job calls it (n_pairs = 0
+ * is legal and still takes part), it issues the four collectives obvi_cov.h lists for its compute call, the blocks are those of the JOINT
+ * problem, any pair among the member's private and shared objects is served, and a rank-deficient system on any member returns
+ * OBVI_ERR_NUMERICAL on every member. */
 int obvi_ba_object_covariances(obvi_ba_handle* h, int64_t n_pairs, const uint32_t* obj_a, const uint32_t* obj_b,
                                double* cov49 /*[n_pairs][od*od]*/);
 
@@ -244,7 +248,9 @@ int obvi_ba_object_covariances(obvi_ba_handle* h, int64_t n_pairs, const uint32_
  * for parameters whose Jacobian columns are numerically zero, with mean = the current estimate
  * (src/refactoring/long_term_map/long_term_object_map_extraction.cpp:764-927).  Accordingly they take part in
  * obvi_ba_object_covariances and obvi_ba_column_sqnorms (their Jacobian 1 / std_dev in the parameter's column; the residual is zero
- * at the mean) and NOT in obvi_ba_solve / obvi_ba_evaluate.  block_kind: 0 pose, 1 point, 2 object.  n = 0 clears them. */
+ * at the mean) and NOT in obvi_ba_solve / obvi_ba_evaluate.  block_kind: 0 pose, 1 point, 2 object.  n = 0 clears them.
+ * A prior on an object SHARED across ranks is an object-only factor: exactly one rank uploads it (any rank); it is summed into the joint system once per
+ * rank that uploaded it (obvi_cov.h). */
 int obvi_ba_set_parameter_priors(obvi_ba_handle* h, int64_t n, const uint8_t* block_kind, const uint32_t* block_idx,
                                  const uint8_t* param_idx, const double* mean, const double* std_dev);
 /* Squared column norms of the robustified Jacobian at the current estimate, one per scalar parameter (what findRankDeficiencies
@@ -288,7 +294,9 @@ int obvi_ba_prepare(obvi_ba_handle* h);
  *               that rank's gradient maximum (9 + world doubles), so that every rank takes the same accept / reject decision.
  * (1) is issued on the handle's side stream -- it overlaps the Schur complement of the rank's own blocks --, (2) and (3) on its main
  * stream, always in this order on every rank.  `fn` sums (op 0) or maximises (op 1) `count_f64` doubles in place across ranks --
- * ncclAllReduce on `stream` (a hipStream_t) in a C++ host, torch.distributed.all_reduce from Python.  Non-zero return aborts the solve. */
+ * ncclAllReduce on `stream` (a hipStream_t) in a C++ host, torch.distributed.all_reduce from Python.  Non-zero return aborts the solve.
+ * obvi_ba_object_covariances and the compute call of obvi_cov.h are collective calls on such a handle as well: the 2-double proof of the tail order, then (1), (2), (3)
+ * of one step (obvi_cov.h). */
 typedef int (*obvi_allreduce_fn)(void* user, void* device_buf, int64_t count_f64, int32_t op, void* stream);
 int obvi_ba_set_allreduce(obvi_ba_handle* h, obvi_allreduce_fn fn, void* user);
 /* is_shared[i] != 0: object i is shared across ranks.  rank / world: this handle's position in the job. */

@@ -17,8 +17,36 @@
  * handle's own: the Y tiles of the widest level, allocated by the first obvi_cov_compute (32 KB per off-diagonal tile of that level).
  *
  * The getters are gathers: they read the device result and return; n = 0 is legal.  Nothing throws or aborts; status codes as in
- * obvi_ba.h (rank-deficient normal equations: OBVI_ERR_NUMERICAL; objects shared across ranks with an exchange hook set:
- * OBVI_ERR_INVALID_ARGUMENT, as obvi_ba_object_covariances).  Results are bit-identical from run to run on a deterministic handle.
+ * obvi_ba.h (rank-deficient normal equations: OBVI_ERR_NUMERICAL).  Results are bit-identical from run to run on a deterministic handle.
+ *
+ * OBJECTS SHARED ACROSS RANKS (obvi_ba_set_shared_objects and an exchange hook, obvi_ba.h "multi-GPU"): obvi_cov_compute is then a COLLECTIVE
+ * call, as obvi_ba_solve is -- every member of the job calls it, each on its own host thread, and so is obvi_ba_object_covariances.  A handle
+ * without shared objects or without a hook behaves as described above.  The matrix is that of the JOINT problem of all members.  The shared
+ * objects are eliminated last on every member, so the shared tail is the root of every member's elimination tree: after the members' Schur
+ * complements onto it are summed, every member holds the joint factor of the tail, and the recursion from the root down needs nothing of the
+ * other members' factors.
+ *   Collectives per call, in this order, each issued exactly once by every member (obvi_rccl_group_stats counts four per call):
+ *     (0) 2 doubles, sum: proof that every member lays the shared tail out alike (the check obvi_ba_solve runs first).  A member whose shared
+ *         objects are ordered differently is refused with OBVI_ERR_INVALID_ARGUMENT -- as is every other member, since the sum is the same
+ *         everywhere -- before any tile is summed.
+ *     (1) (od^2 + od) doubles per shared object, sum: their diagonal blocks and gradients, with the members' parameter priors on them.
+ *     (2) the lower tiles and right-hand side of the shared tail, sum: the members' Schur complements onto the shared objects.
+ *     (3) the step's scalar block, sum: it carries the counts of non-positive pivots and non-finite entries, so a rank-deficient or non-finite
+ *         system on ANY member makes EVERY member return OBVI_ERR_NUMERICAL from the same call; no member leaves before (3), none waits alone.
+ *         (A scheduling time-out of the fused factor kernel is summed there too: all members repeat (1)-(3) together.)
+ *   An error that only one member can see before (0) -- cameras not set, indices out of range -- returns on that member at once; the others are
+ *   released by the group's time-out (obvi_rccl_group_set_timeout), which bounds every wait of a collective.
+ *   Parameter priors (obvi_ba_set_parameter_priors) on a SHARED object follow the rule for object-only factors: exactly ONE member uploads them
+ *   (any member).  They travel in (1) and reach the joint tail once per member that uploaded them: the same prior given by two members counts twice.
+ *   Priors on poses, features and private objects stay with their member.
+ *   Results: obvi_cov_object_blocks of a shared object is its block of the joint covariance, the same on every member (bit-identical across
+ *   deterministic members of a group, which sums in member order).  Pose, feature and private-object blocks are marginals of the joint problem,
+ *   not of the member's sub-problem.  obvi_cov_cross_blocks / obvi_cov_on_pattern serve the member's own poses and private objects paired with
+ *   each other and with shared objects wherever the tile pattern has them, and every pair of shared objects; obvi_ba_object_covariances serves
+ *   any pair among the member's private and shared objects.  Indices are per handle: a pair of blocks private to two DIFFERENT members cannot be
+ *   named -- a caller who wants such pairs marks both objects as shared.
+ *   Validity: invalidation is per handle, as above.  A pass describes the joint problem only while NO member has changed state since; a member
+ *   cannot see that a peer did, so after any member changes values, factors, masks, flags or priors, all members call obvi_cov_compute again.
  */
 #ifndef OBVI_COV_H_
 #define OBVI_COV_H_

@@ -291,14 +291,17 @@ int obvi_ba_object_covariances(obvi_ba_handle* h, int64_t n_pairs, const uint32_
   prepare(h);
   const int od = h->od, od2 = od * od;
   std::fill(cov49, cov49 + od2 * n_pairs, 0.0);
-  if (n_pairs == 0 || h->nOv == 0 || h->m == 0) return OBVI_OK;
-  if (h->allreduce != nullptr && !h->h_shared_ov.empty()) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "object_covariances: not available with objects shared across ranks");
+  // objects shared across ranks and an exchange hook: a collective call (include/obvi_ba.h) -- a member with no pairs of its own still takes part in the step's collectives
+  const bool collective = exchanging(h);
+  if ((n_pairs == 0 && !collective) || h->nOv == 0 || h->m == 0) return OBVI_OK;
+  if (collective) { const int trc = prove_tail_order(h, "object_covariances"); if (trc != OBVI_OK) return trc; }
   // the undamped reduced system S = J_c^T J_c - (Schur complement of the features) at the current point, factorised: one
   // LM step's linearisation and factorisation with the trust-region radius at infinity (its candidate point is not used)
   upload_parameter_prior_diagonals(h);
   { QuietStep quiet(h, /*use_extra=*/!h->h_pp_kind.empty()); submit_step(h, 1e300, true, true, /*keep_factor=*/true); }
   if (h->h_scal[SC_CHOL_FAIL] != 0.0 || h->h_scal[SC_NONFINITE] != 0.0 || !std::isfinite(h->h_scal[SC_STEPSQ]))
     return fail(h, OBVI_ERR_NUMERICAL, "object_covariances: the normal equations are rank deficient at the current estimate");
+  if (n_pairs == 0) return OBVI_OK;
   hipStream_t s = h->stream;
   const int nslabs = (int)((od * h->nOv + kTile - 1) / kTile);
   const int64_t ldt = (int64_t)h->nt * kTile, nrhs = (int64_t)nslabs * kTile;   // Y = L^-1 E transposed: [nrhs][ldt]

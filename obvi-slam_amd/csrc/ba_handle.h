@@ -557,6 +557,8 @@ bool prepare_masks(obvi_ba_handle* h);
 // ---- lm.cpp
 void submit_step(obvi_ba_handle* h, double radius, bool first_iter, bool solve, bool keep_factor = false);
 void assemble_step(obvi_ba_handle* h, double radius, bool first_iter, bool schur, bool exchange);
+int prove_tail_order(obvi_ba_handle* h, const char* what);   // first collective of a covariance pass on a handle that exchanges
+inline bool exchanging(const obvi_ba_handle* h) { return h->allreduce != nullptr && !h->h_shared_ov.empty(); }
 // A step outside the LM loop (covariances, column norms, the debug system): no phase events, the LM loop's caches do not survive it, and the
 // parameter priors' diagonals are added (`use_extra`) for this step only -- also when a launch throws.
 struct QuietStep {

@@ -894,7 +894,8 @@ __global__ void __launch_bounds__(kBlock) k_reduced_diag(BlocksDev b, const doub
       const double c = Hd[d * k + k];
       double s;
       if (first_iter) { s = 1.0 / (1.0 + sqrt(c)); rd.scale[crow + k] = s; } else { s = rd.scale[crow + k]; }
-      const double lam = lm_lambda(c, s, radius) + (rd.extra ? rd.extra[crow + k] : 0.0);
+      const bool prior_summed = !is_pose && b.obj_shared != nullptr && b.obj_shared[vid];   // (its parameter priors came with the summed block: k_pack_shared_blocks)
+      const double lam = lm_lambda(c, s, radius) + (rd.extra && !prior_summed ? rd.extra[crow + k] : 0.0);
       rd.lam[crow + k] = lam;
       if (contribute) {
         // atomics: the Schur complement kernels subtract from the same tiles and right-hand side, possibly at the same time (side stream)
@@ -1652,13 +1653,18 @@ __global__ void __launch_bounds__(kBlock) k_fill(double* p, int64_t n, double v)
   for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) p[i] = v;
 }
 
-// multi-GPU exchange (1): (Hdiag od^2 | g od) of the shared objects <-> contiguous buffer (56 doubles per object; 90 with the 9-parameter block)
+// multi-GPU exchange (1): (Hdiag od^2 | g od) of the shared objects <-> contiguous buffer (56 doubles per object; 90 with the 9-parameter block).
+// A covariance pass (rd.extra set): the rank's parameter priors on a shared object ride on the packed block's diagonal, so that the sum holds every rank's priors
+// once each and k_reduced_diag, which adds a shared object's block on one rank only, leaves rd.extra out for them.
 __global__ void __launch_bounds__(128) k_pack_shared_blocks(BlocksDev b, ReducedDev rd, const int32_t* __restrict__ shared_ov, int32_t n_shared, double* buf, int unpack) {
   const int o = blockIdx.x, od = b.od, nh = od * od, n = nh + od;
   if (o >= n_shared || (int)threadIdx.x >= n) return;
   const int32_t ov = shared_ov[o];
-  double* src = (int)threadIdx.x < nh ? rd.Hdiag + 36 * b.nPv + nh * (int64_t)ov + threadIdx.x : rd.g + 6 * b.nPv + od * (int64_t)ov + (threadIdx.x - nh);
-  if (unpack) *src = buf[n * (int64_t)o + threadIdx.x]; else buf[n * (int64_t)o + threadIdx.x] = *src;
+  const int e = (int)threadIdx.x;
+  double* src = e < nh ? rd.Hdiag + 36 * b.nPv + nh * (int64_t)ov + e : rd.g + 6 * b.nPv + od * (int64_t)ov + (e - nh);
+  if (unpack) { *src = buf[n * (int64_t)o + e]; return; }
+  const bool prior = rd.extra != nullptr && e < nh && e / od == e % od;
+  buf[n * (int64_t)o + e] = *src + (prior ? rd.extra[6 * b.nPv + od * (int64_t)ov + e / od] : 0.0);
 }
 // multi-GPU exchange (2): lower tiles (i >= j >= t0) of the tile grid, then rhs rows [t0*64, nt*64)
 __global__ void __launch_bounds__(kBlock) k_pack_tail(ReducedDev rd, int32_t t0, double* buf, int unpack) {

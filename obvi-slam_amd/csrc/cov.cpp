@@ -116,7 +116,9 @@ int obvi_cov_compute(obvi_ba_handle* h) {
   { const int vrc = validate_indices(h); if (vrc != OBVI_OK) return vrc; }
   prepare(h);
   h->cov_valid = false;
-  if (h->allreduce != nullptr && !h->h_shared_ov.empty()) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "cov_compute: not available with objects shared across ranks");
+  // objects shared across ranks and an exchange hook: a collective pass (include/obvi_cov.h).  Collective (0) proves the tail order; the step below issues (1), (2)
+  // and (3) as in a solve, and (3) sums the failure flags, so every member takes the branch below together.
+  if (exchanging(h)) { const int trc = prove_tail_order(h, "cov_compute"); if (trc != OBVI_OK) return trc; }
   hipStream_t s = h->stream;
   const double t0 = wall_s();
   h->cov_ms[0] = h->cov_ms[1] = 0.0;

@@ -186,6 +186,22 @@ void submit_step(obvi_ba_handle* h, double radius, bool first_iter, bool solve, 
   if (!publish_and_wait(h, keep_factor, t_submit0)) submit_step(h, radius, first_iter, solve, keep_factor);
 }
 
+// A collective covariance pass (cov.cpp, obvi_ba_object_covariances) on a handle that exchanges: the proof obvi_ba_solve runs first, as a collective of its
+// own -- 2 doubles, the slot of the fixed cost carrying zero -- so that a pass with no solve before it on the current plan is guarded too and every pass issues
+// the same sequence.  Before the step's stages: a rank whose tail is laid out differently never gets its tiles summed.  OBVI_OK, or the failed status with the message set.
+int prove_tail_order(obvi_ba_handle* h, const char* what) {
+  hipStream_t s = h->stream;
+  static_assert(SC_TAIL_ORDER == SC_COST_FIXED + 1, "summed together");
+  const double pair[2] = {0.0, h->tail_order_hash};
+  h2d_async(h->d_scal.get() + SC_COST_FIXED, pair, sizeof(pair), s);
+  if (h->allreduce(h->allreduce_user, h->d_scal.get() + SC_COST_FIXED, 2, 0, s)) return fail(h, OBVI_ERR_HIP, std::string(what) + ": allreduce hook (tail order)");
+  OBVI_HIP(hipMemcpyAsync(h->h_scal + SC_COST_FIXED, h->d_scal.get() + SC_COST_FIXED, sizeof(pair), hipMemcpyDeviceToHost, s));
+  sync(h);
+  if (h->h_scal[SC_TAIL_ORDER] != (double)h->world * h->tail_order_hash)
+    return fail(h, OBVI_ERR_INVALID_ARGUMENT, std::string(what) + ": the ranks order the shared objects differently -- every rank must upload the shared objects with the same indices and the same values (include/obvi_ba.h, multi-GPU)");
+  return OBVI_OK;
+}
+
 }  // namespace obvi_lib
 
 extern "C" {

@@ -284,6 +284,51 @@ class RcclGroup:
             self._g = C.c_void_p()
 
 
+def run_members(calls, timeout_s=600.0):
+    """One host thread per member of a collective call (obvi_ba_solve, obvi_cov_compute, obvi_ba_object_covariances on handles behind one
+    group): [result or exception per member].  The threads are joined with a time-out; a member that did not come back raises here -- the
+    group's own time-out (RcclGroup.set_timeout) should be shorter, so that a refused member fails every other one first."""
+    import threading
+    out = [None] * len(calls)
+
+    def run(m):
+        try:
+            out[m] = calls[m]()
+        except Exception as e:      # noqa: BLE001 -- handed to the caller, per member
+            out[m] = e
+    th = [threading.Thread(target=run, args=(m,)) for m in range(len(calls))]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join(timeout=timeout_s)
+    if any(t.is_alive() for t in th):
+        raise RuntimeError("a member of the collective call did not return within %.0f s" % timeout_s)
+    return out
+
+
+def joint_long_term_map(handles, shared_ids, cross_pairs=None, timeout_s=600.0):
+    """The long-term map of a CONCURRENT joint solve: every member of the job (`handles`: this rank's, behind one group; the other
+    ranks call this too) runs the collective obvi_cov_compute in a thread of its own, then the shared objects' estimates, their own blocks of
+    the joint covariance and the cross blocks of `cross_pairs` (pairs (a, b) of shared object ids; all of them lie on the tile pattern of the
+    shared tail) are read from member 0 -- every member holds the same.  `shared_ids`: the shared objects' indices, the same on every handle.
+    Returns dict(ids, mean [n, od], cov [n, od, od], cross {(a, b): [od, od]}): what a following session takes as IndependentObjectMapFactor
+    priors (set_ltm_priors(ids, mean, cov.reshape(n, -1), huber))."""
+    import numpy as np
+    ids = np.ascontiguousarray(shared_ids, dtype=np.uint32)
+    res = run_members([h.covariance_compute for h in handles], timeout_s)
+    for r in res:
+        if isinstance(r, Exception):
+            raise r
+    h0 = handles[0]
+    pairs = [(int(a), int(b)) for a, b in (cross_pairs or [])]
+    cross = {}
+    if pairs:
+        a, b = zip(*pairs)
+        kind = np.full(len(pairs), 2, dtype=np.uint8)
+        cross = dict(zip(pairs, h0.cross_covariances(kind, a, kind, b)))
+    return dict(ids=ids, mean=h0.get_objects()[ids], cov=h0.object_covariance_blocks(ids), cross=cross)
+
+
 class HostGroup:
     """The group for libraries whose exchange buffers live in HOST memory (the CPU oracle; tests/test_distributed_gloo.py): k handles of this
     process, one thread each; per collective the last one to arrive sums / maximises the k buffers, runs ONE inter-rank all-reduce

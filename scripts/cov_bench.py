@@ -2,7 +2,10 @@
 """Times obvi_ba_object_covariances on BASELINE config #3 (200 objects, own blocks) and, with --oracle, the CPU restatement
 on a smaller problem of the same shape; with --selinv, the selected-inversion entries of include/obvi_cov.h (compute split into linearise + factorise and
 inversion, reading all pose / feature blocks) beside the merged route and a one-iteration solve, at config #3's sizes and at 500 frames / 50 objects.
-usage: python scripts/cov_bench.py [--oracle] [--selinv]"""
+With --shared K: K sessions of 500 frames / 50 000 features over one shared map of 50 objects behind one group -- the wall time of the COLLECTIVE
+obvi_cov_compute (every member in a thread of its own), split as obvi_cov_get_stats splits it, beside K unshared handles doing the pass on their sessions alone
+and one fused handle holding the joint problem.
+usage: python scripts/cov_bench.py [--oracle] [--selinv] [--shared K]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "obvi-slam_amd", "python"), os.path.join(ROOT, "tests")]
@@ -44,6 +47,78 @@ def selinv_leg(g, prob, label, n=5):
     print("  own object blocks, both routes: max relative difference %.2e; median pose sigma xyz %.3g m" %
           ((np.abs(co - cm).max(axis=(1, 2))[live] / np.abs(cm).max(axis=(1, 2))[live]).max(), np.median(np.sqrt(np.einsum("pii->pi", cp)[:, :3][np.einsum("pii->pi", cp)[:, 0] > 0]))))
 
+
+def shared_leg(K, n=5, O=50):
+    import dist_util
+    warm = obvi_ba.SolverParams(max_num_iterations=6, allow_non_monotonic_steps=True, function_tolerance=1e-6, gradient_tolerance=1e-10,
+                                parameter_tolerance=1e-8, initial_trust_region_radius=1e4, max_trust_region_radius=1e16)
+    sessions = synth.make_sessions(K, P=500, L=50000, O=O, seed0=1000, object_seed=77, const_poses=1, min_obj_obs=10, object_classes=("bench",))
+
+    def members(call, handles):
+        out = dist_util.run_members([lambda h=h: call(h) for h in handles])
+        for o in out:
+            if isinstance(o, Exception):
+                raise o
+        return out
+
+    def timed_pass(handles):
+        members(lambda h: h.covariance_compute(), handles)
+        wall, lin, inv = 0.0, 0.0, 0.0
+        for _ in range(n):
+            t = time.time(); members(lambda h: h.covariance_compute(), handles); wall += (time.time() - t) / n * 1e3
+            st = [h.covariance_stats() for h in handles]
+            lin += max(a for a, _, _ in st) / n; inv += max(b for _, b, _ in st) / n
+        return wall, lin, inv
+
+    def handles_of(problems, group=None):
+        hs = []
+        for m, q in enumerate(problems):
+            ba = obvi_ba.BundleAdjuster(device_id=0); synth.upload(ba, q)
+            if group is not None:
+                group.attach(m, ba, np.ones(O, np.uint8))
+            hs.append(ba)
+        return hs
+    print("%d sessions of 500 frames / 50 000 features over one map of %d objects; wall time per obvi_cov_compute of all members (threads), ms; the split is the slowest member's" % (K, O))
+    group = dist_util.RcclGroup(K); group.set_timeout(120.0)
+    hs = handles_of(sessions, group)
+    members(lambda h: h.solve(warm), hs)
+    c0 = group.stats()[0]
+    wall, lin, inv = timed_pass(hs)
+    per_pass = (group.stats()[0] - c0) / (n + 1)
+    st = hs[0].problem_stats()
+    print("  collective pass behind one group:   %.2f ms = linearise + factorise + %g collectives %.2f + selected inversion %.2f   (%d tile columns, %d levels per member)" %
+          (wall, per_pass, lin, inv, st["tiles_per_dim"], st["chol_levels"]))
+    states = [h.get_state() for h in hs]
+    shared_blocks = hs[0].object_covariance_blocks(np.arange(O))
+    for h in hs:
+        h.close()
+    group.close()
+    alone = []
+    for q, (po, pt, ob) in zip(sessions, states):
+        a = dict(q); a.update(poses=po, points=pt, objects=ob); alone.append(a)
+    hs = handles_of(alone)
+    wall, lin, inv = timed_pass(hs)
+    print("  %d unshared handles, sessions alone:  %.2f ms = linearise + factorise %.2f + selected inversion %.2f" % (K, wall, lin, inv))
+    t = time.time()
+    for _ in range(n):
+        hs[0].covariance_compute()
+    print("  one unshared handle by itself:       %.2f ms" % ((time.time() - t) / n * 1e3))
+    for h in hs:
+        h.close()
+    joint = synth.join_problems(sessions)
+    joint.update(poses=np.concatenate([s[0] for s in states]), points=np.concatenate([s[1] for s in states]), objects=states[0][2])
+    hs = handles_of([joint])
+    wall, lin, inv = timed_pass(hs)
+    st = hs[0].problem_stats()
+    fused_blocks = hs[0].object_covariance_blocks(np.arange(O))
+    print("  one fused handle, the joint problem: %.2f ms = linearise + factorise %.2f + selected inversion %.2f   (%d tile columns, %d levels)" % (wall, lin, inv, st["tiles_per_dim"], st["chol_levels"]))
+    print("  shared object blocks, collective against fused: max relative difference %.2e" % (np.abs(shared_blocks - fused_blocks).max(axis=(1, 2)) / np.abs(fused_blocks).max(axis=(1, 2))).max())
+    hs[0].close()
+
+
+if "--shared" in sys.argv:
+    shared_leg(int(sys.argv[sys.argv.index("--shared") + 1]))
+    sys.exit(0)
 
 if "--selinv" in sys.argv:
     for label, kw in (("500 frames / 50 000 features / 50 objects", dict(P=500, L=50000, O=50, seed=3)), ("config #3: 2000 frames / 300 000 features / 200 objects", dict(P=2000, L=300000, O=200, seed=20241008))):

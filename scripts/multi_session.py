@@ -4,17 +4,57 @@
 = local-BA-sized problem (500 keyframes / 50 000 features) over one shared object set; it starts from the map of session
 s-1 (ellipsoid estimates + marginal covariances as IndependentObjectMapFactor priors), runs the two-phase BA and ends by
 extracting the new map on the device.  Prints per-session times and the map's error against the synthetic truth.
-usage: python scripts/multi_session.py [sessions=16] [objects=200]"""
+usage: python scripts/multi_session.py [sessions=16] [objects=200]
+       python scripts/multi_session.py --concurrent [sessions=4] [objects=50]
+--concurrent: the sessions run at the same time instead, one handle each behind one group, as ONE joint solve over the shared map, and the job ends
+with the map of the joint solve (the collective obvi_cov_compute through dist_util.joint_long_term_map): estimates and joint covariances of the shared objects."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "obvi-slam_amd", "python")]
 import numpy as np
 import obvi_ba, synth
 
-n_sessions = int(sys.argv[1]) if len(sys.argv) > 1 else 16
-n_objects = int(sys.argv[2]) if len(sys.argv) > 2 else 200
+concurrent = "--concurrent" in sys.argv
+args = [a for a in sys.argv[1:] if a != "--concurrent"]
+n_sessions = int(args[0]) if len(args) > 0 else (4 if concurrent else 16)
+n_objects = int(args[1]) if len(args) > 1 else (50 if concurrent else 200)
 prm = obvi_ba.SolverParams(max_num_iterations=50, allow_non_monotonic_steps=True, function_tolerance=1e-4, gradient_tolerance=1e-10,
                            parameter_tolerance=1e-8, initial_trust_region_radius=100.0, max_trust_region_radius=1e4)
+
+def concurrent_sessions():
+    import dist_util
+    t0 = time.time()
+    sessions = synth.make_sessions(n_sessions, P=500, L=50000, O=n_objects, seed0=1000, object_seed=77, const_poses=1, min_obj_obs=10, object_classes=("bench",))
+    t1 = time.time()
+    group = dist_util.RcclGroup(n_sessions)
+    group.set_timeout(120.0)
+    handles = []
+    for m, q in enumerate(sessions):
+        ba = obvi_ba.BundleAdjuster(device_id=0)
+        synth.upload(ba, q)
+        group.attach(m, ba, np.ones(n_objects, np.uint8))
+        handles.append(ba)
+    t2 = time.time()
+    out = dist_util.run_members([lambda h=h: h.solve(prm) for h in handles])
+    for o in out:
+        if isinstance(o, Exception):
+            raise o
+    t3 = time.time()
+    ltm = dist_util.joint_long_term_map(handles, np.arange(n_objects))
+    t4 = time.time()
+    gt = sessions[0]["gt_objects"]
+    err = np.linalg.norm(ltm["mean"][:, :3] - gt[:, :3], axis=1)
+    sd = np.sqrt(np.einsum("oii->oi", ltm["cov"])[:, :3]).mean(axis=1)
+    print("%d concurrent sessions over %d objects: joint solve %.1f ms (%d iterations, final cost %.6e) | joint map %.2f ms (%d collectives in all) | generation %.0f ms, upload %.0f ms | centre error median %.3f m, sigma median %.3f m"
+          % (n_sessions, n_objects, (t3 - t2) * 1e3, out[0].num_iterations, out[0].final_cost, (t4 - t3) * 1e3, group.stats()[0], (t1 - t0) * 1e3, (t2 - t1) * 1e3, np.median(err), np.median(sd)), flush=True)
+    for ba in handles:
+        ba.close()
+    group.close()
+
+
+if concurrent:
+    concurrent_sessions()
+    sys.exit(0)
 ltm = None   # (object ids, means, covariances)
 g = obvi_ba.BundleAdjuster(device_id=0)
 for s in range(n_sessions):
