@@ -75,7 +75,8 @@ int obvi_cov_point_blocks(obvi_ba_handle* h, int64_t n, const uint32_t* point_id
  * Pair i is written at out + out_offset[i] (out_offset NULL: one behind the other in the order given), dim(a) x dim(b) doubles.
  * A pair whose block is not on the tile pattern of the factor is refused with OBVI_ERR_INVALID_ARGUMENT and nothing is written: off
  * the pattern the covariance is not zero, it is not computed (object pairs: obvi_ba_object_covariances serves any pair).
- * obvi_cov_on_pattern answers the question without failing: on[i] = 1 if pair i can be served.  Feature cross blocks are not served. */
+ * obvi_cov_on_pattern answers the question without failing: on[i] = 1 if pair i can be served.  Feature cross blocks are not served.
+ * (Both serve every pair that was declared to obvi_cov_compute_pairs, features included: obvi_cov_pairs.h.) */
 int obvi_cov_cross_blocks(obvi_ba_handle* h, int64_t n, const uint8_t* kind_a, const uint32_t* idx_a, const uint8_t* kind_b,
                           const uint32_t* idx_b, double* out, const int64_t* out_offset);
 int obvi_cov_on_pattern(obvi_ba_handle* h, int64_t n, const uint8_t* kind_a, const uint32_t* idx_a, const uint8_t* kind_b,
@@ -87,4 +88,8 @@ int obvi_cov_get_stats(const obvi_ba_handle* h, double* linearize_factor_ms, dou
 #ifdef __cplusplus
 }
 #endif
+
+/* pairs off the pattern and cross blocks of features, declared up front: the entry that takes the list of wanted pairs */
+#include "obvi_cov_pairs.h"
+
 #endif /* OBVI_COV_H_ */

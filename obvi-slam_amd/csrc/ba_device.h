@@ -327,5 +327,17 @@ void launch_cov_gather(hipStream_t s, const double* S, int32_t nt, int64_t n, co
 void launch_cov_points(hipStream_t s, const double* S, int32_t nt, int64_t n, const int64_t* idx, const uint32_t* point_ptr, const int32_t* yrow, const uint8_t* point_var,
                        const double* Z, const double* Ci, double* out);
 
+// declared pairs off the pattern (obvi_cov_compute_pairs), between the factorisation and the selected inversion: Yt [64 nslabs][ldt = 64 nt] = (L^-1 E)^T for
+// the unit vectors of the rows rhs_row[0 .. nrhs) (ascending; cleared and seeded here), slab_first[sl] = tile row of the slab's first right-hand side
+void launch_cov_forward(hipStream_t s, const CholPlan& plan, const double* S, const double* Linv, double* Yt, int64_t ldt, int nslabs, const int32_t* slab_first,
+                        const int32_t* rhs_row, int32_t nrhs);
+// blocks Yt[ca .. ca + da)  Yt[cb .. cb + db)^T over the columns from first[p] on -> out + off[p], da x db row-major; (da, db) one of (6, 6), (6, od), (od, od)
+void launch_cov_rhs_pairs(hipStream_t s, const double* Yt, int64_t ldt, int64_t n_pairs, int da, int db, const int32_t* cols, const int32_t* first, const int64_t* off, double* out);
+// Blocks with a feature.  Request g = (internal feature l, x, dx, -): dx > 0: x = first row of a reduced block of dx rows, the 3 x dx block (l, x); dx = 0: x = internal
+// feature m != l, the 3 x 3 block (l, m).  ops[op_ptr[g] + e]: where Sigma_{p(a), x} (e = observation a of l) or Sigma_{p(a) p(b)} (e = a * |obs(m)| + b) comes from:
+// -1 the tiles of Sigma, else offset << 1 | transposed into `side`.  Block g -> side + out_off[g].
+void launch_cov_point_cross(hipStream_t s, const double* S, int32_t nt, int64_t n, const int32_t* req, const int64_t* op_ptr, const int64_t* ops, const int64_t* out_off,
+                            const uint32_t* point_ptr, const int32_t* yrow, const double* Z, const double* Ci, double* side);
+
 }  // namespace obvi
 #endif  // OBVI_BA_DEVICE_H_

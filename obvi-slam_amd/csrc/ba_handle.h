@@ -23,6 +23,7 @@
 #include <string>
 #include <system_error>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "ba_device.h"
@@ -233,6 +234,17 @@ struct obvi_ba_handle {
   DevBuf<int32_t> d_cov_ybase, d_cov_desc;
   DevBuf<int64_t> d_cov_off;
   double cov_ms[2] = {};                   // the last obvi_cov_compute: linearisation + factorisation, selected inversion (wall time)
+  // ---- declared pairs (obvi_cov_compute_pairs) ----
+  // canonical pair (kind << 32 | index of each side, the smaller first) -> where its block lies in h_cov_pair_blk: -1 a zero block, else offset << 1 | 1 if
+  // the block is stored as (second, first).  Holds what the getters' own route does not serve: reduced pairs off the tile pattern and pairs with a feature.
+  // Valid while cov_valid holds; every covariance pass rebuilds or clears it.  The device buffers exist only on handles that declared pairs.
+  struct CovPairKey { uint64_t a, b; bool operator==(const CovPairKey& o) const { return a == o.a && b == o.b; } };
+  struct CovPairHash { size_t operator()(const CovPairKey& k) const { return std::hash<uint64_t>()(k.a * 0x9E3779B97F4A7C15ull ^ (k.b + (k.a << 17))); } };
+  std::unordered_map<CovPairKey, int64_t, CovPairHash> h_cov_pairs;
+  std::vector<double> h_cov_pair_blk;      // the side buffer's blocks, read back at the end of the pass
+  DevBuf<double> d_cov_pair_Y, d_cov_side; // Yt = (L^-1 E)^T of the off-pattern blocks' unit vectors; off-pattern reduced blocks, then the feature pairs' blocks
+  DevBuf<int32_t> d_cov_pair_i32;          // tables of the pass, packed
+  DevBuf<int64_t> d_cov_pair_i64;
   // ---- last solve ----
   std::vector<obvi_iteration_summary> iterations;
   obvi_allreduce_fn allreduce = nullptr;

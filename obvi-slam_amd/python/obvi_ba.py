@@ -288,6 +288,12 @@ class BundleAdjuster:
         """Linearise at the current estimate, factorise the undamped reduced system and invert it on the factor's tile pattern."""
         self._check(self._cov_fn("cov_compute")(self._h), "cov_compute")
 
+    def covariance_compute_pairs(self, kind_a, idx_a, kind_b, idx_b):
+        """covariance_compute, after which cross_covariances also serves the pairs declared here: any kinds (0 pose / 1 feature / 2 object), on the pattern or not."""
+        ka, ia, kb, ib = self._cov_pairs(kind_a, idx_a, kind_b, idx_b)
+        self._check(self._cov_fn("cov_compute_pairs")(self._h, C.c_int64(len(ia)), _ptr(ka, C.c_uint8), _ptr(ia, C.c_uint32), _ptr(kb, C.c_uint8), _ptr(ib, C.c_uint32)),
+                    "cov_compute_pairs")
+
     def _cov_own(self, name, idx, dim):
         i = np.ascontiguousarray(idx, dtype=np.uint32)
         out = np.zeros((len(i), dim, dim))
@@ -310,9 +316,10 @@ class BundleAdjuster:
         return ka, ia, kb, ib
 
     def cross_covariances(self, kind_a, idx_a, kind_b, idx_b):
-        """Cross blocks of pairs of poses (kind 0) / objects (kind 2) on the factor's tile pattern: a list of dim(a) x dim(b) arrays."""
+        """Cross blocks of pairs of poses (kind 0) / objects (kind 2) on the factor's tile pattern, and of every pair declared to covariance_compute_pairs
+        (features, kind 1, included): a list of dim(a) x dim(b) arrays."""
         ka, ia, kb, ib = self._cov_pairs(kind_a, idx_a, kind_b, idx_b)
-        dim = lambda k: np.where(k == 0, 6, self.od).astype(np.int64)
+        dim = lambda k: np.where(k == 0, 6, np.where(k == 1, 3, self.od)).astype(np.int64)
         sz = dim(ka) * dim(kb)
         off = np.ascontiguousarray(np.concatenate([[0], np.cumsum(sz)]).astype(np.int64))
         out = np.zeros(int(off[-1]))

@@ -5,7 +5,9 @@ inversion, reading all pose / feature blocks) beside the merged route and a one-
 With --shared K: K sessions of 500 frames / 50 000 features over one shared map of 50 objects behind one group -- the wall time of the COLLECTIVE
 obvi_cov_compute (every member in a thread of its own), split as obvi_cov_get_stats splits it, beside K unshared handles doing the pass on their sessions alone
 and one fused handle holding the joint problem.
-usage: python scripts/cov_bench.py [--oracle] [--selinv] [--shared K]"""
+With --pairs: obvi_cov_compute_pairs (include/obvi_cov_pairs.h) at 500 frames and at config #3 -- off-pattern pose pairs, observed pose-feature pairs and the
+object pairs (o, o + 1) -- beside a plain obvi_cov_compute and obvi_ba_object_covariances on the same object pairs: median and range of the repeated runs.
+usage: python scripts/cov_bench.py [--oracle] [--selinv] [--shared K] [--pairs]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "obvi-slam_amd", "python"), os.path.join(ROOT, "tests")]
@@ -116,8 +118,52 @@ def shared_leg(K, n=5, O=50):
     hs[0].close()
 
 
+def pairs_leg(g, prob, label, n=7):
+    """median [min, max] ms over n runs after a warm-up run"""
+    rng = np.random.default_rng(17)
+    P, O = len(prob["poses"]), len(prob["objects"])
+    def timed(fn):
+        fn(); ts = []
+        for _ in range(n):
+            t = time.perf_counter(); fn(); ts.append((time.perf_counter() - t) * 1e3)
+        return "%8.2f [%7.2f, %7.2f]" % (np.median(ts), min(ts), max(ts))
+    g.covariance_compute()
+    pv = np.flatnonzero(np.abs(g.pose_covariances(np.arange(P))).max(axis=(1, 2)) > 0)
+    a, b = rng.choice(pv, 4000), rng.choice(pv, 4000)
+    off = np.flatnonzero((g.covariance_on_pattern(0, a, 0, b) == 0) & (a != b))[:100]
+    pa, pb = np.concatenate([[pv[0]], a[off]]), np.concatenate([[pv[-1]], b[off]])
+    n_off = int((g.covariance_on_pattern(0, pa, 0, pb) == 0).sum())
+    obs = rng.choice(len(prob["rp_pose"]), 10000, replace=False)
+    oa = np.arange(O - 1)
+    st = g.problem_stats()
+    print("%s: %d tile columns, %d levels; median [min, max] ms over %d runs after a warm-up" % (label, st["tiles_per_dim"], st["chol_levels"], n))
+    print("  obvi_cov_compute                                                  %s" % timed(g.covariance_compute))
+    print("  obvi_cov_compute_pairs, %3d pose pairs (%d off the pattern)        %s" % (len(pa), n_off, timed(lambda: g.covariance_compute_pairs(0, pa, 0, pb))))
+    print("  obvi_cov_compute_pairs, 10 000 observed pose-feature pairs        %s" % timed(lambda: g.covariance_compute_pairs(0, prob["rp_pose"][obs], 1, prob["rp_point"][obs])))
+    print("  obvi_cov_compute_pairs, the %3d object pairs (o, o + 1)            %s" % (len(oa), timed(lambda: g.covariance_compute_pairs(2, oa, 2, oa + 1))))
+    print("  obvi_ba_object_covariances, the same pairs                        %s" % timed(lambda: g.object_covariances(oa, oa + 1)))
+    g.covariance_compute_pairs(2, oa, 2, oa + 1)
+    new = np.array(g.cross_covariances(2, oa, 2, oa + 1)); old = g.object_covariances(oa, oa + 1)
+    print("  the two routes on those pairs: max difference %.2e of the largest entry" % (np.abs(new - old).max() / np.abs(old).max()))
+    g.covariance_compute()
+    print("  (%d of them are off the pattern of the factor)" % int((g.covariance_on_pattern(2, oa, 2, oa + 1) == 0).sum()))
+
+
 if "--shared" in sys.argv:
     shared_leg(int(sys.argv[sys.argv.index("--shared") + 1]))
+    sys.exit(0)
+
+if "--pairs" in sys.argv:
+    only = sys.argv[sys.argv.index("--pairs") + 1] if len(sys.argv) > sys.argv.index("--pairs") + 1 else ""
+    for label, kw in (("500 frames / 50 000 features / 50 objects", dict(P=500, L=50000, O=50, seed=3)), ("config #3: 2000 frames / 300 000 features / 200 objects", dict(P=2000, L=300000, O=200, seed=20241008))):
+        if only and not label.startswith(only):
+            continue
+        pr = synth.make_problem(const_poses=1, min_obj_obs=10, **kw)
+        gg = obvi_ba.BundleAdjuster(device_id=0); synth.upload(gg, pr)
+        gg.solve(obvi_ba.SolverParams(max_num_iterations=10, allow_non_monotonic_steps=True, function_tolerance=1e-6, gradient_tolerance=1e-10,
+                                      parameter_tolerance=1e-8, initial_trust_region_radius=1e4, max_trust_region_radius=1e16))
+        pairs_leg(gg, pr, label)
+        gg.close()
     sys.exit(0)
 
 if "--selinv" in sys.argv:

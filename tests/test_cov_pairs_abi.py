@@ -1,0 +1,26 @@
+"""CPU: obvi_cov_compute_pairs (include/obvi_cov_pairs.h, which include/obvi_cov.h includes) is declared to callers of the covariance header, exported by
+libobvi_ba.so, and refuses null arguments without a device."""
+import ctypes as C
+import os
+import re
+import sys
+
+import helpers
+
+sys.path.insert(0, helpers.ROOT)
+import __graft_entry__ as entry  # noqa: E402
+
+
+def test_the_declared_pairs_entry_is_declared_and_exported():
+    assert entry.abi_symbols("obvi_cov_pairs.h", "obvi_cov_") == ["obvi_cov_compute_pairs"]
+    cov = open(os.path.join(helpers.ROOT, "include", "obvi_cov.h")).read()
+    assert re.search(r'^#include "obvi_cov_pairs.h"', cov, flags=re.M)          # whoever includes the covariance header sees the declaration
+    assert hasattr(C.CDLL(helpers.PRODUCT_LIB), "obvi_cov_compute_pairs")
+
+
+def test_null_arguments_are_refused_without_a_device():
+    lib = C.CDLL(helpers.PRODUCT_LIB)
+    lib.obvi_cov_compute_pairs.restype = C.c_int
+    null = C.c_void_p()
+    assert lib.obvi_cov_compute_pairs(null, C.c_int64(0), null, null, null, null) == -1
+    assert lib.obvi_cov_compute_pairs(null, C.c_int64(1), null, null, null, null) == -1
