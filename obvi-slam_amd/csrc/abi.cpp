@@ -154,6 +154,7 @@ int obvi_ba_reset(obvi_ba_handle* h) {
   if (!rc) rc = obvi_ba_set_shape_priors(h, 0, nullptr, nullptr, nullptr, 1.0);
   if (!rc) rc = obvi_ba_set_ltm_priors(h, 0, nullptr, nullptr, nullptr, 1.0);
   if (!rc) rc = obvi_ba_set_relpose(h, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 1.0);
+  if (!rc) rc = obvi_map_set_pair_priors(h, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1.0);
   if (!rc) rc = obvi_ba_set_poses(h, 0, nullptr, nullptr);
   if (!rc) rc = obvi_ba_set_points(h, 0, nullptr, nullptr);
   if (!rc) rc = obvi_ba_set_objects(h, 0, nullptr, nullptr);
@@ -197,7 +198,7 @@ int obvi_ba_evaluate(obvi_ba_handle* h, int32_t apply_loss, double* cost, double
   { const int vrc = validate_indices(h); if (vrc != OBVI_OK) return vrc; }
   prepare(h);
   hipStream_t s = h->stream;
-  const int64_t nres = obvi_ba_num_residuals(h), nfac = h->n_rp + h->n_bb + h->n_sp + h->n_lt + h->n_rl;
+  const int64_t nres = obvi_ba_num_residuals(h), nfac = h->n_rp + h->n_bb + h->n_sp + h->n_lt + h->n_rl + h->n_mp;
   h->d_eval_res.resize((size_t)nres + 1); h->d_eval_sq.resize((size_t)nfac + 1);
   OBVI_HIP(hipMemsetAsync(h->d_scal.get(), 0, sizeof(double) * SC_COUNT, s));
   launch_pose_cache(s, h->P, h->d_pose.get(), h->d_pc.get(), h->reproj_variant == OBVI_REPROJECTION_ANALYTIC);
@@ -228,6 +229,7 @@ int obvi_ba_debug_linearize(obvi_ba_handle* h, int32_t type, double* r, double* 
     case OBVI_FACTOR_SHAPE_PRIOR: m = 3; d0 = h->od; d1 = 0; n = h->n_sp; break;
     case OBVI_FACTOR_LTM_PRIOR: m = h->od; d0 = h->od; d1 = 0; n = h->n_lt; break;
     case OBVI_FACTOR_REL_POSE: m = 6; d0 = 6; d1 = 6; n = h->n_rl; break;
+    case OBVI_FACTOR_MAP_PAIR_PRIOR: m = 2 * h->od; d0 = h->od; d1 = h->od; n = h->n_mp; break;
     default: return fail(h, OBVI_ERR_INVALID_ARGUMENT, "debug_linearize: unknown factor type");
   }
   DevBuf<double> dr, dJ0, dJ1;
@@ -436,6 +438,7 @@ int obvi_ba_select_outliers(obvi_ba_handle* h, int32_t type, double fraction, ui
     case OBVI_FACTOR_SHAPE_PRIOR: off = h->n_rp + h->n_bb; n = h->n_sp; act = h->d_sp_active.get(); break;
     case OBVI_FACTOR_LTM_PRIOR: off = h->n_rp + h->n_bb + h->n_sp; n = h->n_lt; act = h->d_lt_active.get(); break;
     case OBVI_FACTOR_REL_POSE: off = h->n_rp + h->n_bb + h->n_sp + h->n_lt; n = h->n_rl; act = h->d_rl_active.get(); break;
+    case OBVI_FACTOR_MAP_PAIR_PRIOR: off = h->n_rp + h->n_bb + h->n_sp + h->n_lt + h->n_rl; n = h->n_mp; act = h->d_mp_active.get(); break;
     default: return fail(h, OBVI_ERR_INVALID_ARGUMENT, "select_outliers: unknown factor type");
   }
   run_selection(h, n, h->d_eval_sq.get() + off, act, inv, fraction, mask_out, num_excluded);

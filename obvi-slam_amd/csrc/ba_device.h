@@ -79,7 +79,11 @@ constexpr int kBaBlock = 256;   // threads per workgroup of the ba_kernels.hip k
 inline int64_t blocks_of(int64_t n, int64_t per) { return (n + per - 1) / per; }
 inline int64_t point_pass_grid(int64_t n_waves) { return blocks_of(n_waves, kBaBlock / 64); }   // k_point_pass: a wavefront per piece of the observation list
 inline int64_t point_pass_long_grid(int64_t n_long) { return blocks_of(n_long, kBaBlock); }     // k_point_pass_long: a thread per long-track point
-inline int64_t small_lin_grid(int64_t n_bb, int64_t n_priors, int64_t n_rl) { return blocks_of(n_bb, 4) + blocks_of(n_priors, 64) + blocks_of(n_rl, 4); }   // k_small_lin_lanes: 16 lanes per box / relative pose, one per prior
+// k_small_lin_lanes: 16 lanes per box / relative pose, one per prior; a map pair prior has 2 od rows: 16 lanes (od = 7), 32 (od = 9)
+inline int64_t map_pair_per_block(int64_t od) { return od > 7 ? 2 : 4; }
+inline int64_t small_lin_grid(int64_t n_bb, int64_t n_priors, int64_t n_rl, int64_t n_mp = 0, int64_t od = 7) {
+  return blocks_of(n_bb, 4) + blocks_of(n_priors, 64) + blocks_of(n_rl, 4) + blocks_of(n_mp, map_pair_per_block(od));
+}
 inline int64_t reduced_diag_grid(int64_t P, int64_t O, int64_t od) { return blocks_of((od > 8 ? 16 : 8) * (P + O), kBaBlock); }   // k_reduced_diag: 8 threads per diagonal block, 16 if od > 8
 // k_backsub_apply: `lanes` per feature on at most 2048 workgroups (8 per CU), then a thread per pose / object
 inline int64_t backsub_grid(int64_t L, int64_t P, int64_t O, int lanes) { return std::min<int64_t>(blocks_of(L * lanes, kBaBlock), 2048) + blocks_of(P + O, kBaBlock); }
@@ -87,10 +91,10 @@ inline int64_t cost_grid(int64_t P, int64_t n_obs, int64_t n_small) { return (n_
 inline int64_t eval_reproj_grid(int64_t n_obs) { return blocks_of(n_obs, kBaBlock); }   // k_eval_reproj, k_eval_small: a thread per factor
 inline int64_t eval_small_grid(int64_t n_small) { return blocks_of(n_small, 64); }
 // the largest of those grids (launch_backsub_apply takes at most 32 lanes per feature), at least 1 for an empty problem: the stride is also the mode's flag
-struct DetCounts { int64_t P, L, O, od, n_rp, n_point_waves, n_long_points, n_bb, n_sp, n_lt, n_rl; };
+struct DetCounts { int64_t P, L, O, od, n_rp, n_point_waves, n_long_points, n_bb, n_sp, n_lt, n_rl, n_mp = 0; };
 inline int64_t det_slots_needed(const DetCounts& c) {
-  const int64_t ns = c.n_bb + c.n_sp + c.n_lt + c.n_rl;
-  return std::max<int64_t>({1, point_pass_grid(c.n_point_waves), point_pass_long_grid(c.n_long_points), small_lin_grid(c.n_bb, c.n_sp + c.n_lt, c.n_rl),
+  const int64_t ns = c.n_bb + c.n_sp + c.n_lt + c.n_rl + c.n_mp;
+  return std::max<int64_t>({1, point_pass_grid(c.n_point_waves), point_pass_long_grid(c.n_long_points), small_lin_grid(c.n_bb, c.n_sp + c.n_lt, c.n_rl, c.n_mp, c.od),
                             reduced_diag_grid(c.P, c.O, c.od), backsub_grid(c.L, c.P, c.O, 32), cost_grid(c.P, c.n_rp, ns), eval_reproj_grid(c.n_rp), eval_small_grid(ns)});
 }
 
@@ -145,7 +149,8 @@ struct SmallFactorsDev {    // N <= ~3e4 each; arrays in caller order
   const uint32_t* bbp_ptr; const uint32_t* bbp_idx;     // factors by pose:   [P+1], [n_bb]
   // deterministic mode: the priors and the relative-pose factors go the same way -- per-factor blocks into a scratch (slot = shape prior i,
   // then n_sp + LTM prior i, then n_sp + n_lt + relative-pose factor i; kBbBlk doubles: first block | second block), summed per target
-  // block in list order by k_small_gather.  Targets: objects [0, O), then poses [O, O + P); entry = 2 slot + side (1: the slot's second block)
+  // block in list order by k_small_gather.  Targets: objects [0, O), then poses [O, O + P); entry = 2 slot + side (1: the slot's second block).
+  // A map pair prior i takes two slots behind those, n_sp + n_lt + n_rl + 2 i (object a) and + 2 i + 1 (object b): two object blocks do not fit one
   double* sm_blk; const uint32_t* smt_ptr; const uint32_t* smt_idx;
   // shape priors
   int64_t n_sp; const uint32_t* sp_obj; const double* sp_mean; const double* sp_sqrt_inf; const uint8_t* sp_active; double sp_huber;
@@ -154,6 +159,9 @@ struct SmallFactorsDev {    // N <= ~3e4 each; arrays in caller order
   // relative poses
   int64_t n_rl; const uint32_t* rl_a; const uint32_t* rl_b; const double* rl_t; const double* rl_R; const double* rl_sqrt_inf;
   const uint8_t* rl_active; double rl_huber;
+  // map pair priors (include/obvi_map_prior.h), N = 2 od: mean [n][N] (a's, then b's), W [n][N][N] (r = W d), Lambda = W^T W [n][N][N]
+  int64_t n_mp; const uint32_t* mp_a; const uint32_t* mp_b; const double* mp_mean; const double* mp_W; const double* mp_Lambda;
+  const uint8_t* mp_active; double mp_huber;
 };
 
 struct ReducedDev {         // accumulators of the reduced system

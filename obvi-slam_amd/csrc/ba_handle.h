@@ -8,6 +8,7 @@
 #ifndef OBVI_BA_HANDLE_H_
 #define OBVI_BA_HANDLE_H_
 #include "../../include/obvi_ba.h"
+#include "../../include/obvi_map_prior.h"
 
 #include <algorithm>
 #include <atomic>
@@ -123,13 +124,13 @@ struct obvi_ba_handle {
   std::vector<uint32_t> scr_cursor, scr_wave_obs, scr_long_points, scr_pose_ptr;   // scratch of set_reproj, kept between calls
   std::vector<uint8_t> scr_pose_used, scr_obj_used, scr_point_used, scr_point_var, scr_is_pad; std::vector<int32_t> scr_pose_vid, scr_obj_vid;   // ... of prepare_masks
   double rp_huber = 1.0;
-  int64_t n_bb = 0, n_sp = 0, n_lt = 0, n_rl = 0;
-  std::vector<uint32_t> h_bb_obj, h_bb_pose, h_sp_obj, h_lt_obj, h_rl_a, h_rl_b;
-  std::vector<uint8_t> h_bb_active, h_sp_active, h_lt_active, h_rl_active;
-  double bb_huber = 1.0, bb_invalid = 1e6, sp_huber = 1.0, lt_huber = 1.0, rl_huber = 1.0;
+  int64_t n_bb = 0, n_sp = 0, n_lt = 0, n_rl = 0, n_mp = 0;   // (n_mp: map pair priors, include/obvi_map_prior.h)
+  std::vector<uint32_t> h_bb_obj, h_bb_pose, h_sp_obj, h_lt_obj, h_rl_a, h_rl_b, h_mp_a, h_mp_b;
+  std::vector<uint8_t> h_bb_active, h_sp_active, h_lt_active, h_rl_active, h_mp_active;
+  double bb_huber = 1.0, bb_invalid = 1e6, sp_huber = 1.0, lt_huber = 1.0, rl_huber = 1.0, mp_huber = 1.0;
   // largest block / camera index each factor family refers to (-1: none): re-checked against the current block counts before every
   // evaluate / solve, because blocks and cameras may be re-uploaded (with other counts) after the factors
-  int64_t max_rp_pose = -1, max_rp_point = -1, max_rp_cam = -1, max_bb_obj = -1, max_bb_pose = -1, max_bb_cam = -1, max_sp_obj = -1, max_lt_obj = -1, max_rl_pose = -1;
+  int64_t max_rp_pose = -1, max_rp_point = -1, max_rp_cam = -1, max_bb_obj = -1, max_bb_pose = -1, max_bb_cam = -1, max_sp_obj = -1, max_lt_obj = -1, max_rl_pose = -1, max_mp_obj = -1;
   // bounding boxes as uploaded (pixels, (cov^-1)^1/2): the rectified corners and sqrt_inf on the device depend on the cameras and
   // are re-derived when the cameras change
   std::vector<uint16_t> h_bb_cam;
@@ -162,10 +163,10 @@ struct obvi_ba_handle {
   DevBuf<double2> d_rq_pixel;
   DevBuf<double> d_rq_sigma;
   DevBuf<uint8_t> d_rq_active;
-  DevBuf<uint32_t> d_bb_obj, d_bb_pose, d_sp_obj, d_lt_obj, d_rl_a, d_rl_b;
+  DevBuf<uint32_t> d_bb_obj, d_bb_pose, d_sp_obj, d_lt_obj, d_rl_a, d_rl_b, d_mp_a, d_mp_b;
   DevBuf<uint16_t> d_bb_cam;
-  DevBuf<double> d_bb_rect, d_bb_sqrt_inf, d_sp_mean, d_sp_sqrt_inf, d_lt_mean, d_lt_sqrt_inf, d_rl_t, d_rl_R, d_rl_sqrt_inf;
-  DevBuf<uint8_t> d_bb_active, d_sp_active, d_lt_active, d_rl_active;
+  DevBuf<double> d_bb_rect, d_bb_sqrt_inf, d_sp_mean, d_sp_sqrt_inf, d_lt_mean, d_lt_sqrt_inf, d_rl_t, d_rl_R, d_rl_sqrt_inf, d_mp_mean, d_mp_W, d_mp_Lambda;
+  DevBuf<uint8_t> d_bb_active, d_sp_active, d_lt_active, d_rl_active, d_mp_active;
   DevBuf<double> d_bb_blk;                                    // per-factor blocks of the bounding-box factors (k_bbox_gather)
   DevBuf<double> d_sm_blk; DevBuf<uint32_t> d_smt_ptr, d_smt_idx;   // deterministic mode: the same for the priors and relative-pose factors (k_small_gather)
   int32_t bb_pairs_unique = 1;
@@ -205,7 +206,7 @@ struct obvi_ba_handle {
   // what the plan was built for: variable blocks and active factors.  A later state whose variable blocks and active factors are
   // subsets of these runs on the same plan (rows of dropped blocks become padding, masked observations contribute zeros)
   std::vector<int32_t> plan_pose_vid, plan_obj_vid;
-  std::vector<uint8_t> plan_point_var, plan_is_pad, plan_rp_active, plan_bb_active, plan_sp_active, plan_lt_active, plan_rl_active;
+  std::vector<uint8_t> plan_point_var, plan_is_pad, plan_rp_active, plan_bb_active, plan_sp_active, plan_lt_active, plan_rl_active, plan_mp_active;
   int64_t live_rows = 0;                 // 6 (variable poses) + od (variable objects) of the current state (== m_canon right after a full plan)
   int64_t nPv = 0, nOv = 0, nLv = 0, m = 0, m_canon = 0, num_params = 0, num_residuals = 0;
   int32_t nt = 0;
@@ -403,6 +404,8 @@ inline SmallFactorsDev small_dev(const obvi_ba_handle* h) {
   s.lt_active = h->d_lt_active.get(); s.lt_huber = h->lt_huber;
   s.n_rl = h->n_rl; s.rl_a = h->d_rl_a.get(); s.rl_b = h->d_rl_b.get(); s.rl_t = h->d_rl_t.get(); s.rl_R = h->d_rl_R.get();
   s.rl_sqrt_inf = h->d_rl_sqrt_inf.get(); s.rl_active = h->d_rl_active.get(); s.rl_huber = h->rl_huber;
+  s.n_mp = h->n_mp; s.mp_a = h->d_mp_a.get(); s.mp_b = h->d_mp_b.get(); s.mp_mean = h->d_mp_mean.get(); s.mp_W = h->d_mp_W.get();
+  s.mp_Lambda = h->d_mp_Lambda.get(); s.mp_active = h->d_mp_active.get(); s.mp_huber = h->mp_huber;
   return s;
 }
 inline ReducedDev reduced_dev(const obvi_ba_handle* h) {
@@ -495,6 +498,11 @@ inline int validate_indices(obvi_ba_handle* h) {
   if (h->n_sp > 0 && h->max_sp_obj >= h->O) return bad("shape priors");
   if (h->n_lt > 0 && h->max_lt_obj >= h->O) return bad("long-term-map priors");
   if (h->n_rl > 0 && h->max_rl_pose >= h->P) return bad("relative-pose factors");
+  if (h->n_mp > 0 && h->max_mp_obj >= h->O) return bad("map pair priors");
+  // map pair priors couple two object blocks on one handle; across handles that exchange shared objects they are not built (include/obvi_map_prior.h):
+  // refused here, before the plan and before any collective
+  if (h->n_mp > 0 && h->allreduce != nullptr && std::any_of(h->h_is_shared.begin(), h->h_is_shared.end(), [](uint8_t v) { return v != 0; }))
+    return fail(h, OBVI_ERR_INVALID_ARGUMENT, "map pair priors on a handle that exchanges shared objects: the collective form is not built");
   for (size_t i = 0; i < h->h_pp_kind.size(); ++i) {
     const int64_t cnt = h->h_pp_kind[i] == 0 ? h->P : h->h_pp_kind[i] == 1 ? h->L : h->O;
     if ((int64_t)h->h_pp_block[i] >= cnt) return bad("parameter priors");
@@ -535,7 +543,7 @@ inline void prepare_plan(obvi_ba_handle* h);
 // reallocated when the problem outgrows it -- only between API calls: every call clears the scalars before its first launch.
 inline void ensure_det_slots(obvi_ba_handle* h) {
   if (!h->deterministic) return;
-  const int64_t need = det_slots_needed({h->P, h->L, h->O, h->od, h->n_rp, h->n_point_waves, h->n_long_points, h->n_bb, h->n_sp, h->n_lt, h->n_rl});
+  const int64_t need = det_slots_needed({h->P, h->L, h->O, h->od, h->n_rp, h->n_point_waves, h->n_long_points, h->n_bb, h->n_sp, h->n_lt, h->n_rl, h->n_mp});
   if (need > kDetMaxStride) throw HipError{hipErrorInvalidValue, "deterministic mode: the problem needs more partial-sum slots than kDetMaxStride", __FILE__, __LINE__};
   if (need <= h->det_stride) return;
   int64_t stride = h->knobs.det_min_stride;   // (the tests start small to see the block grow)

@@ -765,14 +765,77 @@ __device__ __forceinline__ void relpose_lin_lanes(int64_t block, const BlocksDev
   if (threadIdx.x == 0) scal_add(scal, b.deterministic, SC_COST, cost);
 }
 
-// the three small-factor families of a small problem in one launch (at this size an iteration's first half is bound by the host's launches)
+// Map pair priors (include/obvi_map_prior.h).  The factor is linear in the raw parameters, so there is no dual arithmetic: lane x of the factor's
+// group owns row x of [a ; b] (N = 2 OD rows: 14 on a 16-lane group, 18 on a 32-lane group -- map_pair_per_block), holds d_x, and forms r_x = W_x d
+// and (Lambda d)_x from the group's d (wave shuffles).  |r|^2 is summed in lane order by every lane alike.  Rows of w Lambda_aa | w Lambda_bb and
+// w Lambda d go to the diagonal blocks (atomics, or the factor's two scratch slots in deterministic mode, zeros included: k_small_gather reads every
+// slot of its lists); the lanes of the later-eliminated object add the off-diagonal block into the lower triangle -- one factor per unordered pair
+// (the upload refuses a second), so that block has one writer in either mode.
+template <int OD>
+__device__ __forceinline__ void map_pair_lin_lanes(int64_t block, const BlocksDev& b, const SmallFactorsDev& sf, const double* __restrict__ objects, const ReducedDev& rd, double* scal) {
+  constexpr int G = OD == 7 ? 16 : 32, N = 2 * OD, NH = OD * (OD + 1) / 2;
+  static_assert(N <= G && NH + OD <= kSmBlk, "a row per lane, a block per scratch slot");
+  const int64_t i = block * (int64_t)(64 / G) + (threadIdx.x / G);
+  const int x = threadIdx.x & (G - 1), base = threadIdx.x & ~(G - 1);
+  const bool in = i < sf.n_mp && x < N, first = x < OD;
+  const int xl = first ? x : x - OD;
+  uint32_t oa = 0, ob = 0;
+  int32_t va = -1, vb = -1;
+  if (i < sf.n_mp && sf.mp_active[i]) { oa = sf.mp_a[i]; ob = sf.mp_b[i]; va = b.obj_vid[oa]; vb = b.obj_vid[ob]; }
+  const bool work = (va >= 0 || vb >= 0) && x < N;
+  const double dx = work ? objects[OD * (int64_t)(first ? oa : ob) + xl] - sf.mp_mean[(int64_t)N * i + x] : 0.0;
+  double d[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) d[k] = __shfl(dx, base + k, 64);
+  const double* Lx = sf.mp_Lambda + (int64_t)(N * N) * i + N * x;   // row x of Lambda (read only where `work`)
+  double rx = 0.0, gx = 0.0;
+  if (work) {
+    const double* Wx = sf.mp_W + (int64_t)(N * N) * i + N * x;
+#pragma unroll
+    for (int k = 0; k < N; ++k) { rx += Wx[k] * d[k]; gx += Lx[k] * d[k]; }
+  }
+  double s = 0.0;
+#pragma unroll
+  for (int k = 0; k < N; ++k) { const double rk = __shfl(rx, base + k, 64); s += rk * rk; }
+  double rho0, w;
+  huber_eval(s, sf.mp_huber, &rho0, &w);
+  double cost = (work && x == 0) ? 0.5 * rho0 : 0.0;
+  const int32_t vid = first ? va : vb;
+  const bool add = work && vid >= 0;
+  if (b.deterministic && in) {
+    double* slot = sf.sm_blk + (int64_t)kSmBlk * (sf.n_sp + sf.n_lt + sf.n_rl + 2 * i + (first ? 0 : 1));
+    for (int y = 0; y <= xl; ++y) slot[xl * (xl + 1) / 2 + y] = add ? w * Lx[(first ? 0 : OD) + y] : 0.0;
+    slot[NH + xl] = add ? w * gx : 0.0;
+  }
+  if (add) {
+    if (!b.deterministic) {
+      double* Hd = rd.Hdiag + 36 * b.nPv + OD * OD * (int64_t)vid;
+      for (int y = 0; y <= xl; ++y) atomic_add_f64(Hd + OD * xl + y, w * Lx[(first ? 0 : OD) + y]);
+      atomic_add_f64(rd.g + 6 * b.nPv + OD * (int64_t)vid + xl, w * gx);
+    }
+    if (va >= 0 && vb >= 0) {
+      const int64_t ra = b.obj_row[va], rb = b.obj_row[vb];
+      const bool b_low = rb > ra;  // lower triangle: the later-eliminated block is the row, and its lanes add the block (it may straddle a tile edge: S_at per entry)
+      if (b_low != first) {
+        const int64_t row = b_low ? rb : ra, col = b_low ? ra : rb;
+#pragma unroll
+        for (int y = 0; y < OD; ++y) atomic_add_f64(S_at(rd.S, rd.nt, row + xl, col + y), w * Lx[(first ? OD : 0) + y]);
+      }
+    }
+  }
+  cost = wave_sum(cost);
+  if (threadIdx.x == 0) scal_add(scal, b.deterministic, SC_COST, cost);
+}
+
+// the four small-factor families of a small problem in one launch (at this size an iteration's first half is bound by the host's launches)
 template <bool STORE, int OD>
 __global__ void __launch_bounds__(64) k_small_lin_lanes(BlocksDev b, SmallFactorsDev sf, const DevCam* __restrict__ cams, const double* __restrict__ poses,
-                                                       const double* __restrict__ objects, ReducedDev rd, double* scal, int nb_bbox, int nb_priors) {
+                                                       const double* __restrict__ objects, ReducedDev rd, double* scal, int nb_bbox, int nb_priors, int nb_relpose) {
   const int blk = blockIdx.x;
   if (blk < nb_bbox) bbox_lin_lanes<STORE, OD>(blk, b, sf, cams, poses, objects, rd, scal);
   else if (blk < nb_bbox + nb_priors) object_priors_lin(blk - nb_bbox, b, sf, objects, rd, scal);
-  else relpose_lin_lanes(blk - nb_bbox - nb_priors, b, sf, poses, rd, scal);
+  else if (blk < nb_bbox + nb_priors + nb_relpose) relpose_lin_lanes(blk - nb_bbox - nb_priors, b, sf, poses, rd, scal);
+  else map_pair_lin_lanes<OD>(blk - nb_bbox - nb_priors - nb_relpose, b, sf, objects, rd, scal);
 }
 
 // The sums behind k_small_lin_lanes<true>: the diagonal blocks.  Workgroups [0, O): one per object, its factors' H_oo | g_o (CSR by
@@ -1415,7 +1478,7 @@ __device__ __forceinline__ void cost_reproj_block(int64_t p, const BlocksDev& b,
   block_accumulate(cost, scal, mode == 0 ? SC_COST_CAND : SC_COST_FIXED, b.deterministic);
 }
 
-// small factors: one kernel, thread ranges [bbox | shape | ltm | relpose]
+// small factors: one kernel, thread ranges [bbox | shape | ltm | relpose | map pair]
 __device__ __forceinline__ void cost_small_block(int64_t block, const BlocksDev& b, const SmallFactorsDev& sf, const DevCam* __restrict__ cams,
                                                  const double* __restrict__ poses, const double* __restrict__ objects, int mode, double* scal) {
   int64_t t = block * (int64_t)kBlock + threadIdx.x;
@@ -1458,6 +1521,14 @@ __device__ __forceinline__ void cost_small_block(int64_t block, const BlocksDev&
       relpose_eval_n<1>(poses + 6 * (int64_t)pa, poses + 6 * (int64_t)pb, sf.rl_t + 3 * i, sf.rl_R + 9 * i, sf.rl_sqrt_inf + 36 * i, res);
       for (int a = 0; a < 6; ++a) s += res[a].v * res[a].v;
       huber_eval(s, sf.rl_huber, &rho0, &w);
+      cost = 0.5 * rho0;
+    }
+  } else if ((t -= sf.n_rl) < sf.n_mp) {
+    const int64_t i = t;
+    const uint32_t oa = sf.mp_a[i], ob = sf.mp_b[i];
+    if (sf.mp_active[i] && (b.obj_vid[oa] >= 0 || b.obj_vid[ob] >= 0) == (mode == 0)) {
+      const double s = map_pair_sqnorm(objects + od * (int64_t)oa, objects + od * (int64_t)ob, sf.mp_mean + 2 * od * i, sf.mp_W + 4 * od * od * i, od);
+      huber_eval(s, sf.mp_huber, &rho0, &w);
       cost = 0.5 * rho0;
     }
   }
@@ -1529,7 +1600,8 @@ __device__ __forceinline__ double finish_eval(double* r, double huber, int apply
 
 __global__ void __launch_bounds__(64) k_eval_small(SmallFactorsDev sf, const DevCam* __restrict__ cams, const double* __restrict__ poses,
                                                   const double* __restrict__ objects, int apply_loss, double* res_bb, double* sq_bb,
-                                                  double* res_sp, double* sq_sp, double* res_lt, double* sq_lt, double* res_rl, double* sq_rl, double* scal, int det) {
+                                                  double* res_sp, double* sq_sp, double* res_lt, double* sq_lt, double* res_rl, double* sq_rl, double* res_mp, double* sq_mp,
+                                                  double* scal, int det) {
   int64_t t = blockIdx.x * 64LL + threadIdx.x;
   const int od = sf.od;
   double cost = 0.0;
@@ -1571,6 +1643,12 @@ __global__ void __launch_bounds__(64) k_eval_small(SmallFactorsDev sf, const Dev
       for (int a = 0; a < 6; ++a) r[a] = res[a].v;
     }
     cost = finish_eval<6>(r, sf.rl_huber, apply_loss, res_rl, sq_rl, i, act);
+  } else if ((t -= sf.n_rl) < sf.n_mp) {
+    const int64_t i = t;
+    double r[18] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const bool act = sf.mp_active[i] != 0;
+    if (act) map_pair_eval(objects + od * (int64_t)sf.mp_a[i], objects + od * (int64_t)sf.mp_b[i], sf.mp_mean + 2 * od * i, sf.mp_W + 4 * od * od * i, r, od);
+    cost = od == 7 ? finish_eval<14>(r, sf.mp_huber, apply_loss, res_mp, sq_mp, i, act) : finish_eval<18>(r, sf.mp_huber, apply_loss, res_mp, sq_mp, i, act);
   }
   cost = wave_sum(cost);
   if (threadIdx.x == 0) scal_add(scal, det, SC_COST, cost);
@@ -1645,6 +1723,15 @@ __global__ void __launch_bounds__(64) k_debug_lin_small(int type, SmallFactorsDe
     for (int a = 0; a < 6; ++a) {
       r_out[6 * i + a] = res[a].v;
       for (int k = 0; k < 6; ++k) { J0[36 * i + 6 * a + k] = res[a].d[k]; J1[36 * i + 6 * a + k] = res[a].d[6 + k]; }
+    }
+  } else if (type == 9 && i < sf.n_mp) {
+    const int n = 2 * od;
+    const double* W = sf.mp_W + (int64_t)(n * n) * i;
+    double r[18];
+    map_pair_eval(objects + od * (int64_t)sf.mp_a[i], objects + od * (int64_t)sf.mp_b[i], sf.mp_mean + n * i, W, r, od);
+    for (int a = 0; a < n; ++a) {
+      r_out[n * i + a] = r[a];
+      for (int k = 0; k < od; ++k) { J0[(int64_t)(n * od) * i + od * a + k] = W[n * a + k]; J1[(int64_t)(n * od) * i + od * a + k] = W[n * a + od + k]; }
     }
   }
 }
@@ -1736,18 +1823,18 @@ void launch_pose_pass(hipStream_t s, const BlocksDev& b, const ReprojPoseDev& rq
 void launch_small_factors(hipStream_t s, const BlocksDev& b, const SmallFactorsDev& sf, const DevCam* cams, const double* poses,
                           const double* objects, const ReducedDev& rd, double* scal, int64_t lanes_below) {
   // few factors (below lanes_below: a sliding window): 16 lanes per factor, the latency of a handful of wavefronts is the whole side stream; one launch
-  const int64_t grid = small_lin_grid(sf.n_bb, sf.n_sp + sf.n_lt, sf.n_rl);
-  const int nb_bbox = (int)small_lin_grid(sf.n_bb, 0, 0), nb_priors = (int)small_lin_grid(0, sf.n_sp + sf.n_lt, 0);
+  const int64_t grid = small_lin_grid(sf.n_bb, sf.n_sp + sf.n_lt, sf.n_rl, sf.n_mp, b.od);
+  const int nb_bbox = (int)small_lin_grid(sf.n_bb, 0, 0), nb_priors = (int)small_lin_grid(0, sf.n_sp + sf.n_lt, 0), nb_relpose = (int)small_lin_grid(0, 0, sf.n_rl);
   if (grid == 0) return;
   // (the bounding-box lanes are compiled per ellipsoid block size: 13 or 15 directions on the factor's 16 lanes)
 #define OBVI_SMALL_LIN(STORE) launch_reducing(s, b, scal, grid, OBVI_SC(SC_COST), [&](dim3 g) { \
-    if (b.od == 9) hipLaunchKernelGGL((k_small_lin_lanes<STORE, 9>), g, dim3(64), 0, s, b, sf, cams, poses, objects, rd, scal, nb_bbox, nb_priors); \
-    else hipLaunchKernelGGL((k_small_lin_lanes<STORE, 7>), g, dim3(64), 0, s, b, sf, cams, poses, objects, rd, scal, nb_bbox, nb_priors); })
+    if (b.od == 9) hipLaunchKernelGGL((k_small_lin_lanes<STORE, 9>), g, dim3(64), 0, s, b, sf, cams, poses, objects, rd, scal, nb_bbox, nb_priors, nb_relpose); \
+    else hipLaunchKernelGGL((k_small_lin_lanes<STORE, 7>), g, dim3(64), 0, s, b, sf, cams, poses, objects, rd, scal, nb_bbox, nb_priors, nb_relpose); })
   if (b.deterministic) {
     // no fp64 atomics on the diagonal blocks: every factor leaves its blocks in a scratch slot, the gathers add them per target in list order
     OBVI_SMALL_LIN(true);
     if (sf.n_bb > 0) hipLaunchKernelGGL(k_bbox_gather, dim3((unsigned)b.O + grid_for(b.P, kBlock / 64)), dim3(kBlock), 0, s, b, sf, rd);
-    if (sf.n_sp + sf.n_lt + sf.n_rl > 0) hipLaunchKernelGGL(k_small_gather, dim3(grid_for(b.O + b.P, kBlock / 64)), dim3(kBlock), 0, s, b, sf, rd);
+    if (sf.n_sp + sf.n_lt + sf.n_rl + sf.n_mp > 0) hipLaunchKernelGGL(k_small_gather, dim3(grid_for(b.O + b.P, kBlock / 64)), dim3(kBlock), 0, s, b, sf, rd);
     return;
   }
   if (sf.n_bb < lanes_below) {
@@ -1801,7 +1888,7 @@ void launch_cost(hipStream_t s, const BlocksDev& b, const ReprojPoseDev& rq, con
   const double* points = mode == 0 ? points_cand : points_cur;
   const double* objects = mode == 0 ? objects_cand : objects_cur;
   const int n_pose_blocks = (int)cost_grid(b.P, rq.n, 0);
-  launch_reducing(s, b, scal, cost_grid(b.P, rq.n, sf.n_bb + sf.n_sp + sf.n_lt + sf.n_rl), mode == 0 ? OBVI_SC(SC_COST_CAND) : OBVI_SC(SC_COST_FIXED), [&](dim3 g) {
+  launch_reducing(s, b, scal, cost_grid(b.P, rq.n, sf.n_bb + sf.n_sp + sf.n_lt + sf.n_rl + sf.n_mp), mode == 0 ? OBVI_SC(SC_COST_CAND) : OBVI_SC(SC_COST_FIXED), [&](dim3 g) {
     if (b.P <= 256) hipLaunchKernelGGL(k_cost<true>, g, dim3(kBlock), 0, s, b, rq, sf, cams, pc, poses, points, objects, mode, n_pose_blocks, scal);   // (few poses: cost_reproj_block)
     else hipLaunchKernelGGL(k_cost<false>, g, dim3(kBlock), 0, s, b, rq, sf, cams, pc, poses, points, objects, mode, n_pose_blocks, scal); });
 }
@@ -1814,12 +1901,14 @@ void launch_evaluate(hipStream_t s, const BlocksDev& b, const ReprojDev& rp, con
   double* r_sp = residuals ? r_bb + 4 * sf.n_bb : nullptr;
   double* r_lt = residuals ? r_sp + 3 * sf.n_sp : nullptr;
   double* r_rl = residuals ? r_lt + sf.od * sf.n_lt : nullptr;
+  double* r_mp = residuals ? r_rl + 6 * sf.n_rl : nullptr;
   double* q_bb = sqnorm ? sqnorm + rp.n : nullptr;
   double* q_sp = sqnorm ? q_bb + sf.n_bb : nullptr;
   double* q_lt = sqnorm ? q_sp + sf.n_sp : nullptr;
   double* q_rl = sqnorm ? q_lt + sf.n_lt : nullptr;
-  launch_reducing(s, b, scal, eval_small_grid(sf.n_bb + sf.n_sp + sf.n_lt + sf.n_rl), OBVI_SC(SC_COST), [&](dim3 g) {
-    hipLaunchKernelGGL(k_eval_small, g, dim3(64), 0, s, sf, cams, poses, objects, apply_loss, r_bb, q_bb, r_sp, q_sp, r_lt, q_lt, r_rl, q_rl, scal, b.deterministic); });
+  double* q_mp = sqnorm ? q_rl + sf.n_rl : nullptr;
+  launch_reducing(s, b, scal, eval_small_grid(sf.n_bb + sf.n_sp + sf.n_lt + sf.n_rl + sf.n_mp), OBVI_SC(SC_COST), [&](dim3 g) {
+    hipLaunchKernelGGL(k_eval_small, g, dim3(64), 0, s, sf, cams, poses, objects, apply_loss, r_bb, q_bb, r_sp, q_sp, r_lt, q_lt, r_rl, q_rl, r_mp, q_mp, scal, b.deterministic); });
 }
 void launch_debug_linearize_reproj(hipStream_t s, const ReprojDev& rp, const uint32_t* rp_perm, const DevCam* cams, const PoseCache* pc,
                                    const double* points, double* r, double* J0, double* J1) {
@@ -1827,7 +1916,7 @@ void launch_debug_linearize_reproj(hipStream_t s, const ReprojDev& rp, const uin
 }
 void launch_debug_linearize_small(hipStream_t s, int factor_type, const SmallFactorsDev& sf, const DevCam* cams, const double* poses,
                                   const double* objects, double* r, double* J0, double* J1) {
-  const int64_t n = factor_type == 2 ? sf.n_bb : factor_type == 3 ? sf.n_sp : factor_type == 4 ? sf.n_lt : sf.n_rl;
+  const int64_t n = factor_type == 2 ? sf.n_bb : factor_type == 3 ? sf.n_sp : factor_type == 4 ? sf.n_lt : factor_type == 5 ? sf.n_rl : sf.n_mp;
   if (n > 0) hipLaunchKernelGGL(k_debug_lin_small, dim3(grid_for(n, 64)), dim3(64), 0, s, factor_type, sf, cams, poses, objects, r, J0, J1);
 }
 __global__ void __launch_bounds__(kBlock) k_permute_rows3(double* __restrict__ dst, const double* __restrict__ src, const uint32_t* __restrict__ map, int64_t n) {

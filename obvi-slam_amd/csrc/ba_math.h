@@ -384,5 +384,30 @@ OBVI_HD void ltm_prior_eval(const double* ell, const double* mean, const double*
   }
 }
 
+
+// Map pair prior (include/obvi_map_prior.h): r = W [x_a - mu_a ; x_b - mu_b], W 2od x 2od row-major (the Jacobian: its left od columns d r / d a,
+// its right od columns d r / d b), mean 2od (a's, then b's).
+OBVI_HD void map_pair_eval(const double* ell_a, const double* ell_b, const double* mean, const double* W, double* r, int od = 7) {
+  const int n = 2 * od;
+  double d[18];
+  for (int k = 0; k < od; ++k) { d[k] = ell_a[k] - mean[k]; d[od + k] = ell_b[k] - mean[od + k]; }
+  for (int i = 0; i < n; ++i) {
+    double acc = 0.0;
+    for (int k = 0; k < n; ++k) acc += W[n * i + k] * d[k];
+    r[i] = acc;
+  }
+}
+// |W d|^2 alone, row by row with d formed on the fly: nothing indexed on the stack (the trial-cost kernel runs on every iteration of every problem)
+OBVI_HD double map_pair_sqnorm(const double* ell_a, const double* ell_b, const double* mean, const double* W, int od = 7) {
+  const int n = 2 * od;
+  double s = 0.0;
+  for (int i = 0; i < n; ++i) {
+    double acc = 0.0;
+    for (int k = 0; k < od; ++k) acc += W[n * i + k] * (ell_a[k] - mean[k]) + W[n * i + od + k] * (ell_b[k] - mean[od + k]);
+    s += acc * acc;
+  }
+  return s;
+}
+
 }  // namespace obvi
 #endif  // OBVI_BA_MATH_H_

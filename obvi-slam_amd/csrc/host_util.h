@@ -11,6 +11,7 @@
 #include <sched.h>
 #endif
 
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <condition_variable>
@@ -226,11 +227,12 @@ class HostPool {
   bool stop_ = false;
 };
 
-// out = (sym(cov))^(-1/2) for an n x n (n <= 9) symmetric positive definite matrix, row-major.
+// out = (sym(cov))^(-1/2) for an n x n (n <= 18) symmetric positive definite matrix, row-major.  rel_floor > 0: also refuse a matrix whose smallest
+// eigenvalue is not above rel_floor x the largest (numerically singular: a tiny positive pivot of rounding would become an enormous weight).
 // One-sided view: eigen-decomposition by threshold-free cyclic Jacobi sweeps on a working copy,
 // then out = sum_k v_k v_k^T / sqrt(lambda_k).  Returns false when cov is not finite / not SPD.
-inline bool sym_inverse_sqrt(const double* cov, int n, double* out) {
-  double a[9][9], v[9][9];
+inline bool sym_inverse_sqrt(const double* cov, int n, double* out, double rel_floor = 0.0) {
+  double a[18][18], v[18][18];   // n <= 18: the joint covariance of two 9-parameter ellipsoid blocks
   for (int i = 0; i < n; ++i)
     for (int j = 0; j < n; ++j) {
       a[i][j] = 0.5 * (cov[i * n + j] + cov[j * n + i]);
@@ -255,13 +257,49 @@ inline bool sym_inverse_sqrt(const double* cov, int n, double* out) {
         for (int k = 0; k < n; ++k) { const double x = v[k][p], y = v[k][q]; v[k][p] = c * x - s * y; v[k][q] = s * x + c * y; }
       }
   }
-  for (int k = 0; k < n; ++k) if (!(a[k][k] > 0.0)) return false;
+  double ev_max = 0.0;
+  for (int k = 0; k < n; ++k) ev_max = std::max(ev_max, a[k][k]);
+  for (int k = 0; k < n; ++k) if (!(a[k][k] > rel_floor * ev_max)) return false;
   for (int i = 0; i < n; ++i)
     for (int j = 0; j < n; ++j) {
       double acc = 0.0;
       for (int k = 0; k < n; ++k) acc += v[i][k] * v[j][k] / std::sqrt(a[k][k]);
       out[i * n + j] = acc;
     }
+  return true;
+}
+
+
+// Map pair prior (include/obvi_map_prior.h): from the pair's joint covariance C = [[A, B], [B^T, D]] (N x N row-major, N = 2 od, symmetrised as for the
+// other priors) the matrix W of r = W d and the information Lambda = W^T W.  Joint form: W = C^-1/2.  Conditional form p(b | a): K = B^T A^-1,
+// S_c = D - K B, rows [0, od) of W zero, rows [od, N) = S_c^-1/2 [-K, I].  false: C is not positive definite (either form needs the whole of it), or
+// numerically singular: condition number above 1e13, where an fp64 inverse keeps no more than three digits -- a joint covariance assembled from computed
+// blocks can be that close to singular, and its information would be an artefact of rounding.
+inline bool map_pair_weights(const double* C, int od, bool joint, double* W, double* Lambda) {
+  const int N = 2 * od;
+  double Ci[18 * 18];
+  constexpr double kFloor = 1e-13;
+  if (!sym_inverse_sqrt(C, N, Ci, kFloor)) return false;
+  std::fill(W, W + N * N, 0.0);
+  if (joint) {
+    std::copy(Ci, Ci + N * N, W);
+  } else {
+    double A[81], Ais[81], Ainv[81], K[81], Sc[81], Scis[81];
+    for (int x = 0; x < od; ++x) for (int y = 0; y < od; ++y) A[od * x + y] = C[N * x + y];
+    if (!sym_inverse_sqrt(A, od, Ais, kFloor)) return false;
+    for (int x = 0; x < od; ++x) for (int y = 0; y < od; ++y) { double acc = 0.0; for (int k = 0; k < od; ++k) acc += Ais[od * x + k] * Ais[od * k + y]; Ainv[od * x + y] = acc; }
+    auto Bt = [&](int x, int k) { return 0.5 * (C[N * (od + x) + k] + C[N * k + od + x]); };   // B^T: the lower-left block
+    for (int x = 0; x < od; ++x) for (int y = 0; y < od; ++y) { double acc = 0.0; for (int k = 0; k < od; ++k) acc += Bt(x, k) * Ainv[od * k + y]; K[od * x + y] = acc; }
+    for (int x = 0; x < od; ++x) for (int y = 0; y < od; ++y) { double acc = 0.0; for (int k = 0; k < od; ++k) acc += K[od * x + k] * Bt(y, k); Sc[od * x + y] = C[N * (od + x) + od + y] - acc; }
+    if (!sym_inverse_sqrt(Sc, od, Scis, kFloor)) return false;
+    for (int x = 0; x < od; ++x)
+      for (int y = 0; y < od; ++y) {
+        double acc = 0.0;
+        for (int k = 0; k < od; ++k) acc += Scis[od * x + k] * K[od * k + y];
+        W[N * (od + x) + y] = -acc; W[N * (od + x) + od + y] = Scis[od * x + y];
+      }
+  }
+  for (int x = 0; x < N; ++x) for (int y = 0; y <= x; ++y) { double acc = 0.0; for (int k = 0; k < N; ++k) acc += W[N * k + x] * W[N * k + y]; Lambda[N * x + y] = Lambda[N * y + x] = acc; }
   return true;
 }
 

@@ -118,6 +118,15 @@ struct PlanBuilder {
       if (!ca) pose_used[a] = 1;
       if (!cb) pose_used[b] = 1;
     }
+    for (int64_t i = 0; i < h->n_mp; ++i) {   // map pair priors: an object they alone touch is a variable of the solve
+      if (!h->h_mp_active[i]) continue;
+      const uint32_t a = h->h_mp_a[i], b = h->h_mp_b[i];
+      const bool ca = h->h_object_const[a], cb = h->h_object_const[b];
+      if (ca && cb) continue;
+      nres += 2 * h->od;
+      if (!ca) obj_used[a] = 1;
+      if (!cb) obj_used[b] = 1;
+    }
     if (!h->h_is_shared.empty()) for (int64_t o = 0; o < O; ++o) if (h->h_is_shared[o]) obj_used[o] = 1;   // shared objects exist on every rank
     pose_vid.assign((size_t)P, -1); obj_vid.assign((size_t)O, -1);
     point_var.assign((size_t)L, 0);
@@ -660,6 +669,11 @@ struct PlanBuilder {
       const int32_t va = pose_vid[h->h_rl_a[i]], vb = pose_vid[h->h_rl_b[i]];
       if (va >= 0 && vb >= 0 && va != vb) mark(h->h_pose_row[std::max(va, vb)], 6, h->h_pose_row[std::min(va, vb)], 6);
     }
+    for (int64_t i = 0; i < h->n_mp; ++i) {   // the object-object block of a map pair prior: its row is the later-eliminated object
+      if (!h->h_mp_active[i]) continue;
+      const int32_t va = obj_vid[h->h_mp_a[i]], vb = obj_vid[h->h_mp_b[i]];
+      if (va >= 0 && vb >= 0) { const int64_t ra = h->h_obj_row[va], rb = h->h_obj_row[vb]; mark(std::max(ra, rb), h->od, std::min(ra, rb), h->od); }
+    }
     // object diagonal blocks may straddle tiles
     for (int64_t w = 0; w < h->nOv; ++w) mark(h->h_obj_row[w], h->od, h->h_obj_row[w], h->od);
     for (int64_t v = 0; v < nPv; ++v) mark(h->h_pose_row[v], 6, h->h_pose_row[v], 6);
@@ -927,11 +941,12 @@ struct PlanBuilder {
       h->d_bb_blk.resize((size_t)(h->od * (h->od + 1) / 2 + h->od + 27) * (size_t)h->n_bb + 1);   // BbSlot<OD>::kBlk: 62, 81
       if (h->deterministic) {
         // priors and relative-pose factors by target block (objects, then poses), in factor order: entry = 2 slot + side
-        const int64_t nsl = h->n_sp + h->n_lt + h->n_rl;
+        const int64_t nsl = h->n_sp + h->n_lt + h->n_rl + 2 * h->n_mp;   // (a map pair prior: a slot per object)
         std::vector<uint32_t> tptr((size_t)O + (size_t)P + 1, 0), tidx;
         for (int64_t i = 0; i < h->n_sp; ++i) tptr[h->h_sp_obj[i] + 1]++;
         for (int64_t i = 0; i < h->n_lt; ++i) tptr[h->h_lt_obj[i] + 1]++;
         for (int64_t i = 0; i < h->n_rl; ++i) { tptr[O + h->h_rl_a[i] + 1]++; tptr[O + h->h_rl_b[i] + 1]++; }
+        for (int64_t i = 0; i < h->n_mp; ++i) { tptr[h->h_mp_a[i] + 1]++; tptr[h->h_mp_b[i] + 1]++; }
         for (size_t t = 0; t + 1 < tptr.size(); ++t) tptr[t + 1] += tptr[t];
         tidx.resize(tptr.back() + 1);
         std::vector<uint32_t> cur(tptr.begin(), tptr.end() - 1);
@@ -940,6 +955,10 @@ struct PlanBuilder {
         for (int64_t i = 0; i < h->n_rl; ++i) {
           tidx[cur[O + h->h_rl_a[i]]++] = (uint32_t)(2 * (h->n_sp + h->n_lt + i));
           tidx[cur[O + h->h_rl_b[i]]++] = (uint32_t)(2 * (h->n_sp + h->n_lt + i) + 1);
+        }
+        for (int64_t i = 0; i < h->n_mp; ++i) {   // first blocks of the factor's two slots
+          tidx[cur[h->h_mp_a[i]]++] = (uint32_t)(2 * (h->n_sp + h->n_lt + h->n_rl + 2 * i));
+          tidx[cur[h->h_mp_b[i]]++] = (uint32_t)(2 * (h->n_sp + h->n_lt + h->n_rl + 2 * i + 1));
         }
         h->d_smt_ptr.upload(tptr, s); h->d_smt_idx.upload(tidx, s);
         h->d_sm_blk.resize((size_t)62 * (size_t)nsl + 1);
@@ -983,7 +1002,7 @@ struct PlanBuilder {
     h->dirty = false; h->mask_dirty = false; h->pc_valid = false; h->tiles_cleared = false;
     h->plan_serial++; h->cov_valid = false;
     h->plan_pose_vid = pose_vid; h->plan_obj_vid = obj_vid; h->plan_point_var = point_var; h->plan_is_pad = h->h_is_pad;
-    h->plan_rp_active = h->h_rp_active; h->plan_bb_active = h->h_bb_active; h->plan_sp_active = h->h_sp_active; h->plan_lt_active = h->h_lt_active; h->plan_rl_active = h->h_rl_active;
+    h->plan_rp_active = h->h_rp_active; h->plan_bb_active = h->h_bb_active; h->plan_sp_active = h->h_sp_active; h->plan_lt_active = h->h_lt_active; h->plan_rl_active = h->h_rl_active; h->plan_mp_active = h->h_mp_active;
     h->live_rows = h->m_canon;
   }
 };
@@ -1011,7 +1030,7 @@ bool prepare_masks(obvi_ba_handle* h) {
     return true;
   };
   if (h->h_rp_active.size() != h->plan_rp_active.size() || !subset(h->h_bb_active, h->plan_bb_active) || !subset(h->h_sp_active, h->plan_sp_active) ||
-      !subset(h->h_lt_active, h->plan_lt_active) || !subset(h->h_rl_active, h->plan_rl_active)) return false;
+      !subset(h->h_lt_active, h->plan_lt_active) || !subset(h->h_rl_active, h->plan_rl_active) || !subset(h->h_mp_active, h->plan_mp_active)) return false;
   // (scratch kept between calls: a session runs this once per frame)
   std::vector<uint8_t>& pose_used = h->scr_pose_used; std::vector<uint8_t>& obj_used = h->scr_obj_used; std::vector<uint8_t>& point_used = h->scr_point_used;
   pose_used.assign(P, 0); obj_used.assign(O, 0); point_used.assign(L, 0);
@@ -1050,6 +1069,15 @@ bool prepare_masks(obvi_ba_handle* h) {
     nres += 6;
     if (!ca) pose_used[a] = 1;
     if (!cb) pose_used[b] = 1;
+  }
+  for (int64_t i = 0; i < h->n_mp; ++i) {
+    if (!h->h_mp_active[i]) continue;
+    const uint32_t a = h->h_mp_a[i], b = h->h_mp_b[i];
+    const bool ca = h->h_object_const[a], cb = h->h_object_const[b];
+    if (ca && cb) continue;
+    nres += 2 * h->od;
+    if (!ca) obj_used[a] = 1;
+    if (!cb) obj_used[b] = 1;
   }
   if (!h->h_is_shared.empty()) for (int64_t o = 0; o < O; ++o) if (h->h_is_shared[o]) obj_used[o] = 1;
   std::vector<int32_t>& pose_vid = h->scr_pose_vid; std::vector<int32_t>& obj_vid = h->scr_obj_vid;

@@ -354,6 +354,44 @@ int obvi_ba_set_relpose(obvi_ba_handle* h, int64_t n, const uint32_t* ia, const 
   OBVI_API_END(h)
 }
 
+// include/obvi_map_prior.h.  The small dense algebra is done here, once: W (r = W d) and Lambda = W^T W, the device only multiplies.
+int obvi_map_set_pair_priors(obvi_ba_handle* h, int64_t n, const uint32_t* obj_a, const uint32_t* obj_b, const double* mean_a, const double* mean_b,
+                             const double* cov_joint, const uint8_t* form, double huber) {
+  if (!h || n < 0 || (n > 0 && (!obj_a || !obj_b || !mean_a || !mean_b || !cov_joint))) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "map_set_pair_priors: bad arguments");
+  OBVI_API_BEGIN
+  OBVI_HIP(hipSetDevice(h->device));
+  const int od = h->od, N = 2 * od, N2 = N * N;
+  std::vector<double> W((size_t)N2 * n, 0.0), Lam((size_t)N2 * n, 0.0), mean((size_t)N * n);
+  std::vector<uint64_t> keys((size_t)n);
+  for (int64_t i = 0; i < n; ++i) {
+    const uint32_t a = obj_a[i], b = obj_b[i];
+    if (a == b) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "map_set_pair_priors: a pair of an object with itself");
+    if (form && form[i] != OBVI_MAP_PAIR_JOINT && form[i] != OBVI_MAP_PAIR_CONDITIONAL) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "map_set_pair_priors: unknown form");
+    if (a >= h->O || b >= h->O) return fail(h, OBVI_ERR_OUT_OF_RANGE, "map_set_pair_priors: index out of range");
+    keys[i] = (uint64_t)std::min(a, b) << 32 | std::max(a, b);
+  }
+  {   // one factor per unordered pair: the object-object block of the reduced matrix has one writer
+    std::vector<uint64_t> sorted(keys);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "map_set_pair_priors: the same pair twice");
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    if (!map_pair_weights(cov_joint + (size_t)N2 * i, od, !form || form[i] == OBVI_MAP_PAIR_JOINT, &W[(size_t)N2 * i], &Lam[(size_t)N2 * i]))
+      return fail(h, OBVI_ERR_NUMERICAL, "map_set_pair_priors: covariance not SPD");
+    for (int k = 0; k < od; ++k) { mean[(size_t)N * i + k] = mean_a[(size_t)od * i + k]; mean[(size_t)N * i + od + k] = mean_b[(size_t)od * i + k]; }
+    for (int k = 0; k < N; ++k) if (!std::isfinite(mean[(size_t)N * i + k])) return fail(h, OBVI_ERR_NUMERICAL, "map_set_pair_priors: non-finite mean");
+  }
+  h->n_mp = n; h->mp_huber = huber; h->max_mp_obj = std::max(max_index(obj_a, n), max_index(obj_b, n));
+  h->h_mp_a.assign(obj_a, obj_a + n); h->h_mp_b.assign(obj_b, obj_b + n); h->h_mp_active.assign(n, 1);
+  hipStream_t s = h->stream;
+  h->d_mp_a.upload(h->h_mp_a, s); h->d_mp_b.upload(h->h_mp_b, s); h->d_mp_mean.upload(mean, s); h->d_mp_W.upload(W, s); h->d_mp_Lambda.upload(Lam, s);
+  h->d_mp_active.upload(h->h_mp_active, s);
+  finish_upload(h);
+  h->dirty = true;
+  return OBVI_OK;
+  OBVI_API_END(h)
+}
+
 int obvi_ba_set_active_mask(obvi_ba_handle* h, int32_t type, const uint8_t* mask) {
   if (!h) return OBVI_ERR_INVALID_ARGUMENT;
   OBVI_API_BEGIN
@@ -372,6 +410,7 @@ int obvi_ba_set_active_mask(obvi_ba_handle* h, int32_t type, const uint8_t* mask
     case OBVI_FACTOR_SHAPE_PRIOR: set_mask<uint32_t>(h->h_sp_active, h->d_sp_active, mask, h->n_sp, s, nullptr); break;
     case OBVI_FACTOR_LTM_PRIOR: set_mask<uint32_t>(h->h_lt_active, h->d_lt_active, mask, h->n_lt, s, nullptr); break;
     case OBVI_FACTOR_REL_POSE: set_mask<uint32_t>(h->h_rl_active, h->d_rl_active, mask, h->n_rl, s, nullptr); break;
+    case OBVI_FACTOR_MAP_PAIR_PRIOR: set_mask<uint32_t>(h->h_mp_active, h->d_mp_active, mask, h->n_mp, s, nullptr); break;
     default: return fail(h, OBVI_ERR_INVALID_ARGUMENT, "set_active_mask: unknown factor type");
   }
   finish_upload(h);
@@ -384,9 +423,10 @@ int64_t obvi_ba_num_factors(const obvi_ba_handle* h, int32_t type) {
   if (!h) return -1;
   switch (type) {
     case OBVI_FACTOR_REPROJECTION: return h->n_rp; case OBVI_FACTOR_BBOX: return h->n_bb; case OBVI_FACTOR_SHAPE_PRIOR: return h->n_sp;
-    case OBVI_FACTOR_LTM_PRIOR: return h->n_lt; case OBVI_FACTOR_REL_POSE: return h->n_rl; default: return -1;
+    case OBVI_FACTOR_LTM_PRIOR: return h->n_lt; case OBVI_FACTOR_REL_POSE: return h->n_rl;
+    case OBVI_FACTOR_MAP_PAIR_PRIOR: return h->n_mp; default: return -1;
   }
 }
-int64_t obvi_ba_num_residuals(const obvi_ba_handle* h) { return h ? 2 * h->n_rp + 4 * h->n_bb + 3 * h->n_sp + h->od * h->n_lt + 6 * h->n_rl : -1; }
+int64_t obvi_ba_num_residuals(const obvi_ba_handle* h) { return h ? 2 * h->n_rp + 4 * h->n_bb + 3 * h->n_sp + h->od * h->n_lt + 6 * h->n_rl + 2 * h->od * h->n_mp : -1; }
 
 }  // extern "C"

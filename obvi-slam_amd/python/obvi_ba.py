@@ -15,9 +15,11 @@ FACTOR_BBOX = 2
 FACTOR_SHAPE_PRIOR = 3
 FACTOR_LTM_PRIOR = 4
 FACTOR_REL_POSE = 5
+FACTOR_MAP_PAIR_PRIOR = 9    # include/obvi_map_prior.h: not in FACTOR_TYPES (the oracle does not know it)
+MAP_PAIR_JOINT, MAP_PAIR_CONDITIONAL = 0, 1
 FACTOR_TYPES = (FACTOR_REPROJECTION, FACTOR_BBOX, FACTOR_SHAPE_PRIOR, FACTOR_LTM_PRIOR, FACTOR_REL_POSE)
-RESIDUAL_DIM = {0: 2, 2: 4, 3: 3, 4: 7, 5: 6}
-BLOCK_DIMS = {0: (6, 3), 2: (7, 6), 3: (7, 0), 4: (7, 0), 5: (6, 6)}
+RESIDUAL_DIM = {0: 2, 2: 4, 3: 3, 4: 7, 5: 6, 9: 14}
+BLOCK_DIMS = {0: (6, 3), 2: (7, 6), 3: (7, 0), 4: (7, 0), 5: (6, 6), 9: (7, 7)}
 
 CONVERGENCE, NO_CONVERGENCE, FAILURE = 0, 1, 2
 
@@ -114,7 +116,7 @@ class BundleAdjuster:
         opt = Options(device_id, self.od, int(reprojection_variant), 1 if deterministic else 0)
         self._check(self._fn("ba_create")(C.byref(opt), C.byref(self._h)), "create")
         self._keep = []
-        self._n = {t: 0 for t in FACTOR_TYPES}
+        self._n = {t: 0 for t in FACTOR_TYPES + (FACTOR_MAP_PAIR_PRIOR,)}
         self.P = self.L = self.O = 0
 
     def _fn(self, name):
@@ -217,6 +219,22 @@ class BundleAdjuster:
                                                C.c_double(huber)), "set_relpose")
         self._n[FACTOR_REL_POSE] = len(ia)
 
+    def set_map_pair_priors(self, obj_a, obj_b, mean_a, mean_b, cov_joint, form=None, huber=1.0):
+        """Joint Gaussian priors on object pairs (include/obvi_map_prior.h): cov_joint [n][2od][2od]; form None = all joint, else MAP_PAIR_JOINT / MAP_PAIR_CONDITIONAL per pair."""
+        try:
+            f = getattr(self._lib, self._pre + "map_set_pair_priors")
+        except AttributeError:
+            raise ObviError("%smap_set_pair_priors: this library has no map pair priors (include/obvi_map_prior.h is served by libobvi_ba.so only)" % self._pre)
+        f.restype = C.c_int
+        ia = np.ascontiguousarray(obj_a, dtype=np.uint32)
+        ib = np.ascontiguousarray(obj_b, dtype=np.uint32)
+        n2 = 2 * self.od
+        ma, mb, cv = _f64(mean_a, (-1, self.od)), _f64(mean_b, (-1, self.od)), _f64(cov_joint, (-1, n2 * n2))
+        fm = None if form is None else np.ascontiguousarray(form, dtype=np.uint8)
+        self._check(f(self._h, C.c_int64(len(ia)), _ptr(ia, C.c_uint32), _ptr(ib, C.c_uint32), _ptr(ma, C.c_double), _ptr(mb, C.c_double),
+                      _ptr(cv, C.c_double), _ptr(fm, C.c_uint8), C.c_double(huber)), "map_set_pair_priors")
+        self._n[FACTOR_MAP_PAIR_PRIOR] = len(ia)
+
     def set_active_mask(self, factor_type, mask):
         m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
         self._check(self._fn("ba_set_active_mask")(self._h, C.c_int32(factor_type), _ptr(m, C.c_uint8)), "set_active_mask")
@@ -226,10 +244,10 @@ class BundleAdjuster:
         return self._n[t]
 
     def _residual_dim(self, t):
-        return self.od if t == 4 else RESIDUAL_DIM[t]        # an LTM prior has one residual per ellipsoid parameter
+        return self.od if t == 4 else 2 * self.od if t == 9 else RESIDUAL_DIM[t]        # an LTM prior has one residual per ellipsoid parameter, a map pair prior two
 
     def num_residuals(self):
-        return sum(self._residual_dim(t) * self._n[t] for t in FACTOR_TYPES)
+        return sum(self._residual_dim(t) * n for t, n in self._n.items())
 
     def evaluate(self, apply_loss=True, want_residuals=True):
         cost = C.c_double(0.0)
@@ -399,7 +417,7 @@ class BundleAdjuster:
     def reset(self):
         """obvi_ba_reset: the handle as create left it (no problem, no hook, nothing shared), allocations kept."""
         self._check(self._fn("ba_reset")(self._h), "reset")
-        self._n = {t: 0 for t in FACTOR_TYPES}
+        self._n = {t: 0 for t in FACTOR_TYPES + (FACTOR_MAP_PAIR_PRIOR,)}
         self.P = self.L = self.O = 0
         self._keep.clear()
 
