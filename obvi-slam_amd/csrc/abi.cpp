@@ -155,6 +155,7 @@ int obvi_ba_reset(obvi_ba_handle* h) {
   if (!rc) rc = obvi_ba_set_ltm_priors(h, 0, nullptr, nullptr, nullptr, 1.0);
   if (!rc) rc = obvi_ba_set_relpose(h, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 1.0);
   if (!rc) rc = obvi_map_set_pair_priors(h, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1.0);
+  if (!rc) rc = obvi_map_set_group_priors(h, 0, nullptr, nullptr, nullptr, nullptr, 1.0);
   if (!rc) rc = obvi_ba_set_poses(h, 0, nullptr, nullptr);
   if (!rc) rc = obvi_ba_set_points(h, 0, nullptr, nullptr);
   if (!rc) rc = obvi_ba_set_objects(h, 0, nullptr, nullptr);
@@ -198,12 +199,13 @@ int obvi_ba_evaluate(obvi_ba_handle* h, int32_t apply_loss, double* cost, double
   { const int vrc = validate_indices(h); if (vrc != OBVI_OK) return vrc; }
   prepare(h);
   hipStream_t s = h->stream;
-  const int64_t nres = obvi_ba_num_residuals(h), nfac = h->n_rp + h->n_bb + h->n_sp + h->n_lt + h->n_rl + h->n_mp;
+  const int64_t nres = obvi_ba_num_residuals(h), nfac = h->n_rp + h->n_bb + h->n_sp + h->n_lt + h->n_rl + h->n_mp + h->n_mg;
   h->d_eval_res.resize((size_t)nres + 1); h->d_eval_sq.resize((size_t)nfac + 1);
   OBVI_HIP(hipMemsetAsync(h->d_scal.get(), 0, sizeof(double) * SC_COUNT, s));
   launch_pose_cache(s, h->P, h->d_pose.get(), h->d_pc.get(), h->reproj_variant == OBVI_REPROJECTION_ANALYTIC);
   launch_evaluate(s, blocks_dev(h), reproj_dev(h), h->d_rp_perm.get(), small_dev(h), h->d_cams.get(), h->d_pc.get(), h->d_pose.get(),
                   h->d_point.get(), h->d_obj.get(), apply_loss, h->d_eval_res.get(), h->d_eval_sq.get(), h->d_scal.get());
+  launch_map_group_eval(s, blocks_dev(h), map_group_dev(h), h->d_obj.get(), apply_loss, h->d_eval_res.get() + (nres - h->mg_rows), h->d_eval_sq.get() + (nfac - h->n_mg), h->d_scal.get());   // (behind the pair priors)
   if (!cost && !residuals && !block_sqnorm) return OBVI_OK;   // nothing to hand back (obvi_ba_select_outliers: its kernels follow on the same stream)
   double c = 0.0;
   OBVI_HIP(hipMemcpyAsync(&c, h->d_scal.get() + SC_COST, sizeof(double), hipMemcpyDeviceToHost, s));
@@ -222,6 +224,18 @@ int obvi_ba_debug_linearize(obvi_ba_handle* h, int32_t type, double* r, double* 
   { const int vrc = validate_indices(h); if (vrc != OBVI_OK) return vrc; }
   prepare(h);
   hipStream_t s = h->stream;
+  if (type == OBVI_FACTOR_MAP_GROUP_PRIOR) {   // r of all groups, J0 = W group after group (the device's own copy)
+    if (h->n_mg == 0) return OBVI_OK;
+    DevBuf<double> dr;
+    dr.resize((size_t)h->mg_rows);
+    launch_map_group_debug(s, map_group_dev(h), h->d_obj.get(), dr.get());
+    dr.download(r, (size_t)h->mg_rows, s);
+    size_t nw = 0;
+    for (int64_t g = 0; g < h->n_mg; ++g) { const size_t N = (size_t)h->od * (size_t)(h->h_mg_ptr[g + 1] - h->h_mg_ptr[g]); nw += N * N; }
+    h->d_mg_W.download(J0, nw, s);
+    sync(h);
+    return OBVI_OK;
+  }
   int m, d0, d1; int64_t n;
   switch (type) {
     case OBVI_FACTOR_REPROJECTION: m = 2; d0 = 6; d1 = 3; n = h->n_rp; break;
@@ -439,6 +453,7 @@ int obvi_ba_select_outliers(obvi_ba_handle* h, int32_t type, double fraction, ui
     case OBVI_FACTOR_LTM_PRIOR: off = h->n_rp + h->n_bb + h->n_sp; n = h->n_lt; act = h->d_lt_active.get(); break;
     case OBVI_FACTOR_REL_POSE: off = h->n_rp + h->n_bb + h->n_sp + h->n_lt; n = h->n_rl; act = h->d_rl_active.get(); break;
     case OBVI_FACTOR_MAP_PAIR_PRIOR: off = h->n_rp + h->n_bb + h->n_sp + h->n_lt + h->n_rl; n = h->n_mp; act = h->d_mp_active.get(); break;
+    case OBVI_FACTOR_MAP_GROUP_PRIOR: off = h->n_rp + h->n_bb + h->n_sp + h->n_lt + h->n_rl + h->n_mp; n = h->n_mg; act = h->d_mg_active.get(); break;
     default: return fail(h, OBVI_ERR_INVALID_ARGUMENT, "select_outliers: unknown factor type");
   }
   run_selection(h, n, h->d_eval_sq.get() + off, act, inv, fraction, mask_out, num_excluded);

@@ -90,12 +90,16 @@ inline int64_t backsub_grid(int64_t L, int64_t P, int64_t O, int lanes) { return
 inline int64_t cost_grid(int64_t P, int64_t n_obs, int64_t n_small) { return (n_obs > 0 ? P : 0) + blocks_of(n_small, kBaBlock); }   // k_cost: a workgroup per pose, a thread per small factor
 inline int64_t eval_reproj_grid(int64_t n_obs) { return blocks_of(n_obs, kBaBlock); }   // k_eval_reproj, k_eval_small: a thread per factor
 inline int64_t eval_small_grid(int64_t n_small) { return blocks_of(n_small, 64); }
+// map group priors (include/obvi_map_group_prior.h), rows N = k od of a group: k_map_group_quad and k_map_group_eval run a workgroup per 64-row slab of a group's
+// matrix, k_map_group_scatter one per 64 x 64 tile of its lower triangle, k_map_group_cost one per group
+inline int64_t map_group_slabs(int64_t rows) { return blocks_of(rows, 64); }
+inline int64_t map_group_tiles(int64_t rows) { const int64_t t = blocks_of(rows, 64); return t * (t + 1) / 2; }
 // the largest of those grids (launch_backsub_apply takes at most 32 lanes per feature), at least 1 for an empty problem: the stride is also the mode's flag
-struct DetCounts { int64_t P, L, O, od, n_rp, n_point_waves, n_long_points, n_bb, n_sp, n_lt, n_rl, n_mp = 0; };
+struct DetCounts { int64_t P, L, O, od, n_rp, n_point_waves, n_long_points, n_bb, n_sp, n_lt, n_rl, n_mp = 0, mg_tiles = 0; };   // (mg_tiles: the scatter grid, the largest of the group kernels')
 inline int64_t det_slots_needed(const DetCounts& c) {
   const int64_t ns = c.n_bb + c.n_sp + c.n_lt + c.n_rl + c.n_mp;
   return std::max<int64_t>({1, point_pass_grid(c.n_point_waves), point_pass_long_grid(c.n_long_points), small_lin_grid(c.n_bb, c.n_sp + c.n_lt, c.n_rl, c.n_mp, c.od),
-                            reduced_diag_grid(c.P, c.O, c.od), backsub_grid(c.L, c.P, c.O, 32), cost_grid(c.P, c.n_rp, ns), eval_reproj_grid(c.n_rp), eval_small_grid(ns)});
+                            reduced_diag_grid(c.P, c.O, c.od), backsub_grid(c.L, c.P, c.O, 32), cost_grid(c.P, c.n_rp, ns), eval_reproj_grid(c.n_rp), eval_small_grid(ns), c.mg_tiles});
 }
 
 struct ReprojDev {          // observations sorted by (point, pose): CSC by point
@@ -164,6 +168,20 @@ struct SmallFactorsDev {    // N <= ~3e4 each; arrays in caller order
   const uint8_t* mp_active; double mp_huber;
 };
 
+// Map group priors (include/obvi_map_group_prior.h).  Group g: members [ptr[g], ptr[g + 1]) of obj / mean (od doubles each), N_g = od x members rows.
+// Lambda_g: N_g rows of ld_g = N_g rounded up to even doubles at lam_off[g] (16-byte rows: k_map_group_quad loads pairs); W_g: lower triangular, N_g x N_g
+// at w_off[g], no padding (obvi_ba_debug_linearize hands it out as it is).  Rows of all groups one after the other: row od ptr[g] + i <-> y, residuals.
+// Work lists: slab (group, 64 rows) and tile (group, ti << 16 | tj, tj <= ti), group after group; slab_ptr[g] / tile_ptr[g]: a group's first.
+struct MapGroupDev {
+  int64_t n; int32_t od;
+  const int64_t* ptr; const uint32_t* obj; const double* mean; const uint8_t* active; double huber;
+  const int64_t* lam_off; const double* Lambda; const int64_t* w_off; const double* W;
+  int64_t n_slabs, n_tiles;
+  const int32_t* slab_ptr; const int32_t* slab_grp; const int32_t* tile_ptr; const int32_t* tile_grp; const int32_t* tile_ij;
+  double* y;         // [rows] Lambda d of the last k_map_group_quad
+  double* partial;   // [n_slabs] the slabs' sum d_i y_i (or sum r_i^2: k_map_group_eval)
+};
+
 struct ReducedDev {         // accumulators of the reduced system
   double* Hdiag;            // pose v: 36 doubles at 36 v; object w: od^2 doubles at 36 nPv + od^2 w (row-major, lower part used)
   double* g;                // [6 nPv + od nOv] gradient J^T r (compact index: pose v at 6v, object w at 6 nPv + od w)
@@ -202,6 +220,17 @@ void launch_small_factors(hipStream_t s, const BlocksDev& b, const SmallFactorsD
                           const double* poses, const double* objects, const ReducedDev& rd, double* scal, int64_t lanes_below /* Knobs::small_lanes_below */);
 void launch_reduced_diag(hipStream_t s, const BlocksDev& b, const double* poses, const double* objects,
                          const ReducedDev& rd, double radius, int first_iter, double* scal);
+// map group priors; every launcher returns at once when there are no groups.  Linearisation: y = Lambda d and the slabs' partial sums (launch_map_group_quad,
+// mode 0: groups with a variable member, mode 1: groups whose members are all constant), then w Lambda into Hdiag / S, w y into g, rho / 2 into SC_COST
+// (launch_map_group_scatter: behind the small-factor gathers and in front of launch_reduced_diag, on their stream).  launch_map_group_cost: the quad kernel on
+// `objects` and rho / 2 into SC_COST_CAND (mode 0) or SC_COST_FIXED (mode 1).
+void launch_map_group_quad(hipStream_t s, const BlocksDev& b, const MapGroupDev& mg, const double* objects, int mode);
+void launch_map_group_scatter(hipStream_t s, const BlocksDev& b, const MapGroupDev& mg, const ReducedDev& rd, double* scal);
+void launch_map_group_cost(hipStream_t s, const BlocksDev& b, const MapGroupDev& mg, const double* objects, int mode, double* scal);
+// r = W d of every group into `residuals` (scaled by sqrt(rho') with apply_loss; zeros for an inactive group), |r|^2 per group into `sqnorm`, the cost into SC_COST
+void launch_map_group_eval(hipStream_t s, const BlocksDev& b, const MapGroupDev& mg, const double* objects, int apply_loss, double* residuals, double* sqnorm, double* scal);
+// obvi_ba_debug_linearize: the raw r = W d of every group, inactive ones too; no cost, no norms
+void launch_map_group_debug(hipStream_t s, const MapGroupDev& mg, const double* objects, double* residuals);
 void launch_schur_blocks(hipStream_t s, int64_t nblk, const uint32_t* blk_row, const uint32_t* blk_col, const uint32_t* blk_ptr,
                          const uint32_t* pair_a, const uint32_t* pair_b, const uint32_t* obs_point, const PointDev& pt,
                          const ReducedDev& rd);

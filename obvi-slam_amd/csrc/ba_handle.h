@@ -9,6 +9,7 @@
 #define OBVI_BA_HANDLE_H_
 #include "../../include/obvi_ba.h"
 #include "../../include/obvi_map_prior.h"
+#include "../../include/obvi_map_group_prior.h"
 
 #include <algorithm>
 #include <atomic>
@@ -37,8 +38,8 @@ namespace obvi_lib {
 
 inline double wall_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-enum Phase { PH_POSE_CACHE = 0, PH_POINT_PASS, PH_POSE_PASS, PH_SMALL, PH_DIAG, PH_SCHUR, PH_SCHUR_BLOCKS, PH_CHOL, PH_BACKSUB, PH_APPLY, PH_COST, PH_COUNT };
-inline const char* const kPhaseNames[PH_COUNT] = {"pose_cache", "point_pass", "pose_pass", "small_factors", "reduced_diag", "schur_window", "schur_blocks",
+enum Phase { PH_POSE_CACHE = 0, PH_POINT_PASS, PH_POSE_PASS, PH_SMALL, PH_MAP_QUAD, PH_MAP_SCATTER, PH_DIAG, PH_SCHUR, PH_SCHUR_BLOCKS, PH_CHOL, PH_BACKSUB, PH_APPLY, PH_COST, PH_COUNT };
+inline const char* const kPhaseNames[PH_COUNT] = {"pose_cache", "point_pass", "pose_pass", "small_factors", "map_group_quad", "map_group_scatter", "reduced_diag", "schur_window", "schur_blocks",
                                      "cholesky_solve", "point_backsub", "apply_step", "cost"};
 
 // The tuning knobs of a handle.  read_knobs() is the only reader of the environment: obvi_ba_create takes one
@@ -128,6 +129,10 @@ struct obvi_ba_handle {
   std::vector<uint32_t> h_bb_obj, h_bb_pose, h_sp_obj, h_lt_obj, h_rl_a, h_rl_b, h_mp_a, h_mp_b;
   std::vector<uint8_t> h_bb_active, h_sp_active, h_lt_active, h_rl_active, h_mp_active;
   double bb_huber = 1.0, bb_invalid = 1e6, sp_huber = 1.0, lt_huber = 1.0, rl_huber = 1.0, mp_huber = 1.0;
+  // map group priors (include/obvi_map_group_prior.h): members of group g = h_mg_obj[h_mg_ptr[g] .. h_mg_ptr[g + 1]); mg_rows = od x members of all groups
+  int64_t n_mg = 0, mg_rows = 0, mg_slabs = 0, mg_tiles = 0, max_mg_obj = -1;
+  std::vector<int64_t> h_mg_ptr; std::vector<uint32_t> h_mg_obj; std::vector<uint8_t> h_mg_active;
+  double mg_huber = 1.0;
   // largest block / camera index each factor family refers to (-1: none): re-checked against the current block counts before every
   // evaluate / solve, because blocks and cameras may be re-uploaded (with other counts) after the factors
   int64_t max_rp_pose = -1, max_rp_point = -1, max_rp_cam = -1, max_bb_obj = -1, max_bb_pose = -1, max_bb_cam = -1, max_sp_obj = -1, max_lt_obj = -1, max_rl_pose = -1, max_mp_obj = -1;
@@ -167,6 +172,9 @@ struct obvi_ba_handle {
   DevBuf<uint16_t> d_bb_cam;
   DevBuf<double> d_bb_rect, d_bb_sqrt_inf, d_sp_mean, d_sp_sqrt_inf, d_lt_mean, d_lt_sqrt_inf, d_rl_t, d_rl_R, d_rl_sqrt_inf, d_mp_mean, d_mp_W, d_mp_Lambda;
   DevBuf<uint8_t> d_bb_active, d_sp_active, d_lt_active, d_rl_active, d_mp_active;
+  DevBuf<int64_t> d_mg_ptr, d_mg_lam_off, d_mg_w_off; DevBuf<uint32_t> d_mg_obj; DevBuf<uint8_t> d_mg_active;
+  DevBuf<double> d_mg_mean, d_mg_Lambda, d_mg_W, d_mg_y, d_mg_partial;
+  DevBuf<int32_t> d_mg_slab_ptr, d_mg_slab_grp, d_mg_tile_ptr, d_mg_tile_grp, d_mg_tile_ij;   // work lists of the group kernels (ba_device.h, MapGroupDev)
   DevBuf<double> d_bb_blk;                                    // per-factor blocks of the bounding-box factors (k_bbox_gather)
   DevBuf<double> d_sm_blk; DevBuf<uint32_t> d_smt_ptr, d_smt_idx;   // deterministic mode: the same for the priors and relative-pose factors (k_small_gather)
   int32_t bb_pairs_unique = 1;
@@ -206,7 +214,7 @@ struct obvi_ba_handle {
   // what the plan was built for: variable blocks and active factors.  A later state whose variable blocks and active factors are
   // subsets of these runs on the same plan (rows of dropped blocks become padding, masked observations contribute zeros)
   std::vector<int32_t> plan_pose_vid, plan_obj_vid;
-  std::vector<uint8_t> plan_point_var, plan_is_pad, plan_rp_active, plan_bb_active, plan_sp_active, plan_lt_active, plan_rl_active, plan_mp_active;
+  std::vector<uint8_t> plan_point_var, plan_is_pad, plan_rp_active, plan_bb_active, plan_sp_active, plan_lt_active, plan_rl_active, plan_mp_active, plan_mg_active;
   int64_t live_rows = 0;                 // 6 (variable poses) + od (variable objects) of the current state (== m_canon right after a full plan)
   int64_t nPv = 0, nOv = 0, nLv = 0, m = 0, m_canon = 0, num_params = 0, num_residuals = 0;
   int32_t nt = 0;
@@ -408,6 +416,15 @@ inline SmallFactorsDev small_dev(const obvi_ba_handle* h) {
   s.mp_Lambda = h->d_mp_Lambda.get(); s.mp_active = h->d_mp_active.get(); s.mp_huber = h->mp_huber;
   return s;
 }
+inline MapGroupDev map_group_dev(const obvi_ba_handle* h) {
+  MapGroupDev g;
+  g.n = h->n_mg; g.od = h->od; g.ptr = h->d_mg_ptr.get(); g.obj = h->d_mg_obj.get(); g.mean = h->d_mg_mean.get(); g.active = h->d_mg_active.get(); g.huber = h->mg_huber;
+  g.lam_off = h->d_mg_lam_off.get(); g.Lambda = h->d_mg_Lambda.get(); g.w_off = h->d_mg_w_off.get(); g.W = h->d_mg_W.get();
+  g.n_slabs = h->mg_slabs; g.n_tiles = h->mg_tiles;
+  g.slab_ptr = h->d_mg_slab_ptr.get(); g.slab_grp = h->d_mg_slab_grp.get(); g.tile_ptr = h->d_mg_tile_ptr.get(); g.tile_grp = h->d_mg_tile_grp.get(); g.tile_ij = h->d_mg_tile_ij.get();
+  g.y = h->d_mg_y.get(); g.partial = h->d_mg_partial.get();
+  return g;
+}
 inline ReducedDev reduced_dev(const obvi_ba_handle* h) {
   ReducedDev r;
   r.Hdiag = h->d_Hdiag.get(); r.g = h->d_g.get(); r.scale = h->d_scale.get(); r.lam = h->d_lam.get();
@@ -503,6 +520,16 @@ inline int validate_indices(obvi_ba_handle* h) {
   // refused here, before the plan and before any collective
   if (h->n_mp > 0 && h->allreduce != nullptr && std::any_of(h->h_is_shared.begin(), h->h_is_shared.end(), [](uint8_t v) { return v != 0; }))
     return fail(h, OBVI_ERR_INVALID_ARGUMENT, "map pair priors on a handle that exchanges shared objects: the collective form is not built");
+  if (h->n_mg > 0 && h->max_mg_obj >= h->O) return bad("map group priors");
+  if (h->n_mg > 0 && h->allreduce != nullptr && std::any_of(h->h_is_shared.begin(), h->h_is_shared.end(), [](uint8_t v) { return v != 0; }))
+    return fail(h, OBVI_ERR_INVALID_ARGUMENT, "map group priors on a handle that exchanges shared objects: the collective form is not built");
+  if (h->n_mg > 0 && h->n_mp > 0) {   // a pair prior inside a group: the pair's block would have two writers, its information would count twice
+    std::vector<int32_t> group_of((size_t)h->O, -1);
+    for (int64_t g = 0; g < h->n_mg; ++g) for (int64_t k = h->h_mg_ptr[g]; k < h->h_mg_ptr[g + 1]; ++k) group_of[h->h_mg_obj[k]] = (int32_t)g;
+    for (int64_t i = 0; i < h->n_mp; ++i)
+      if (group_of[h->h_mp_a[i]] >= 0 && group_of[h->h_mp_a[i]] == group_of[h->h_mp_b[i]])
+        return fail(h, OBVI_ERR_INVALID_ARGUMENT, "a map pair prior whose two objects are members of one map group prior");
+  }
   for (size_t i = 0; i < h->h_pp_kind.size(); ++i) {
     const int64_t cnt = h->h_pp_kind[i] == 0 ? h->P : h->h_pp_kind[i] == 1 ? h->L : h->O;
     if ((int64_t)h->h_pp_block[i] >= cnt) return bad("parameter priors");
@@ -543,7 +570,7 @@ inline void prepare_plan(obvi_ba_handle* h);
 // reallocated when the problem outgrows it -- only between API calls: every call clears the scalars before its first launch.
 inline void ensure_det_slots(obvi_ba_handle* h) {
   if (!h->deterministic) return;
-  const int64_t need = det_slots_needed({h->P, h->L, h->O, h->od, h->n_rp, h->n_point_waves, h->n_long_points, h->n_bb, h->n_sp, h->n_lt, h->n_rl, h->n_mp});
+  const int64_t need = det_slots_needed({h->P, h->L, h->O, h->od, h->n_rp, h->n_point_waves, h->n_long_points, h->n_bb, h->n_sp, h->n_lt, h->n_rl, h->n_mp, h->mg_tiles});
   if (need > kDetMaxStride) throw HipError{hipErrorInvalidValue, "deterministic mode: the problem needs more partial-sum slots than kDetMaxStride", __FILE__, __LINE__};
   if (need <= h->det_stride) return;
   int64_t stride = h->knobs.det_min_stride;   // (the tests start small to see the block grow)

@@ -1772,6 +1772,193 @@ __global__ void __launch_bounds__(kBlock) k_pack_tail(ReducedDev rd, int32_t t0,
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// Map group priors (include/obvi_map_group_prior.h): a Gaussian on k objects, N = k od rows.  Dense matrix-vector work bound by reading Lambda:
+//   k_map_group_quad     a workgroup per (group, 64-row slab of Lambda): d in LDS, y = Lambda d for its rows, the slab's sum d_i y_i to its slot
+//   k_map_group_scatter  a workgroup per (group, 64 x 64 tile of Lambda's lower triangle): w Lambda into Hdiag / S, w y into g, rho / 2 into the cost
+//   k_map_group_cost     a workgroup per group: rho / 2 from the slabs' sums (trial cost, fixed cost)
+//   k_map_group_eval     r = W d, a wavefront per row of the lower triangular W (evaluate, debug)
+// No kernel adds the slabs' sums with atomics: whoever needs s = d^T Lambda d adds the group's slots in slot order, so every workgroup of a group derives the
+// same s, rho and w in either mode.
+// ---------------------------------------------------------------------------------------
+constexpr int kMgMaxRows = 2048;   // OBVI_MAP_GROUP_MAX_ROWS: d of a group fits 16 KB of LDS
+
+// the groups a pass works on: active, and with a variable member (want_var) or with none.  Whole workgroup; every thread gets the same answer.
+__device__ __forceinline__ bool map_group_selected(const BlocksDev& b, const MapGroupDev& mg, int g, bool want_var) {
+  if (!mg.active[g]) return false;
+  int var = 0;
+  for (int64_t k = mg.ptr[g] + threadIdx.x; k < mg.ptr[g + 1]; k += blockDim.x) var |= b.obj_vid[mg.obj[k]] >= 0 ? 1 : 0;
+  return (__syncthreads_or(var) != 0) == want_var;
+}
+// d = x - mu of group g into LDS, n entries and zeros up to n_pad (whole workgroup; the caller synchronises)
+__device__ __forceinline__ void map_group_stage_d(const MapGroupDev& mg, int g, const double* __restrict__ objects, double* d, int n, int n_pad) {
+  const int od = mg.od;
+  const int64_t m0 = mg.ptr[g];
+  for (int i = threadIdx.x; i < n_pad; i += blockDim.x) {
+    const int k = i / od, x = i - k * od;
+    d[i] = i < n ? objects[od * (int64_t)mg.obj[m0 + k] + x] - mg.mean[od * m0 + i] : 0.0;
+  }
+}
+__device__ __forceinline__ double map_group_sqnorm(const MapGroupDev& mg, int g) {
+  double s = 0.0;
+  for (int k = mg.slab_ptr[g]; k < mg.slab_ptr[g + 1]; ++k) s += mg.partial[k];
+  return s;
+}
+
+// Each of the four wavefronts takes 16 rows of the slab, four at a time: lane l reads the doubles 2 l, 2 l + 1 (+ 128 per round) of a row -- one 16-byte load per
+// lane, 1 KB contiguous per wavefront -- against the same pair of d from LDS, and the row's sum is a DPP reduction (the same order in every run).
+__global__ void __launch_bounds__(kBlock) k_map_group_quad(BlocksDev b, MapGroupDev mg, const double* __restrict__ objects, int want_var) {
+  __shared__ __attribute__((aligned(16))) double d[kMgMaxRows];
+  __shared__ double part[kBlock / 64];
+  const int g = mg.slab_grp[blockIdx.x], slab = (int)blockIdx.x - mg.slab_ptr[g];
+  const int64_t m0 = mg.ptr[g];
+  const int N = mg.od * (int)(mg.ptr[g + 1] - m0), ld = (N + 1) & ~1;
+  if (!map_group_selected(b, mg, g, want_var != 0)) {
+    if (threadIdx.x == 0) mg.partial[blockIdx.x] = 0.0;
+    return;
+  }
+  map_group_stage_d(mg, g, objects, d, N, ld);
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const double* __restrict__ L = mg.Lambda + mg.lam_off[g];
+  const int r0 = 64 * slab + 16 * wv;
+  double q = 0.0;
+  for (int rr = 0; rr < 16; rr += 4) {
+    const int r = r0 + rr;
+    if (r >= N) break;   // (the whole wavefront)
+    const double2* row[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) row[u] = reinterpret_cast<const double2*>(L + (int64_t)ld * min(r + u, N - 1));   // (a ragged slab re-reads its last row)
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int c = lane; c < ld / 2; c += 64) {
+      const double2 dv = *reinterpret_cast<const double2*>(d + 2 * c);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) { const double2 v = row[u][c]; acc[u] = fma(v.x, dv.x, fma(v.y, dv.y, acc[u])); }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const double yv = wave_sum(acc[u]);
+      if (r + u < N) {
+        if (lane == 0) mg.y[mg.od * m0 + r + u] = yv;
+        q += d[r + u] * yv;
+      }
+    }
+  }
+  if (lane == 0) part[wv] = q;
+  __syncthreads();
+  if (threadIdx.x == 0) mg.partial[blockIdx.x] = ((part[0] + part[1]) + part[2]) + part[3];
+}
+
+// Entry (i, j), j <= i, of the tile: members a = i / od >= c = j / od.  a == c: the lower part of a's diagonal block in Hdiag (atomics beside the other factor
+// families; deterministic mode: plain adds behind the gathers -- the groups are disjoint, an entry has one writer).  a != c: the block of the pair in the lower
+// triangle of S, the later-eliminated object as the row, by each member's own row (constant members drop out: the group need not be contiguous in S, and a block
+// may straddle tile edges).  The diagonal tiles add w y of their rows to g.  The group's first workgroup adds rho / 2 to the cost.
+__global__ void __launch_bounds__(kBlock) k_map_group_scatter(BlocksDev b, MapGroupDev mg, ReducedDev rd, double* scal) {
+  __shared__ int32_t s_vid[2][64], s_row[2][64], s_mem[2][64];
+  const int g = mg.tile_grp[blockIdx.x], ij = mg.tile_ij[blockIdx.x], ti = ij >> 16, tj = ij & 0xffff;
+  const int od = mg.od;
+  const int64_t m0 = mg.ptr[g];
+  const int N = od * (int)(mg.ptr[g + 1] - m0), ld = (N + 1) & ~1;
+  double cost = 0.0;
+  if (map_group_selected(b, mg, g, true)) {
+    double rho0, w;
+    huber_eval(map_group_sqnorm(mg, g), mg.huber, &rho0, &w);
+    if ((int)blockIdx.x == mg.tile_ptr[g]) cost = 0.5 * rho0;
+    if (threadIdx.x < 128) {   // rows of tile row ti, then columns of tile column tj: member, its reduced index, the row of the entry in the tile grid
+      const int side = threadIdx.x >> 6, l = threadIdx.x & 63, i = 64 * (side ? tj : ti) + l;
+      int32_t vid = -1, row = 0, mem = 0;
+      if (i < N) {
+        mem = i / od;
+        vid = b.obj_vid[mg.obj[m0 + mem]];
+        if (vid >= 0) row = b.obj_row[vid] + (i - mem * od);
+      }
+      s_vid[side][l] = vid; s_row[side][l] = row; s_mem[side][l] = mem;
+    }
+    __syncthreads();
+    const double* __restrict__ L = mg.Lambda + mg.lam_off[g];
+    for (int e = threadIdx.x; e < 64 * 64; e += kBlock) {
+      const int li = e >> 6, lj = e & 63, i = 64 * ti + li, j = 64 * tj + lj;
+      if (i >= N || j > i) continue;
+      const int32_t va = s_vid[0][li], vc = s_vid[1][lj];
+      if (va < 0 || vc < 0) continue;
+      const double v = w * L[(int64_t)ld * i + j];
+      if (s_mem[0][li] == s_mem[1][lj]) {
+        double* p = rd.Hdiag + 36 * b.nPv + od * od * (int64_t)va + od * (i - s_mem[0][li] * od) + (j - s_mem[1][lj] * od);
+        if (b.deterministic) *p += v; else atomic_add_f64(p, v);
+      } else {
+        const int64_t ra = s_row[0][li], rc = s_row[1][lj];
+        atomic_add_f64(ra > rc ? S_at(rd.S, rd.nt, ra, rc) : S_at(rd.S, rd.nt, rc, ra), v);   // (Lambda is symmetric: the transposed entry of the transposed block)
+      }
+    }
+    if (ti == tj && threadIdx.x < 64) {
+      const int l = threadIdx.x, i = 64 * ti + l;
+      const int32_t va = s_vid[0][l];
+      if (i < N && va >= 0) {
+        double* p = rd.g + 6 * b.nPv + od * (int64_t)va + (i - s_mem[0][l] * od);
+        const double v = w * mg.y[od * m0 + i];
+        if (b.deterministic) *p += v; else atomic_add_f64(p, v);
+      }
+    }
+  }
+  if (threadIdx.x == 0) scal_add(scal, b.deterministic, SC_COST, cost);
+}
+
+__global__ void __launch_bounds__(64) k_map_group_cost(BlocksDev b, MapGroupDev mg, int want_var, int sc, double* scal) {
+  const int g = blockIdx.x;
+  double cost = 0.0;
+  if (map_group_selected(b, mg, g, want_var != 0)) {
+    double rho0, w;
+    huber_eval(map_group_sqnorm(mg, g), mg.huber, &rho0, &w);
+    cost = 0.5 * rho0;
+  }
+  if (threadIdx.x == 0) scal_add(scal, b.deterministic, sc, cost);
+}
+
+// r = W d: W is lower triangular, a wavefront walks row i up to its diagonal (lane l: columns l, l + 64, ...).  `all`: inactive groups too (debug).
+__global__ void __launch_bounds__(kBlock) k_map_group_eval(MapGroupDev mg, const double* __restrict__ objects, int all, double* residuals) {
+  __shared__ double d[kMgMaxRows];
+  __shared__ double part[kBlock / 64];
+  const int g = mg.slab_grp[blockIdx.x], slab = (int)blockIdx.x - mg.slab_ptr[g];
+  const int64_t m0 = mg.ptr[g];
+  const int N = mg.od * (int)(mg.ptr[g + 1] - m0);
+  const bool on = all || mg.active[g];
+  if (on) map_group_stage_d(mg, g, objects, d, N, N);
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const double* __restrict__ W = mg.W + mg.w_off[g];
+  double q = 0.0;
+  for (int r = 64 * slab + 16 * wv; r < min(64 * slab + 16 * wv + 16, N); ++r) {
+    double acc = 0.0;
+    if (on) for (int c = lane; c <= r; c += 64) acc = fma(W[(int64_t)N * r + c], d[c], acc);
+    const double rv = wave_sum(acc);
+    if (lane == 0 && residuals) residuals[mg.od * m0 + r] = rv;
+    q += rv * rv;
+  }
+  if (lane == 0) part[wv] = q;
+  __syncthreads();
+  if (threadIdx.x == 0) mg.partial[blockIdx.x] = ((part[0] + part[1]) + part[2]) + part[3];
+}
+// per group: |r|^2, the cost, the residuals scaled by sqrt(rho') (finish_eval's conventions)
+__global__ void __launch_bounds__(64) k_map_group_eval_finish(MapGroupDev mg, int apply_loss, double* residuals, double* sqnorm, double* scal, int det) {
+  const int g = blockIdx.x;
+  const double s = map_group_sqnorm(mg, g);
+  double cost = 0.0;
+  if (mg.active[g]) {
+    cost = 0.5 * s;
+    if (apply_loss) {
+      double rho0, w;
+      huber_eval(s, mg.huber, &rho0, &w);
+      cost = 0.5 * rho0;
+      const double sw = sqrt(w);
+      if (residuals) for (int64_t i = mg.od * mg.ptr[g] + threadIdx.x; i < mg.od * mg.ptr[g + 1]; i += 64) residuals[i] *= sw;
+    }
+  }
+  if (threadIdx.x == 0) {
+    if (sqnorm) sqnorm[g] = s;
+    scal_add(scal, det, SC_COST, cost);
+  }
+}
+
 inline unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 // a kernel that leaves partial sums (its grid: ba_device.h): launch(grid) enqueues it; in deterministic mode the grid is checked against
 // the slots' room first, and k_det_reduce adds up the scalars in scalar_mask (bit sc: scalar sc) behind it
@@ -1852,6 +2039,27 @@ void launch_reduced_diag(hipStream_t s, const BlocksDev& b, const double* poses,
                          int first_iter, double* scal) {
   launch_reducing(s, b, scal, reduced_diag_grid(b.P, b.O, b.od), OBVI_SC(SC_GSQ) | OBVI_SC(SC_XSQ), [&](dim3 g) {
     hipLaunchKernelGGL(k_reduced_diag, g, dim3(kBlock), 0, s, b, poses, objects, rd, radius, first_iter, scal); });
+}
+void launch_map_group_quad(hipStream_t s, const BlocksDev& b, const MapGroupDev& mg, const double* objects, int mode) {
+  if (mg.n > 0) hipLaunchKernelGGL(k_map_group_quad, dim3((unsigned)mg.n_slabs), dim3(kBlock), 0, s, b, mg, objects, mode == 0 ? 1 : 0);
+}
+void launch_map_group_scatter(hipStream_t s, const BlocksDev& b, const MapGroupDev& mg, const ReducedDev& rd, double* scal) {
+  if (mg.n == 0) return;
+  launch_reducing(s, b, scal, mg.n_tiles, OBVI_SC(SC_COST), [&](dim3 g) { hipLaunchKernelGGL(k_map_group_scatter, g, dim3(kBlock), 0, s, b, mg, rd, scal); });
+}
+void launch_map_group_cost(hipStream_t s, const BlocksDev& b, const MapGroupDev& mg, const double* objects, int mode, double* scal) {
+  if (mg.n == 0) return;
+  launch_map_group_quad(s, b, mg, objects, mode);
+  const int sc = mode == 0 ? SC_COST_CAND : SC_COST_FIXED;
+  launch_reducing(s, b, scal, mg.n, OBVI_SC(sc), [&](dim3 g) { hipLaunchKernelGGL(k_map_group_cost, g, dim3(64), 0, s, b, mg, mode == 0 ? 1 : 0, sc, scal); });
+}
+void launch_map_group_eval(hipStream_t s, const BlocksDev& b, const MapGroupDev& mg, const double* objects, int apply_loss, double* residuals, double* sqnorm, double* scal) {
+  if (mg.n == 0) return;
+  hipLaunchKernelGGL(k_map_group_eval, dim3((unsigned)mg.n_slabs), dim3(kBlock), 0, s, mg, objects, 0, residuals);
+  launch_reducing(s, b, scal, mg.n, OBVI_SC(SC_COST), [&](dim3 g) { hipLaunchKernelGGL(k_map_group_eval_finish, g, dim3(64), 0, s, mg, apply_loss, residuals, sqnorm, scal, b.deterministic); });
+}
+void launch_map_group_debug(hipStream_t s, const MapGroupDev& mg, const double* objects, double* residuals) {
+  if (mg.n > 0) hipLaunchKernelGGL(k_map_group_eval, dim3((unsigned)mg.n_slabs), dim3(kBlock), 0, s, mg, objects, 1, residuals);
 }
 void launch_schur_blocks(hipStream_t s, int64_t nblk, const uint32_t* blk_row, const uint32_t* blk_col, const uint32_t* blk_ptr,
                          const uint32_t* pair_a, const uint32_t* pair_b, const uint32_t* obs_point, const PointDev& pt, const ReducedDev& rd) {

@@ -12,6 +12,7 @@
 #endif
 
 #include <algorithm>
+#include <limits>
 #include <atomic>
 #include <cmath>
 #include <condition_variable>
@@ -300,6 +301,138 @@ inline bool map_pair_weights(const double* C, int od, bool joint, double* W, dou
       }
   }
   for (int x = 0; x < N; ++x) for (int y = 0; y <= x; ++y) { double acc = 0.0; for (int k = 0; k < N; ++k) acc += W[N * k + x] * W[N * k + y]; Lambda[N * x + y] = Lambda[N * y + x] = acc; }
+  return true;
+}
+
+// Map group prior (include/obvi_map_group_prior.h): from the group's joint covariance C (N x N row-major, symmetrised as for the other priors; N up to a few
+// thousand) the lower triangular W = L^-1 of r = W d (C = L L^T; N x N, zeros above the diagonal) and the information Lambda = W^T W = C^-1 (N rows of ld >= N
+// doubles, both triangles, the padding zero).  Plain fp64, once per upload: a blocked right-looking Cholesky (64-column panels: the panel solve and the trailing
+// update are dot products of contiguous row pieces, handed out by rows), the triangular inverse by column strips (a strip's recurrence touches no other strip),
+// Lambda by rows.  par(n, fn) runs fn(i0, i1) over ranges that cover [0, n) -- on the host's workers, or in place.
+// false: C is not finite, not positive definite, or numerically singular: (largest / smallest Cholesky pivot)^2, a lower bound of the condition number, above
+// 1e13, or the condition number itself (largest eigenvalue of C times largest of Lambda, by power steps) above 1e13 -- the floor of map_pair_weights.
+// `work`: N x N scratch.
+template <class Par>
+inline bool map_group_weights(const double* C, int N, double* W, double* Lambda, int ld, double* work, Par&& par) {
+  constexpr int nb = 64;
+  double* A = work;
+  bool finite = true;
+  for (int i = 0; i < N; ++i)
+    for (int j = 0; j <= i; ++j) { const double v = 0.5 * (C[(size_t)N * i + j] + C[(size_t)N * j + i]); A[(size_t)N * i + j] = v; finite = finite && std::isfinite(v); }
+  if (!finite) return false;
+  double piv_min = 0.0, piv_max = 0.0;
+  for (int k0 = 0; k0 < N; k0 += nb) {
+    const int k1 = std::min(N, k0 + nb);
+    for (int j = k0; j < k1; ++j) {   // the diagonal block, unblocked
+      double* Aj = A + (size_t)N * j;
+      double dj = Aj[j];
+      for (int t = k0; t < j; ++t) dj -= Aj[t] * Aj[t];
+      if (!(dj > 0.0) || !std::isfinite(dj)) return false;
+      dj = std::sqrt(dj);
+      Aj[j] = dj;
+      piv_min = (k0 == 0 && j == 0) ? dj : std::min(piv_min, dj); piv_max = std::max(piv_max, dj);
+      for (int i = j + 1; i < k1; ++i) {
+        double* Ai = A + (size_t)N * i;
+        double v = Ai[j];
+        for (int t = k0; t < j; ++t) v -= Ai[t] * Aj[t];
+        Ai[j] = v / dj;
+      }
+    }
+    if (k1 == N) break;
+    par(N - k1, [&](int64_t i0, int64_t i1) {   // the panel below it: L_ik = A_ik L_kk^-T
+      for (int64_t i = k1 + i0; i < k1 + i1; ++i) {
+        double* Ai = A + (size_t)N * i;
+        for (int j = k0; j < k1; ++j) {
+          const double* Aj = A + (size_t)N * j;
+          double v = Ai[j];
+          for (int t = k0; t < j; ++t) v -= Ai[t] * Aj[t];
+          Ai[j] = v / Aj[j];
+        }
+      }
+    });
+    par(N - k1, [&](int64_t i0, int64_t i1) {   // the trailing update, lower triangle
+      for (int64_t i = k1 + i0; i < k1 + i1; ++i) {
+        double* Ai = A + (size_t)N * i;
+        for (int64_t j = k1; j <= i; ++j) {
+          const double* Aj = A + (size_t)N * j;
+          double v = 0.0;
+          for (int t = k0; t < k1; ++t) v += Ai[t] * Aj[t];
+          Ai[j] -= v;
+        }
+      }
+    });
+  }
+  if (!(piv_min * piv_min > 1e-13 * piv_max * piv_max)) return false;
+  // W = L^-1 in strips of 32 columns [j0, j1): row i of the strip is (e_i - sum_{j0 <= k < i} L_ik W_k) / L_ii
+  std::fill(W, W + (size_t)N * N, 0.0);
+  constexpr int ws = 32;
+  par((N + ws - 1) / ws, [&](int64_t s0, int64_t s1) {
+    for (int64_t sidx = s0; sidx < s1; ++sidx) {
+      const int j0 = (int)sidx * ws, j1 = std::min(N, j0 + ws);
+      for (int i = j0; i < N; ++i) {
+        const double* Li = A + (size_t)N * i;
+        double* Wi = W + (size_t)N * i;
+        const int je = std::min(j1, i + 1);   // (lower triangular: columns up to i)
+        for (int k = j0; k < i; ++k) {
+          const double l = Li[k];
+          const double* Wk = W + (size_t)N * k;
+          const int ke = std::min(je, k + 1);
+          for (int j = j0; j < ke; ++j) Wi[j] -= l * Wk[j];
+        }
+        if (i < j1) Wi[i] += 1.0;
+        const double inv = 1.0 / Li[i];
+        for (int j = j0; j < je; ++j) Wi[j] *= inv;
+      }
+    }
+  });
+  // Lambda_ij = sum_{k >= i} W_ki W_kj, j <= i: row i collects the rows k >= i of W; then the upper triangle
+  par(N, [&](int64_t i0, int64_t i1) {
+    for (int64_t i = i0; i < i1; ++i) {
+      double* Li = Lambda + (size_t)ld * i;
+      std::fill(Li, Li + ld, 0.0);
+      for (int64_t k = i; k < N; ++k) {
+        const double* Wk = W + (size_t)N * k;
+        const double wki = Wk[i];
+        for (int64_t j = 0; j <= i; ++j) Li[j] += wki * Wk[j];
+      }
+    }
+  });
+  for (int i = 0; i < N; ++i) for (int j = 0; j < i; ++j) Lambda[(size_t)ld * j + i] = Lambda[(size_t)ld * i + j];
+  // The pivot ratio is only a lower bound (a rotated matrix hides its small eigenvalues from the diagonal of L): the condition number itself, as the product
+  // of the largest eigenvalues of C = L L^T and of Lambda, each by 40 power steps from a fixed start (Rayleigh quotients: lower bounds again, within a few
+  // per cent after the first steps).  N^2 work per step beside the N^3 above.
+  auto top_eigenvalue = [&](auto&& apply) {
+    std::vector<double> x((size_t)N), y((size_t)N);
+    uint64_t lcg = 0x9e3779b97f4a7c15ull;
+    for (int i = 0; i < N; ++i) { lcg = lcg * 6364136223846793005ull + 1442695040888963407ull; x[i] = 0.5 + (double)(lcg >> 11) / 9007199254740992.0; }
+    double ev = 0.0;
+    for (int it = 0; it < 40; ++it) {
+      double nx = 0.0;
+      for (int i = 0; i < N; ++i) nx += x[i] * x[i];
+      nx = std::sqrt(nx);
+      if (!(nx > 0.0) || !std::isfinite(nx)) return std::numeric_limits<double>::infinity();
+      for (int i = 0; i < N; ++i) x[i] /= nx;
+      apply(x.data(), y.data());
+      ev = 0.0;
+      for (int i = 0; i < N; ++i) ev += x[i] * y[i];
+      x.swap(y);
+    }
+    return ev;
+  };
+  std::vector<double> t((size_t)N);
+  const double ev_c = top_eigenvalue([&](const double* x, double* y) {   // y = L (L^T x)
+    std::fill(t.begin(), t.end(), 0.0);
+    for (int i = 0; i < N; ++i) { const double* Li = A + (size_t)N * i; const double xi = x[i]; for (int j = 0; j <= i; ++j) t[j] += Li[j] * xi; }
+    par(N, [&](int64_t i0, int64_t i1) {
+      for (int64_t i = i0; i < i1; ++i) { const double* Li = A + (size_t)N * i; double v = 0.0; for (int64_t j = 0; j <= i; ++j) v += Li[j] * t[j]; y[i] = v; }
+    });
+  });
+  const double ev_l = top_eigenvalue([&](const double* x, double* y) {
+    par(N, [&](int64_t i0, int64_t i1) {
+      for (int64_t i = i0; i < i1; ++i) { const double* Li = Lambda + (size_t)ld * i; double v = 0.0; for (int j = 0; j < N; ++j) v += Li[j] * x[j]; y[i] = v; }
+    });
+  });
+  if (!(ev_c * ev_l <= 1e13)) return false;
   return true;
 }
 

@@ -47,6 +47,14 @@ void assemble_step(obvi_ba_handle* h, double radius, bool first_iter, bool schur
     record(h, PH_SMALL, s2);
     launch_small_factors(s2, b, small_dev(h), h->d_cams.get(), h->d_pose.get(), h->d_obj.get(), rd, scal, h->knobs.small_lanes_below);
     if (side) record_end(h, PH_SMALL, s2);
+    // map group priors (include/obvi_map_group_prior.h): behind the small factors' gathers, in front of the diagonal-block kernel that reads Hdiag and g
+    const MapGroupDev mg = map_group_dev(h);
+    record(h, PH_MAP_QUAD, s2);
+    launch_map_group_quad(s2, b, mg, h->d_obj.get(), 0);
+    if (side) record_end(h, PH_MAP_QUAD, s2);
+    record(h, PH_MAP_SCATTER, s2);
+    launch_map_group_scatter(s2, b, mg, rd, scal);
+    if (side) record_end(h, PH_MAP_SCATTER, s2);
   };
   auto side_diagonal = [&] {
     record(h, PH_DIAG, s2);
@@ -127,6 +135,7 @@ static void trial_point_step(obvi_ba_handle* h, bool solve, bool exchange) {
   record(h, PH_COST);
   if (solve) launch_cost(s, b, reproj_pose_dev(h), small_dev(h), h->d_cams.get(), h->d_pc.get(), h->d_pose.get(), h->d_point.get(), h->d_obj.get(), h->d_pc_c.get(),
                          h->d_pose_c.get(), h->d_point_c.get(), h->d_obj_c.get(), 0, scal);
+  if (solve) launch_map_group_cost(s, b, map_group_dev(h), h->d_obj_c.get(), 0, scal);
   record(h, PH_COUNT);
   if (exchange) {   // (3) every rank must take the same decision: the sums and every rank's gradient maximum in one collective
     launch_pack_scalars(s, scal, h->d_xbuf.get(), h->rank, h->world, 0);
@@ -218,7 +227,7 @@ int obvi_ba_solve(obvi_ba_handle* h, const obvi_solver_params* prm, obvi_summary
   { const int vrc = validate_indices(h); if (vrc != OBVI_OK) return vrc; }
   prepare(h);
   h->pc_valid = false; h->tiles_cleared = false; h->cov_valid = false;
-  const double ms0[3] = {h->phase_ms[PH_POINT_PASS] + h->phase_ms[PH_POSE_PASS] + h->phase_ms[PH_SMALL] + h->phase_ms[PH_DIAG] + h->phase_ms[PH_POSE_CACHE],
+  const double ms0[3] = {h->phase_ms[PH_POINT_PASS] + h->phase_ms[PH_POSE_PASS] + h->phase_ms[PH_SMALL] + h->phase_ms[PH_MAP_QUAD] + h->phase_ms[PH_MAP_SCATTER] + h->phase_ms[PH_DIAG] + h->phase_ms[PH_POSE_CACHE],
                          h->phase_ms[PH_SCHUR] + h->phase_ms[PH_SCHUR_BLOCKS] + h->phase_ms[PH_CHOL] + h->phase_ms[PH_BACKSUB] + h->phase_ms[PH_APPLY], h->phase_ms[PH_COST]};
   hipStream_t s = h->stream;
 
@@ -230,6 +239,7 @@ int obvi_ba_solve(obvi_ba_handle* h, const obvi_solver_params* prm, obvi_summary
   launch_pose_cache(s, h->P, h->d_pose.get(), h->d_pc.get(), h->reproj_variant == OBVI_REPROJECTION_ANALYTIC);
   launch_cost(s, blocks_dev(h), reproj_pose_dev(h), small_dev(h), h->d_cams.get(), h->d_pc.get(), h->d_pose.get(), h->d_point.get(), h->d_obj.get(),
               h->d_pc.get(), h->d_pose.get(), h->d_point.get(), h->d_obj.get(), 1, h->d_scal.get());
+  launch_map_group_cost(s, blocks_dev(h), map_group_dev(h), h->d_obj.get(), 1, h->d_scal.get());
   const bool exchanging = h->allreduce != nullptr && !h->h_shared_ov.empty();
   if (exchanging) {
     // the fixed cost of the job, and -- in the same collective -- proof that every rank lays the shared tail out alike: the order follows the shared objects'
@@ -256,7 +266,7 @@ int obvi_ba_solve(obvi_ba_handle* h, const obvi_solver_params* prm, obvi_summary
     for (const auto& it : h->iterations) sum->final_cost = std::min(sum->final_cost, it.cost);
     sum->is_solution_usable = (term == OBVI_CONVERGENCE || term == OBVI_NO_CONVERGENCE) ? 1 : 0;
     sum->total_time_in_seconds = wall_s() - t_start;
-    sum->jacobian_evaluation_time_in_seconds = 1e-3 * (h->phase_ms[PH_POINT_PASS] + h->phase_ms[PH_POSE_PASS] + h->phase_ms[PH_SMALL] + h->phase_ms[PH_DIAG] + h->phase_ms[PH_POSE_CACHE] - ms0[0]);
+    sum->jacobian_evaluation_time_in_seconds = 1e-3 * (h->phase_ms[PH_POINT_PASS] + h->phase_ms[PH_POSE_PASS] + h->phase_ms[PH_SMALL] + h->phase_ms[PH_MAP_QUAD] + h->phase_ms[PH_MAP_SCATTER] + h->phase_ms[PH_DIAG] + h->phase_ms[PH_POSE_CACHE] - ms0[0]);
     sum->linear_solver_time_in_seconds = 1e-3 * (h->phase_ms[PH_SCHUR] + h->phase_ms[PH_SCHUR_BLOCKS] + h->phase_ms[PH_CHOL] + h->phase_ms[PH_BACKSUB] + h->phase_ms[PH_APPLY] - ms0[1]);
     sum->residual_evaluation_time_in_seconds = 1e-3 * (h->phase_ms[PH_COST] - ms0[2]);
   };

@@ -127,6 +127,12 @@ struct PlanBuilder {
       if (!ca) obj_used[a] = 1;
       if (!cb) obj_used[b] = 1;
     }
+    for (int64_t g = 0; g < h->n_mg; ++g) {   // map group priors: the whole residual block counts as soon as one member varies; every such member is a variable
+      if (!h->h_mg_active[g]) continue;
+      bool any = false;
+      for (int64_t k = h->h_mg_ptr[g]; k < h->h_mg_ptr[g + 1]; ++k) if (!h->h_object_const[h->h_mg_obj[k]]) { obj_used[h->h_mg_obj[k]] = 1; any = true; }
+      if (any) nres += h->od * (h->h_mg_ptr[g + 1] - h->h_mg_ptr[g]);
+    }
     if (!h->h_is_shared.empty()) for (int64_t o = 0; o < O; ++o) if (h->h_is_shared[o]) obj_used[o] = 1;   // shared objects exist on every rank
     pose_vid.assign((size_t)P, -1); obj_vid.assign((size_t)O, -1);
     point_var.assign((size_t)L, 0);
@@ -216,9 +222,22 @@ struct PlanBuilder {
       }
       std::vector<std::vector<int64_t>> node_objs(nodes.size() + 1);   // last slot: no tree (no variable pose)
       std::vector<int64_t> tail_objs;                                   // shared across ranks: eliminated last, in an order every rank derives alike (below)
+      // members of active map group priors are eliminated last, behind the root, group after group in the caller's order: a dense group inside the tree
+      // would couple every dissection leaf that holds a member
+      std::vector<uint8_t> in_group(h->n_mg > 0 ? (size_t)O : 0, 0);
+      std::vector<int64_t> group_objs;
+      for (int64_t g = 0; g < h->n_mg; ++g) {
+        if (!h->h_mg_active[g]) continue;
+        for (int64_t k = h->h_mg_ptr[g]; k < h->h_mg_ptr[g + 1]; ++k) {
+          const int64_t o = h->h_mg_obj[k];
+          if (obj_vid[o] < 0 || (!h->h_is_shared.empty() && h->h_is_shared[o])) continue;
+          in_group[o] = 1; group_objs.push_back(o);
+        }
+      }
       for (int64_t o = 0; o < O; ++o) {
         if (obj_vid[o] < 0) continue;
         if (!h->h_is_shared.empty() && h->h_is_shared[o]) { tail_objs.push_back(o); continue; }
+        if (!in_group.empty() && in_group[o]) continue;
         int32_t n = root;
         if (n >= 0 && fb[o] >= 0) {
           for (;;) {
@@ -230,6 +249,7 @@ struct PlanBuilder {
         node_objs[n >= 0 ? n : (int32_t)nodes.size()].push_back(o);
       }
       for (auto& v : node_objs) std::stable_sort(v.begin(), v.end(), [&](int64_t x, int64_t y) { return fa[x] < fa[y]; });
+      node_objs.back().insert(node_objs.back().end(), group_objs.begin(), group_objs.end());
       // ---- rows of the tile grid: node after node, every node starts on a tile boundary
       std::vector<int32_t> pos(nPv);
       h->h_pose_row.assign(nPv, 0); h->h_obj_row.assign(h->nOv, 0);
@@ -674,6 +694,17 @@ struct PlanBuilder {
       const int32_t va = obj_vid[h->h_mp_a[i]], vb = obj_vid[h->h_mp_b[i]];
       if (va >= 0 && vb >= 0) { const int64_t ra = h->h_obj_row[va], rb = h->h_obj_row[vb]; mark(std::max(ra, rb), h->od, std::min(ra, rb), h->od); }
     }
+    for (int64_t g = 0; g < h->n_mg; ++g) {   // every member pair of a map group prior, the later-eliminated object as the row
+      if (!h->h_mg_active[g]) continue;
+      for (int64_t k = h->h_mg_ptr[g]; k < h->h_mg_ptr[g + 1]; ++k) {
+        const int32_t va = obj_vid[h->h_mg_obj[k]];
+        if (va < 0) continue;
+        for (int64_t q = h->h_mg_ptr[g]; q < k; ++q) {
+          const int32_t vb = obj_vid[h->h_mg_obj[q]];
+          if (vb >= 0) { const int64_t ra = h->h_obj_row[va], rb = h->h_obj_row[vb]; mark(std::max(ra, rb), h->od, std::min(ra, rb), h->od); }
+        }
+      }
+    }
     // object diagonal blocks may straddle tiles
     for (int64_t w = 0; w < h->nOv; ++w) mark(h->h_obj_row[w], h->od, h->h_obj_row[w], h->od);
     for (int64_t v = 0; v < nPv; ++v) mark(h->h_pose_row[v], 6, h->h_pose_row[v], 6);
@@ -1002,7 +1033,7 @@ struct PlanBuilder {
     h->dirty = false; h->mask_dirty = false; h->pc_valid = false; h->tiles_cleared = false;
     h->plan_serial++; h->cov_valid = false;
     h->plan_pose_vid = pose_vid; h->plan_obj_vid = obj_vid; h->plan_point_var = point_var; h->plan_is_pad = h->h_is_pad;
-    h->plan_rp_active = h->h_rp_active; h->plan_bb_active = h->h_bb_active; h->plan_sp_active = h->h_sp_active; h->plan_lt_active = h->h_lt_active; h->plan_rl_active = h->h_rl_active; h->plan_mp_active = h->h_mp_active;
+    h->plan_rp_active = h->h_rp_active; h->plan_bb_active = h->h_bb_active; h->plan_sp_active = h->h_sp_active; h->plan_lt_active = h->h_lt_active; h->plan_rl_active = h->h_rl_active; h->plan_mp_active = h->h_mp_active; h->plan_mg_active = h->h_mg_active;
     h->live_rows = h->m_canon;
   }
 };
@@ -1030,7 +1061,8 @@ bool prepare_masks(obvi_ba_handle* h) {
     return true;
   };
   if (h->h_rp_active.size() != h->plan_rp_active.size() || !subset(h->h_bb_active, h->plan_bb_active) || !subset(h->h_sp_active, h->plan_sp_active) ||
-      !subset(h->h_lt_active, h->plan_lt_active) || !subset(h->h_rl_active, h->plan_rl_active) || !subset(h->h_mp_active, h->plan_mp_active)) return false;
+      !subset(h->h_lt_active, h->plan_lt_active) || !subset(h->h_rl_active, h->plan_rl_active) || !subset(h->h_mp_active, h->plan_mp_active) ||
+      !subset(h->h_mg_active, h->plan_mg_active)) return false;
   // (scratch kept between calls: a session runs this once per frame)
   std::vector<uint8_t>& pose_used = h->scr_pose_used; std::vector<uint8_t>& obj_used = h->scr_obj_used; std::vector<uint8_t>& point_used = h->scr_point_used;
   pose_used.assign(P, 0); obj_used.assign(O, 0); point_used.assign(L, 0);
@@ -1078,6 +1110,12 @@ bool prepare_masks(obvi_ba_handle* h) {
     nres += 2 * h->od;
     if (!ca) obj_used[a] = 1;
     if (!cb) obj_used[b] = 1;
+  }
+  for (int64_t g = 0; g < h->n_mg; ++g) {   // map group priors: the whole residual block counts as soon as one member varies; every such member is a variable
+    if (!h->h_mg_active[g]) continue;
+    bool any = false;
+    for (int64_t k = h->h_mg_ptr[g]; k < h->h_mg_ptr[g + 1]; ++k) if (!h->h_object_const[h->h_mg_obj[k]]) { obj_used[h->h_mg_obj[k]] = 1; any = true; }
+    if (any) nres += h->od * (h->h_mg_ptr[g + 1] - h->h_mg_ptr[g]);
   }
   if (!h->h_is_shared.empty()) for (int64_t o = 0; o < O; ++o) if (h->h_is_shared[o]) obj_used[o] = 1;
   std::vector<int32_t>& pose_vid = h->scr_pose_vid; std::vector<int32_t>& obj_vid = h->scr_obj_vid;

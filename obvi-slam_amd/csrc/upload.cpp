@@ -392,6 +392,69 @@ int obvi_map_set_pair_priors(obvi_ba_handle* h, int64_t n, const uint32_t* obj_a
   OBVI_API_END(h)
 }
 
+// include/obvi_map_group_prior.h.  Every refusal comes before the first device call and before the handle's groups change.  The dense algebra is done here,
+// once: W = L^-1 and Lambda = W^T W of every group (map_group_weights, host_util.h, on the host's workers); the device only multiplies.
+int obvi_map_set_group_priors(obvi_ba_handle* h, int64_t n_groups, const int64_t* group_ptr, const uint32_t* obj_idx, const double* mean, const double* cov, double huber) {
+  if (!h || n_groups < 0 || (n_groups > 0 && (!group_ptr || !obj_idx || !mean || !cov))) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "map_set_group_priors: bad arguments");
+  OBVI_API_BEGIN
+  const int od = h->od;
+  const int64_t n = n_groups;
+  if (n > 0 && group_ptr[0] != 0) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "map_set_group_priors: group_ptr does not start at 0");
+  for (int64_t g = 0; g < n; ++g) {
+    if (group_ptr[g + 1] < group_ptr[g]) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "map_set_group_priors: group_ptr decreases");
+    if (group_ptr[g + 1] == group_ptr[g]) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "map_set_group_priors: an empty group");
+    if ((group_ptr[g + 1] - group_ptr[g]) * od > OBVI_MAP_GROUP_MAX_ROWS) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "map_set_group_priors: a group of more than OBVI_MAP_GROUP_MAX_ROWS rows");
+  }
+  const int64_t members = n > 0 ? group_ptr[n] : 0;
+  for (int64_t k = 0; k < members; ++k) if (obj_idx[k] >= h->O) return fail(h, OBVI_ERR_OUT_OF_RANGE, "map_set_group_priors: index out of range");
+  {   // groups are disjoint: every object-object block of the reduced matrix has one writer among them
+    std::vector<uint32_t> sorted(obj_idx, obj_idx + members);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "map_set_group_priors: an object twice (in one group or in two)");
+  }
+  for (int64_t k = 0; k < members * od; ++k) if (!std::isfinite(mean[k])) return fail(h, OBVI_ERR_NUMERICAL, "map_set_group_priors: non-finite mean");
+  // layout (ba_device.h, MapGroupDev) and the dense algebra
+  std::vector<int64_t> lam_off((size_t)n + 1, 0), w_off((size_t)n + 1, 0);
+  std::vector<int32_t> slab_ptr((size_t)n + 1, 0), slab_grp, tile_ptr((size_t)n + 1, 0), tile_grp, tile_ij;
+  int64_t n_max = 0;
+  for (int64_t g = 0; g < n; ++g) {
+    const int64_t N = (group_ptr[g + 1] - group_ptr[g]) * od, ld = (N + 1) & ~(int64_t)1, nsl = map_group_slabs(N);
+    lam_off[g + 1] = lam_off[g] + N * ld; w_off[g + 1] = w_off[g] + N * N;
+    n_max = std::max(n_max, N);
+    for (int64_t sl = 0; sl < nsl; ++sl) slab_grp.push_back((int32_t)g);
+    for (int64_t ti = 0; ti < nsl; ++ti) for (int64_t tj = 0; tj <= ti; ++tj) { tile_grp.push_back((int32_t)g); tile_ij.push_back((int32_t)(ti << 16 | tj)); }
+    slab_ptr[g + 1] = (int32_t)slab_grp.size(); tile_ptr[g + 1] = (int32_t)tile_grp.size();
+  }
+  std::vector<double> W((size_t)w_off[n]), Lam((size_t)lam_off[n]), work((size_t)n_max * (size_t)n_max);
+  const int threads = h->knobs.host_threads;
+  auto par = [&](int64_t cnt, const std::function<void(int64_t, int64_t)>& fn) {   // (more ranges than workers: the rows' work is uneven)
+    parallel_ranges(cnt, (int)std::max<int64_t>(1, std::min<int64_t>(4 * threads, cnt / 8)), [&](int, int64_t i0, int64_t i1) { fn(i0, i1); });
+  };
+  size_t c_off = 0;
+  for (int64_t g = 0; g < n; ++g) {
+    const int N = (int)((group_ptr[g + 1] - group_ptr[g]) * od), ld = (N + 1) & ~1;
+    if (!map_group_weights(cov + c_off, N, &W[(size_t)w_off[g]], &Lam[(size_t)lam_off[g]], ld, work.data(), par))
+      return fail(h, OBVI_ERR_NUMERICAL, "map_set_group_priors: covariance not SPD, or numerically singular");
+    c_off += (size_t)N * N;
+  }
+  OBVI_HIP(hipSetDevice(h->device));
+  h->n_mg = n; h->mg_huber = huber; h->max_mg_obj = max_index(obj_idx, members); h->mg_rows = members * od;
+  h->mg_slabs = (int64_t)slab_grp.size(); h->mg_tiles = (int64_t)tile_grp.size();
+  h->h_mg_ptr.assign(group_ptr, group_ptr + (n > 0 ? n + 1 : 0)); if (n == 0) h->h_mg_ptr.assign(1, 0);
+  h->h_mg_obj.assign(obj_idx, obj_idx + members); h->h_mg_active.assign((size_t)n, 1);
+  if (n > 0) {
+    hipStream_t s = h->stream;
+    h->d_mg_ptr.upload(h->h_mg_ptr, s); h->d_mg_obj.upload(h->h_mg_obj, s); h->d_mg_mean.upload(mean, (size_t)(members * od), s); h->d_mg_active.upload(h->h_mg_active, s);
+    h->d_mg_lam_off.upload(lam_off, s); h->d_mg_w_off.upload(w_off, s); h->d_mg_Lambda.upload(Lam, s); h->d_mg_W.upload(W, s);
+    h->d_mg_slab_ptr.upload(slab_ptr, s); h->d_mg_slab_grp.upload(slab_grp, s); h->d_mg_tile_ptr.upload(tile_ptr, s); h->d_mg_tile_grp.upload(tile_grp, s); h->d_mg_tile_ij.upload(tile_ij, s);
+    h->d_mg_y.resize((size_t)h->mg_rows); h->d_mg_partial.resize((size_t)h->mg_slabs);
+    sync(h);   // (the matrices went straight from the local vectors)
+  }
+  h->dirty = true;
+  return OBVI_OK;
+  OBVI_API_END(h)
+}
+
 int obvi_ba_set_active_mask(obvi_ba_handle* h, int32_t type, const uint8_t* mask) {
   if (!h) return OBVI_ERR_INVALID_ARGUMENT;
   OBVI_API_BEGIN
@@ -411,6 +474,7 @@ int obvi_ba_set_active_mask(obvi_ba_handle* h, int32_t type, const uint8_t* mask
     case OBVI_FACTOR_LTM_PRIOR: set_mask<uint32_t>(h->h_lt_active, h->d_lt_active, mask, h->n_lt, s, nullptr); break;
     case OBVI_FACTOR_REL_POSE: set_mask<uint32_t>(h->h_rl_active, h->d_rl_active, mask, h->n_rl, s, nullptr); break;
     case OBVI_FACTOR_MAP_PAIR_PRIOR: set_mask<uint32_t>(h->h_mp_active, h->d_mp_active, mask, h->n_mp, s, nullptr); break;
+    case OBVI_FACTOR_MAP_GROUP_PRIOR: set_mask<uint32_t>(h->h_mg_active, h->d_mg_active, mask, h->n_mg, s, nullptr); break;
     default: return fail(h, OBVI_ERR_INVALID_ARGUMENT, "set_active_mask: unknown factor type");
   }
   finish_upload(h);
@@ -424,9 +488,9 @@ int64_t obvi_ba_num_factors(const obvi_ba_handle* h, int32_t type) {
   switch (type) {
     case OBVI_FACTOR_REPROJECTION: return h->n_rp; case OBVI_FACTOR_BBOX: return h->n_bb; case OBVI_FACTOR_SHAPE_PRIOR: return h->n_sp;
     case OBVI_FACTOR_LTM_PRIOR: return h->n_lt; case OBVI_FACTOR_REL_POSE: return h->n_rl;
-    case OBVI_FACTOR_MAP_PAIR_PRIOR: return h->n_mp; default: return -1;
+    case OBVI_FACTOR_MAP_PAIR_PRIOR: return h->n_mp; case OBVI_FACTOR_MAP_GROUP_PRIOR: return h->n_mg; default: return -1;
   }
 }
-int64_t obvi_ba_num_residuals(const obvi_ba_handle* h) { return h ? 2 * h->n_rp + 4 * h->n_bb + 3 * h->n_sp + h->od * h->n_lt + 6 * h->n_rl + 2 * h->od * h->n_mp : -1; }
+int64_t obvi_ba_num_residuals(const obvi_ba_handle* h) { return h ? 2 * h->n_rp + 4 * h->n_bb + 3 * h->n_sp + h->od * h->n_lt + 6 * h->n_rl + 2 * h->od * h->n_mp + h->mg_rows : -1; }
 
 }  // extern "C"

@@ -17,6 +17,8 @@ FACTOR_LTM_PRIOR = 4
 FACTOR_REL_POSE = 5
 FACTOR_MAP_PAIR_PRIOR = 9    # include/obvi_map_prior.h: not in FACTOR_TYPES (the oracle does not know it)
 MAP_PAIR_JOINT, MAP_PAIR_CONDITIONAL = 0, 1
+FACTOR_MAP_GROUP_PRIOR = 10  # include/obvi_map_group_prior.h: a Gaussian on a group of objects (not in FACTOR_TYPES either)
+MAP_GROUP_MAX_ROWS = 2048
 FACTOR_TYPES = (FACTOR_REPROJECTION, FACTOR_BBOX, FACTOR_SHAPE_PRIOR, FACTOR_LTM_PRIOR, FACTOR_REL_POSE)
 RESIDUAL_DIM = {0: 2, 2: 4, 3: 3, 4: 7, 5: 6, 9: 14}
 BLOCK_DIMS = {0: (6, 3), 2: (7, 6), 3: (7, 0), 4: (7, 0), 5: (6, 6), 9: (7, 7)}
@@ -116,7 +118,8 @@ class BundleAdjuster:
         opt = Options(device_id, self.od, int(reprojection_variant), 1 if deterministic else 0)
         self._check(self._fn("ba_create")(C.byref(opt), C.byref(self._h)), "create")
         self._keep = []
-        self._n = {t: 0 for t in FACTOR_TYPES + (FACTOR_MAP_PAIR_PRIOR,)}
+        self._n = {t: 0 for t in FACTOR_TYPES + (FACTOR_MAP_PAIR_PRIOR, FACTOR_MAP_GROUP_PRIOR)}
+        self._mg_sizes = []
         self.P = self.L = self.O = 0
 
     def _fn(self, name):
@@ -235,6 +238,26 @@ class BundleAdjuster:
                       _ptr(cv, C.c_double), _ptr(fm, C.c_uint8), C.c_double(huber)), "map_set_pair_priors")
         self._n[FACTOR_MAP_PAIR_PRIOR] = len(ia)
 
+    def set_map_group_priors(self, groups, means, covs, huber=1.0):
+        """Joint Gaussian priors on groups of objects (include/obvi_map_group_prior.h): groups = a list of object-index lists, means = per group [k][od],
+        covs = per group [k od][k od]; empty lists clear the factors."""
+        try:
+            f = getattr(self._lib, self._pre + "map_set_group_priors")
+        except AttributeError:
+            raise ObviError("%smap_set_group_priors: this library has no map group priors (include/obvi_map_group_prior.h is served by libobvi_ba.so only)" % self._pre)
+        f.restype = C.c_int
+        sizes = [len(g) for g in groups]
+        ptr = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        idx = np.ascontiguousarray(np.concatenate([np.asarray(g, dtype=np.uint32).ravel() for g in groups]) if groups else np.zeros(0), dtype=np.uint32)
+        mu = _f64(np.concatenate([np.asarray(m, dtype=np.float64).reshape(-1, self.od) for m in means]) if groups else np.zeros((0, self.od)), (-1, self.od))
+        cv = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.float64).ravel() for c in covs]) if groups else np.zeros(0), dtype=np.float64)
+        if len(mu) != ptr[-1] or len(cv) != sum((k * self.od) ** 2 for k in sizes):
+            raise ObviError("map_set_group_priors: means / covs do not match the groups")
+        self._check(f(self._h, C.c_int64(len(sizes)), _ptr(ptr, C.c_int64), _ptr(idx, C.c_uint32), _ptr(mu, C.c_double), _ptr(cv, C.c_double), C.c_double(huber)),
+                    "map_set_group_priors")
+        self._n[FACTOR_MAP_GROUP_PRIOR] = len(sizes)
+        self._mg_sizes = sizes
+
     def set_active_mask(self, factor_type, mask):
         m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
         self._check(self._fn("ba_set_active_mask")(self._h, C.c_int32(factor_type), _ptr(m, C.c_uint8)), "set_active_mask")
@@ -247,7 +270,7 @@ class BundleAdjuster:
         return self.od if t == 4 else 2 * self.od if t == 9 else RESIDUAL_DIM[t]        # an LTM prior has one residual per ellipsoid parameter, a map pair prior two
 
     def num_residuals(self):
-        return sum(self._residual_dim(t) * n for t, n in self._n.items())
+        return sum(self._residual_dim(t) * n for t, n in self._n.items() if t != FACTOR_MAP_GROUP_PRIOR) + self.od * sum(self._mg_sizes)   # (a group prior: od per member)
 
     def evaluate(self, apply_loss=True, want_residuals=True):
         cost = C.c_double(0.0)
@@ -417,7 +440,8 @@ class BundleAdjuster:
     def reset(self):
         """obvi_ba_reset: the handle as create left it (no problem, no hook, nothing shared), allocations kept."""
         self._check(self._fn("ba_reset")(self._h), "reset")
-        self._n = {t: 0 for t in FACTOR_TYPES + (FACTOR_MAP_PAIR_PRIOR,)}
+        self._n = {t: 0 for t in FACTOR_TYPES + (FACTOR_MAP_PAIR_PRIOR, FACTOR_MAP_GROUP_PRIOR)}
+        self._mg_sizes = []
         self.P = self.L = self.O = 0
         self._keep.clear()
 
@@ -486,6 +510,12 @@ class BundleAdjuster:
         return {name: getattr(p, name) for name, _ in Peaks._fields_ if name != "reserved"}
 
     def debug_linearize(self, factor_type):
+        if factor_type == FACTOR_MAP_GROUP_PRIOR:       # r of all groups, and per group its lower triangular W; no second block
+            rows = [self.od * k for k in self._mg_sizes]
+            r, W = np.zeros(sum(rows)), np.zeros(sum(n * n for n in rows))
+            self._check(self._fn("ba_debug_linearize")(self._h, C.c_int32(factor_type), _ptr(r, C.c_double), _ptr(W, C.c_double), None), "debug_linearize")
+            ro, wo = np.concatenate([[0], np.cumsum(rows)]).astype(int), np.concatenate([[0], np.cumsum([n * n for n in rows])]).astype(int)
+            return [r[ro[g]:ro[g + 1]] for g in range(len(rows))], [W[wo[g]:wo[g + 1]].reshape(rows[g], rows[g]) for g in range(len(rows))], None
         n, m = self._n[factor_type], self._residual_dim(factor_type)
         d0, d1 = (self.od if d == 7 else d for d in BLOCK_DIMS[factor_type])
         r, J0 = np.zeros((n, m)), np.zeros((n, m, d0))
