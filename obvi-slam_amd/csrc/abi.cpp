@@ -199,13 +199,14 @@ int obvi_ba_evaluate(obvi_ba_handle* h, int32_t apply_loss, double* cost, double
   { const int vrc = validate_indices(h); if (vrc != OBVI_OK) return vrc; }
   prepare(h);
   hipStream_t s = h->stream;
-  const int64_t nres = obvi_ba_num_residuals(h), nfac = h->n_rp + h->n_bb + h->n_sp + h->n_lt + h->n_rl + h->n_mp + h->n_mg;
+  const EvalLayout lay = families(h).layout();
+  const int64_t nres = lay.row[FAM_COUNT], nfac = lay.slot[FAM_COUNT];
   h->d_eval_res.resize((size_t)nres + 1); h->d_eval_sq.resize((size_t)nfac + 1);
   OBVI_HIP(hipMemsetAsync(h->d_scal.get(), 0, sizeof(double) * SC_COUNT, s));
   launch_pose_cache(s, h->P, h->d_pose.get(), h->d_pc.get(), h->reproj_variant == OBVI_REPROJECTION_ANALYTIC);
   launch_evaluate(s, blocks_dev(h), reproj_dev(h), h->d_rp_perm.get(), small_dev(h), h->d_cams.get(), h->d_pc.get(), h->d_pose.get(),
-                  h->d_point.get(), h->d_obj.get(), apply_loss, h->d_eval_res.get(), h->d_eval_sq.get(), h->d_scal.get());
-  launch_map_group_eval(s, blocks_dev(h), map_group_dev(h), h->d_obj.get(), apply_loss, h->d_eval_res.get() + (nres - h->mg_rows), h->d_eval_sq.get() + (nfac - h->n_mg), h->d_scal.get());   // (behind the pair priors)
+                  h->d_point.get(), h->d_obj.get(), apply_loss, lay, h->d_eval_res.get(), h->d_eval_sq.get(), h->d_scal.get());
+  launch_map_group_eval(s, blocks_dev(h), map_group_dev(h), h->d_obj.get(), apply_loss, h->d_eval_res.get() + lay.row[FAM_MG], h->d_eval_sq.get() + lay.slot[FAM_MG], h->d_scal.get());
   if (!cost && !residuals && !block_sqnorm) return OBVI_OK;   // nothing to hand back (obvi_ba_select_outliers: its kernels follow on the same stream)
   double c = 0.0;
   OBVI_HIP(hipMemcpyAsync(&c, h->d_scal.get() + SC_COST, sizeof(double), hipMemcpyDeviceToHost, s));
@@ -236,16 +237,10 @@ int obvi_ba_debug_linearize(obvi_ba_handle* h, int32_t type, double* r, double* 
     sync(h);
     return OBVI_OK;
   }
-  int m, d0, d1; int64_t n;
-  switch (type) {
-    case OBVI_FACTOR_REPROJECTION: m = 2; d0 = 6; d1 = 3; n = h->n_rp; break;
-    case OBVI_FACTOR_BBOX: m = 4; d0 = h->od; d1 = 6; n = h->n_bb; break;
-    case OBVI_FACTOR_SHAPE_PRIOR: m = 3; d0 = h->od; d1 = 0; n = h->n_sp; break;
-    case OBVI_FACTOR_LTM_PRIOR: m = h->od; d0 = h->od; d1 = 0; n = h->n_lt; break;
-    case OBVI_FACTOR_REL_POSE: m = 6; d0 = 6; d1 = 6; n = h->n_rl; break;
-    case OBVI_FACTOR_MAP_PAIR_PRIOR: m = 2 * h->od; d0 = h->od; d1 = h->od; n = h->n_mp; break;
-    default: return fail(h, OBVI_ERR_INVALID_ARGUMENT, "debug_linearize: unknown factor type");
-  }
+  const FamilyTable fams = families(h);
+  const FactorFamily* f = fams.find(type);
+  if (!f) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "debug_linearize: unknown factor type");
+  const int m = f->m, d0 = f->d0, d1 = f->d1; const int64_t n = f->n;
   DevBuf<double> dr, dJ0, dJ1;
   dr.resize((size_t)n * m + 1); dJ0.resize((size_t)n * m * d0 + 1); dJ1.resize((size_t)n * m * d1 + 1);
   if (type == OBVI_FACTOR_REPROJECTION) {
@@ -439,24 +434,15 @@ int obvi_ba_select_outliers(obvi_ba_handle* h, int32_t type, double fraction, ui
     const int rc = obvi_ba_evaluate(h, 0, nullptr, nullptr, nullptr);
     if (rc != OBVI_OK) return rc;
   }
-  int64_t off = 0, n = 0;
-  const uint8_t* act = nullptr;
-  const uint32_t* inv = nullptr;
-  switch (type) {
-    case OBVI_FACTOR_REPROJECTION:
-      off = 0; n = h->n_rp; act = h->d_rp_active.get();
-      if (!h->rp_inv_on_device) { h->d_rp_inv.upload(h->h_rp_inv, h->stream); h->rp_inv_on_device = true; }
-      inv = h->d_rp_inv.get();
-      break;
-    case OBVI_FACTOR_BBOX: off = h->n_rp; n = h->n_bb; act = h->d_bb_active.get(); break;
-    case OBVI_FACTOR_SHAPE_PRIOR: off = h->n_rp + h->n_bb; n = h->n_sp; act = h->d_sp_active.get(); break;
-    case OBVI_FACTOR_LTM_PRIOR: off = h->n_rp + h->n_bb + h->n_sp; n = h->n_lt; act = h->d_lt_active.get(); break;
-    case OBVI_FACTOR_REL_POSE: off = h->n_rp + h->n_bb + h->n_sp + h->n_lt; n = h->n_rl; act = h->d_rl_active.get(); break;
-    case OBVI_FACTOR_MAP_PAIR_PRIOR: off = h->n_rp + h->n_bb + h->n_sp + h->n_lt + h->n_rl; n = h->n_mp; act = h->d_mp_active.get(); break;
-    case OBVI_FACTOR_MAP_GROUP_PRIOR: off = h->n_rp + h->n_bb + h->n_sp + h->n_lt + h->n_rl + h->n_mp; n = h->n_mg; act = h->d_mg_active.get(); break;
-    default: return fail(h, OBVI_ERR_INVALID_ARGUMENT, "select_outliers: unknown factor type");
+  const FamilyTable fams = families(h);
+  const FactorFamily* f = fams.find(type);
+  if (!f) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "select_outliers: unknown factor type");
+  const uint32_t* inv = nullptr;   // reprojection: the norms are in the sorted order, the mask goes out in the caller's
+  if (type == OBVI_FACTOR_REPROJECTION) {
+    if (!h->rp_inv_on_device) { h->d_rp_inv.upload(h->h_rp_inv, h->stream); h->rp_inv_on_device = true; }
+    inv = h->d_rp_inv.get();
   }
-  run_selection(h, n, h->d_eval_sq.get() + off, act, inv, fraction, mask_out, num_excluded);
+  run_selection(h, f->n, h->d_eval_sq.get() + fams.layout().slot[fams.index(f)], f->d_active->get(), inv, fraction, mask_out, num_excluded);
   h->eval_sq_call = h->api_calls;   // (the evaluate above counted as a call of its own)
   return OBVI_OK;
   OBVI_API_END(h)

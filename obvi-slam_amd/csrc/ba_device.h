@@ -94,10 +94,17 @@ inline int64_t eval_small_grid(int64_t n_small) { return blocks_of(n_small, 64);
 // matrix, k_map_group_scatter one per 64 x 64 tile of its lower triangle, k_map_group_cost one per group
 inline int64_t map_group_slabs(int64_t rows) { return blocks_of(rows, 64); }
 inline int64_t map_group_tiles(int64_t rows) { const int64_t t = blocks_of(rows, 64); return t * (t + 1) / 2; }
+// The factor families in the order obvi_ba_evaluate lays them out (DESIGN.md "Factor families"; the table of their records: ba_handle.h), and that layout:
+// per family its first block norm and its first residual row, at [FAM_COUNT] the totals
+enum Family { FAM_RP = 0, FAM_BB, FAM_SP, FAM_LT, FAM_RL, FAM_MP, FAM_MG, FAM_COUNT };
+struct EvalLayout { int64_t slot[FAM_COUNT + 1], row[FAM_COUNT + 1]; };
+// the factors that k_cost and k_eval_small give a thread each: every family of SmallFactorsDev (c: it, or DetCounts)
+template <class C>
+inline int64_t num_small_factors(const C& c) { return c.n_bb + c.n_sp + c.n_lt + c.n_rl + c.n_mp; }
 // the largest of those grids (launch_backsub_apply takes at most 32 lanes per feature), at least 1 for an empty problem: the stride is also the mode's flag
 struct DetCounts { int64_t P, L, O, od, n_rp, n_point_waves, n_long_points, n_bb, n_sp, n_lt, n_rl, n_mp = 0, mg_tiles = 0; };   // (mg_tiles: the scatter grid, the largest of the group kernels')
 inline int64_t det_slots_needed(const DetCounts& c) {
-  const int64_t ns = c.n_bb + c.n_sp + c.n_lt + c.n_rl + c.n_mp;
+  const int64_t ns = num_small_factors(c);
   return std::max<int64_t>({1, point_pass_grid(c.n_point_waves), point_pass_long_grid(c.n_long_points), small_lin_grid(c.n_bb, c.n_sp + c.n_lt, c.n_rl, c.n_mp, c.od),
                             reduced_diag_grid(c.P, c.O, c.od), backsub_grid(c.L, c.P, c.O, 32), cost_grid(c.P, c.n_rp, ns), eval_reproj_grid(c.n_rp), eval_small_grid(ns), c.mg_tiles});
 }
@@ -257,10 +264,10 @@ void launch_cost(hipStream_t s, const BlocksDev& b, const ReprojPoseDev& rq, con
                  const PoseCache* pc_cur, const double* poses_cur, const double* points_cur, const double* objects_cur,
                  const PoseCache* pc_cand, const double* poses_cand, const double* points_cand, const double* objects_cand,
                  int mode, double* scal);
-// problem->Evaluate: raw / robustified residuals of every factor in caller order
+// problem->Evaluate: raw / robustified residuals of every factor in caller order, family after family as `lay` places them (the map group priors: launch_map_group_eval)
 void launch_evaluate(hipStream_t s, const BlocksDev& b, const ReprojDev& rp, const uint32_t* rp_perm, const SmallFactorsDev& sf,
                      const DevCam* cams, const PoseCache* pc, const double* poses, const double* points, const double* objects,
-                     int apply_loss, double* residuals, double* sqnorm, double* scal);
+                     int apply_loss, const EvalLayout& lay, double* residuals, double* sqnorm, double* scal);
 void launch_debug_linearize_reproj(hipStream_t s, const ReprojDev& rp, const uint32_t* rp_perm, const DevCam* cams,
                                    const PoseCache* pc, const double* points, double* r, double* J0, double* J1);
 void launch_debug_linearize_small(hipStream_t s, int factor_type, const SmallFactorsDev& sf, const DevCam* cams,

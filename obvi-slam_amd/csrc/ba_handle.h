@@ -283,6 +283,74 @@ struct obvi_ba_handle {
 
 namespace obvi_lib {
 
+// ---- factor families (DESIGN.md "Factor families") ----
+// One record per family, in evaluate order (Family, ba_device.h): what the host has to know of a family without knowing which one it is.  The handle keeps
+// every family as prefixed members (n_bb, h_bb_active, ...); families() is the one place that says which members are whose, built on the stack when asked.
+struct FactorFamily {
+  int32_t type; const char* name;      // OBVI_FACTOR_*; the family in error messages
+  int64_t n, rows;                     // factors; residual rows of all of them
+  int32_t m, d0, d1;                   // residual rows of one factor (0: od x members, group by group) and the widths of its two blocks in obvi_ba_debug_linearize
+  std::vector<uint8_t>* h_active; DevBuf<uint8_t>* d_active; std::vector<uint8_t>* plan_active;   // the mask on the host, on the device, and as the plan was built for it
+  int64_t max_pose, max_point, max_obj, max_cam;   // largest index of each kind the family refers to (-1: none)
+};
+struct FamilyTable {
+  FactorFamily f[FAM_COUNT];
+  const FactorFamily* find(int32_t type) const { for (const FactorFamily& x : f) if (x.type == type) return &x; return nullptr; }   // null: not a factor type
+  Family index(const FactorFamily* x) const { return (Family)(x - f); }
+  EvalLayout layout() const {
+    EvalLayout l; l.slot[0] = l.row[0] = 0;
+    for (int i = 0; i < FAM_COUNT; ++i) { l.slot[i + 1] = l.slot[i] + f[i].n; l.row[i + 1] = l.row[i] + f[i].rows; }
+    return l;
+  }
+};
+inline FamilyTable families(const obvi_ba_handle* handle) {
+  obvi_ba_handle* h = const_cast<obvi_ba_handle*>(handle);   // (the masks are handed out writable: obvi_ba_set_active_mask)
+  const int od = h->od;
+  return {{
+      {OBVI_FACTOR_REPROJECTION, "reprojection factors", h->n_rp, 2 * h->n_rp, 2, 6, 3, &h->h_rp_active, &h->d_rp_active, &h->plan_rp_active, h->max_rp_pose, h->max_rp_point, -1, h->max_rp_cam},
+      {OBVI_FACTOR_BBOX, "bounding-box factors", h->n_bb, 4 * h->n_bb, 4, od, 6, &h->h_bb_active, &h->d_bb_active, &h->plan_bb_active, h->max_bb_pose, -1, h->max_bb_obj, h->max_bb_cam},
+      {OBVI_FACTOR_SHAPE_PRIOR, "shape priors", h->n_sp, 3 * h->n_sp, 3, od, 0, &h->h_sp_active, &h->d_sp_active, &h->plan_sp_active, -1, -1, h->max_sp_obj, -1},
+      {OBVI_FACTOR_LTM_PRIOR, "long-term-map priors", h->n_lt, od * h->n_lt, od, od, 0, &h->h_lt_active, &h->d_lt_active, &h->plan_lt_active, -1, -1, h->max_lt_obj, -1},
+      {OBVI_FACTOR_REL_POSE, "relative-pose factors", h->n_rl, 6 * h->n_rl, 6, 6, 6, &h->h_rl_active, &h->d_rl_active, &h->plan_rl_active, h->max_rl_pose, -1, -1, -1},
+      {OBVI_FACTOR_MAP_PAIR_PRIOR, "map pair priors", h->n_mp, 2 * od * h->n_mp, 2 * od, od, od, &h->h_mp_active, &h->d_mp_active, &h->plan_mp_active, -1, -1, h->max_mp_obj, -1},
+      {OBVI_FACTOR_MAP_GROUP_PRIOR, "map group priors", h->n_mg, h->mg_rows, 0, 0, 0, &h->h_mg_active, &h->d_mg_active, &h->plan_mg_active, -1, -1, h->max_mg_obj, -1},
+  }};
+}
+
+// The reduced program's share of every family but the reprojection factors (their loops are plan.cpp's own) and of the shared objects: a factor counts unless
+// all its blocks are constant, and its variable blocks are variables of the solve.  Marks those in pose_used [P] / obj_used [O]; returns the residual rows.
+// The full plan and the mask-only re-plan both take it from here, so they cannot disagree.
+inline int64_t reduce_small_families(const obvi_ba_handle* h, uint8_t* pose_used, uint8_t* obj_used) {
+  const FamilyTable fams = families(h);
+  const uint8_t* pose_const = h->h_pose_const.data(); const uint8_t* obj_const = h->h_object_const.data();
+  int64_t nres = 0;
+  // a family of factors on blocks (a[i], b[i]); one block: the same array on both sides
+  auto walk = [&](Family fam, const std::vector<uint32_t>& a, const uint8_t* a_const, uint8_t* a_used, const std::vector<uint32_t>& b, const uint8_t* b_const, uint8_t* b_used) {
+    const FactorFamily& f = fams.f[fam];
+    const uint8_t* active = f.h_active->data();
+    for (int64_t i = 0; i < f.n; ++i) {
+      if (!active[i]) continue;
+      const bool ca = a_const[a[i]], cb = b_const[b[i]];
+      if (ca && cb) continue;
+      nres += f.m;
+      if (!ca) a_used[a[i]] = 1;
+      if (!cb) b_used[b[i]] = 1;
+    }
+  };
+  walk(FAM_BB, h->h_bb_obj, obj_const, obj_used, h->h_bb_pose, pose_const, pose_used);
+  walk(FAM_SP, h->h_sp_obj, obj_const, obj_used, h->h_sp_obj, obj_const, obj_used);
+  walk(FAM_LT, h->h_lt_obj, obj_const, obj_used, h->h_lt_obj, obj_const, obj_used);
+  walk(FAM_RL, h->h_rl_a, pose_const, pose_used, h->h_rl_b, pose_const, pose_used);
+  walk(FAM_MP, h->h_mp_a, obj_const, obj_used, h->h_mp_b, obj_const, obj_used);   // an object that map priors alone touch is a variable of the solve
+  for (int64_t g = 0; g < h->n_mg; ++g) {   // map group priors: the whole residual block counts as soon as one member varies; every such member is a variable
+    if (!h->h_mg_active[g]) continue;
+    bool any = false;
+    for (int64_t k = h->h_mg_ptr[g]; k < h->h_mg_ptr[g + 1]; ++k) if (!obj_const[h->h_mg_obj[k]]) { obj_used[h->h_mg_obj[k]] = 1; any = true; }
+    if (any) nres += h->od * (h->h_mg_ptr[g + 1] - h->h_mg_ptr[g]);
+  }
+  if (!h->h_is_shared.empty()) for (int64_t o = 0; o < h->O; ++o) if (h->h_is_shared[o]) obj_used[o] = 1;   // shared objects exist on every rank
+  return nres;
+}
 
 inline int fail(obvi_ba_handle* h, int code, const std::string& msg) {
   if (h) h->err = msg;
@@ -509,18 +577,14 @@ inline void parallel_ranges(int64_t n, int parts, F&& fn) {
 inline int validate_indices(obvi_ba_handle* h) {
   const int64_t ncam = (int64_t)h->h_cams.size();
   auto bad = [&](const char* what) { return fail(h, OBVI_ERR_OUT_OF_RANGE, std::string(what) + " refer to a block that is not in the current upload (blocks / cameras were re-uploaded after the factors)"); };
-  if (h->n_rp > 0 && (h->max_rp_pose >= h->P || h->max_rp_point >= h->L || h->max_rp_cam >= ncam)) return bad("reprojection factors");
+  const FamilyTable fams = families(h);
+  for (const FactorFamily& f : fams.f)
+    if (f.n > 0 && (f.max_pose >= h->P || f.max_point >= h->L || f.max_obj >= h->O || f.max_cam >= ncam)) return bad(f.name);
   if (h->n_rp > 0 && (int64_t)h->h_point_ptr.size() != h->L + 1) return bad("reprojection factors (point count changed)");
-  if (h->n_bb > 0 && (h->max_bb_obj >= h->O || h->max_bb_pose >= h->P || h->max_bb_cam >= ncam)) return bad("bounding-box factors");
-  if (h->n_sp > 0 && h->max_sp_obj >= h->O) return bad("shape priors");
-  if (h->n_lt > 0 && h->max_lt_obj >= h->O) return bad("long-term-map priors");
-  if (h->n_rl > 0 && h->max_rl_pose >= h->P) return bad("relative-pose factors");
-  if (h->n_mp > 0 && h->max_mp_obj >= h->O) return bad("map pair priors");
   // map pair priors couple two object blocks on one handle; across handles that exchange shared objects they are not built (include/obvi_map_prior.h):
   // refused here, before the plan and before any collective
   if (h->n_mp > 0 && h->allreduce != nullptr && std::any_of(h->h_is_shared.begin(), h->h_is_shared.end(), [](uint8_t v) { return v != 0; }))
     return fail(h, OBVI_ERR_INVALID_ARGUMENT, "map pair priors on a handle that exchanges shared objects: the collective form is not built");
-  if (h->n_mg > 0 && h->max_mg_obj >= h->O) return bad("map group priors");
   if (h->n_mg > 0 && h->allreduce != nullptr && std::any_of(h->h_is_shared.begin(), h->h_is_shared.end(), [](uint8_t v) { return v != 0; }))
     return fail(h, OBVI_ERR_INVALID_ARGUMENT, "map group priors on a handle that exchanges shared objects: the collective form is not built");
   if (h->n_mg > 0 && h->n_mp > 0) {   // a pair prior inside a group: the pair's block would have two writers, its information would count twice

@@ -12,6 +12,7 @@
 
 #include <cstdlib>
 #include <stdexcept>
+#include "../../include/obvi_map_prior.h"   // OBVI_FACTOR_* (launch_debug_linearize_small)
 #include "ba_device.h"
 
 namespace obvi {
@@ -2096,27 +2097,20 @@ void launch_cost(hipStream_t s, const BlocksDev& b, const ReprojPoseDev& rq, con
   const double* points = mode == 0 ? points_cand : points_cur;
   const double* objects = mode == 0 ? objects_cand : objects_cur;
   const int n_pose_blocks = (int)cost_grid(b.P, rq.n, 0);
-  launch_reducing(s, b, scal, cost_grid(b.P, rq.n, sf.n_bb + sf.n_sp + sf.n_lt + sf.n_rl + sf.n_mp), mode == 0 ? OBVI_SC(SC_COST_CAND) : OBVI_SC(SC_COST_FIXED), [&](dim3 g) {
+  launch_reducing(s, b, scal, cost_grid(b.P, rq.n, num_small_factors(sf)), mode == 0 ? OBVI_SC(SC_COST_CAND) : OBVI_SC(SC_COST_FIXED), [&](dim3 g) {
     if (b.P <= 256) hipLaunchKernelGGL(k_cost<true>, g, dim3(kBlock), 0, s, b, rq, sf, cams, pc, poses, points, objects, mode, n_pose_blocks, scal);   // (few poses: cost_reproj_block)
     else hipLaunchKernelGGL(k_cost<false>, g, dim3(kBlock), 0, s, b, rq, sf, cams, pc, poses, points, objects, mode, n_pose_blocks, scal); });
 }
 void launch_evaluate(hipStream_t s, const BlocksDev& b, const ReprojDev& rp, const uint32_t* rp_perm, const SmallFactorsDev& sf, const DevCam* cams,
-                     const PoseCache* pc, const double* poses, const double* points, const double* objects, int apply_loss, double* residuals,
-                     double* sqnorm, double* scal) {
+                     const PoseCache* pc, const double* poses, const double* points, const double* objects, int apply_loss, const EvalLayout& lay,
+                     double* residuals, double* sqnorm, double* scal) {
   launch_reducing(s, b, scal, eval_reproj_grid(rp.n), OBVI_SC(SC_COST), [&](dim3 g) {
     hipLaunchKernelGGL(k_eval_reproj, g, dim3(kBlock), 0, s, rp, rp_perm, cams, pc, points, apply_loss, residuals, sqnorm, scal, b.deterministic); });
-  double* r_bb = residuals ? residuals + 2 * rp.n : nullptr;
-  double* r_sp = residuals ? r_bb + 4 * sf.n_bb : nullptr;
-  double* r_lt = residuals ? r_sp + 3 * sf.n_sp : nullptr;
-  double* r_rl = residuals ? r_lt + sf.od * sf.n_lt : nullptr;
-  double* r_mp = residuals ? r_rl + 6 * sf.n_rl : nullptr;
-  double* q_bb = sqnorm ? sqnorm + rp.n : nullptr;
-  double* q_sp = sqnorm ? q_bb + sf.n_bb : nullptr;
-  double* q_lt = sqnorm ? q_sp + sf.n_sp : nullptr;
-  double* q_rl = sqnorm ? q_lt + sf.n_lt : nullptr;
-  double* q_mp = sqnorm ? q_rl + sf.n_rl : nullptr;
-  launch_reducing(s, b, scal, eval_small_grid(sf.n_bb + sf.n_sp + sf.n_lt + sf.n_rl + sf.n_mp), OBVI_SC(SC_COST), [&](dim3 g) {
-    hipLaunchKernelGGL(k_eval_small, g, dim3(64), 0, s, sf, cams, poses, objects, apply_loss, r_bb, q_bb, r_sp, q_sp, r_lt, q_lt, r_rl, q_rl, r_mp, q_mp, scal, b.deterministic); });
+  auto r = [&](Family f) { return residuals ? residuals + lay.row[f] : nullptr; };
+  auto q = [&](Family f) { return sqnorm ? sqnorm + lay.slot[f] : nullptr; };
+  launch_reducing(s, b, scal, eval_small_grid(num_small_factors(sf)), OBVI_SC(SC_COST), [&](dim3 g) {
+    hipLaunchKernelGGL(k_eval_small, g, dim3(64), 0, s, sf, cams, poses, objects, apply_loss, r(FAM_BB), q(FAM_BB), r(FAM_SP), q(FAM_SP), r(FAM_LT), q(FAM_LT), r(FAM_RL), q(FAM_RL),
+                       r(FAM_MP), q(FAM_MP), scal, b.deterministic); });
 }
 void launch_debug_linearize_reproj(hipStream_t s, const ReprojDev& rp, const uint32_t* rp_perm, const DevCam* cams, const PoseCache* pc,
                                    const double* points, double* r, double* J0, double* J1) {
@@ -2124,7 +2118,8 @@ void launch_debug_linearize_reproj(hipStream_t s, const ReprojDev& rp, const uin
 }
 void launch_debug_linearize_small(hipStream_t s, int factor_type, const SmallFactorsDev& sf, const DevCam* cams, const double* poses,
                                   const double* objects, double* r, double* J0, double* J1) {
-  const int64_t n = factor_type == 2 ? sf.n_bb : factor_type == 3 ? sf.n_sp : factor_type == 4 ? sf.n_lt : factor_type == 5 ? sf.n_rl : sf.n_mp;
+  const int64_t n = factor_type == OBVI_FACTOR_BBOX ? sf.n_bb : factor_type == OBVI_FACTOR_SHAPE_PRIOR ? sf.n_sp : factor_type == OBVI_FACTOR_LTM_PRIOR ? sf.n_lt
+                    : factor_type == OBVI_FACTOR_REL_POSE ? sf.n_rl : sf.n_mp;
   if (n > 0) hipLaunchKernelGGL(k_debug_lin_small, dim3(grid_for(n, 64)), dim3(64), 0, s, factor_type, sf, cams, poses, objects, r, J0, J1);
 }
 __global__ void __launch_bounds__(kBlock) k_permute_rows3(double* __restrict__ dst, const double* __restrict__ src, const uint32_t* __restrict__ map, int64_t n) {

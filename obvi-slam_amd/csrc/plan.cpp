@@ -98,42 +98,7 @@ struct PlanBuilder {
       for (int64_t n : nres_t) nres += n;
       for (const auto& pu : pose_used_t) for (int64_t p = 0; p < P && !pu.empty(); ++p) pose_used[p] |= pu[p];
     }
-    for (int64_t i = 0; i < h->n_bb; ++i) {
-      if (!h->h_bb_active[i]) continue;
-      const uint32_t o = h->h_bb_obj[i], p = h->h_bb_pose[i];
-      const bool co = h->h_object_const[o], cp = h->h_pose_const[p];
-      if (co && cp) continue;
-      nres += 4;
-      if (!co) obj_used[o] = 1;
-      if (!cp) pose_used[p] = 1;
-    }
-    for (int64_t i = 0; i < h->n_sp; ++i) if (h->h_sp_active[i] && !h->h_object_const[h->h_sp_obj[i]]) { nres += 3; obj_used[h->h_sp_obj[i]] = 1; }
-    for (int64_t i = 0; i < h->n_lt; ++i) if (h->h_lt_active[i] && !h->h_object_const[h->h_lt_obj[i]]) { nres += h->od; obj_used[h->h_lt_obj[i]] = 1; }
-    for (int64_t i = 0; i < h->n_rl; ++i) {
-      if (!h->h_rl_active[i]) continue;
-      const uint32_t a = h->h_rl_a[i], b = h->h_rl_b[i];
-      const bool ca = h->h_pose_const[a], cb = h->h_pose_const[b];
-      if (ca && cb) continue;
-      nres += 6;
-      if (!ca) pose_used[a] = 1;
-      if (!cb) pose_used[b] = 1;
-    }
-    for (int64_t i = 0; i < h->n_mp; ++i) {   // map pair priors: an object they alone touch is a variable of the solve
-      if (!h->h_mp_active[i]) continue;
-      const uint32_t a = h->h_mp_a[i], b = h->h_mp_b[i];
-      const bool ca = h->h_object_const[a], cb = h->h_object_const[b];
-      if (ca && cb) continue;
-      nres += 2 * h->od;
-      if (!ca) obj_used[a] = 1;
-      if (!cb) obj_used[b] = 1;
-    }
-    for (int64_t g = 0; g < h->n_mg; ++g) {   // map group priors: the whole residual block counts as soon as one member varies; every such member is a variable
-      if (!h->h_mg_active[g]) continue;
-      bool any = false;
-      for (int64_t k = h->h_mg_ptr[g]; k < h->h_mg_ptr[g + 1]; ++k) if (!h->h_object_const[h->h_mg_obj[k]]) { obj_used[h->h_mg_obj[k]] = 1; any = true; }
-      if (any) nres += h->od * (h->h_mg_ptr[g + 1] - h->h_mg_ptr[g]);
-    }
-    if (!h->h_is_shared.empty()) for (int64_t o = 0; o < O; ++o) if (h->h_is_shared[o]) obj_used[o] = 1;   // shared objects exist on every rank
+    nres += reduce_small_families(h, pose_used.data(), obj_used.data());   // every other family, and the shared objects
     pose_vid.assign((size_t)P, -1); obj_vid.assign((size_t)O, -1);
     point_var.assign((size_t)L, 0);
     h->nPv = h->nOv = h->nLv = 0;
@@ -1033,7 +998,8 @@ struct PlanBuilder {
     h->dirty = false; h->mask_dirty = false; h->pc_valid = false; h->tiles_cleared = false;
     h->plan_serial++; h->cov_valid = false;
     h->plan_pose_vid = pose_vid; h->plan_obj_vid = obj_vid; h->plan_point_var = point_var; h->plan_is_pad = h->h_is_pad;
-    h->plan_rp_active = h->h_rp_active; h->plan_bb_active = h->h_bb_active; h->plan_sp_active = h->h_sp_active; h->plan_lt_active = h->h_lt_active; h->plan_rl_active = h->h_rl_active; h->plan_mp_active = h->h_mp_active; h->plan_mg_active = h->h_mg_active;
+    const FamilyTable fams = families(h);
+    for (const FactorFamily& f : fams.f) *f.plan_active = *f.h_active;
     h->live_rows = h->m_canon;
   }
 };
@@ -1060,9 +1026,9 @@ bool prepare_masks(obvi_ba_handle* h) {
     for (size_t i = 0; i < now.size(); ++i) if (now[i] && !plan[i]) return false;
     return true;
   };
-  if (h->h_rp_active.size() != h->plan_rp_active.size() || !subset(h->h_bb_active, h->plan_bb_active) || !subset(h->h_sp_active, h->plan_sp_active) ||
-      !subset(h->h_lt_active, h->plan_lt_active) || !subset(h->h_rl_active, h->plan_rl_active) || !subset(h->h_mp_active, h->plan_mp_active) ||
-      !subset(h->h_mg_active, h->plan_mg_active)) return false;
+  const FamilyTable fams = families(h);
+  if (h->h_rp_active.size() != h->plan_rp_active.size()) return false;   // (the observations' own subset test: fused with their pass below)
+  for (int f = FAM_RP + 1; f < FAM_COUNT; ++f) if (!subset(*fams.f[f].h_active, *fams.f[f].plan_active)) return false;
   // (scratch kept between calls: a session runs this once per frame)
   std::vector<uint8_t>& pose_used = h->scr_pose_used; std::vector<uint8_t>& obj_used = h->scr_obj_used; std::vector<uint8_t>& point_used = h->scr_point_used;
   pose_used.assign(P, 0); obj_used.assign(O, 0); point_used.assign(L, 0);
@@ -1082,42 +1048,7 @@ bool prepare_masks(obvi_ba_handle* h) {
       if (!cl) point_used[l] = 1;
     }
   }
-  for (int64_t i = 0; i < h->n_bb; ++i) {
-    if (!h->h_bb_active[i]) continue;
-    const uint32_t o = h->h_bb_obj[i], p = h->h_bb_pose[i];
-    const bool co = h->h_object_const[o], cp = h->h_pose_const[p];
-    if (co && cp) continue;
-    nres += 4;
-    if (!co) obj_used[o] = 1;
-    if (!cp) pose_used[p] = 1;
-  }
-  for (int64_t i = 0; i < h->n_sp; ++i) if (h->h_sp_active[i] && !h->h_object_const[h->h_sp_obj[i]]) { nres += 3; obj_used[h->h_sp_obj[i]] = 1; }
-  for (int64_t i = 0; i < h->n_lt; ++i) if (h->h_lt_active[i] && !h->h_object_const[h->h_lt_obj[i]]) { nres += h->od; obj_used[h->h_lt_obj[i]] = 1; }
-  for (int64_t i = 0; i < h->n_rl; ++i) {
-    if (!h->h_rl_active[i]) continue;
-    const uint32_t a = h->h_rl_a[i], b = h->h_rl_b[i];
-    const bool ca = h->h_pose_const[a], cb = h->h_pose_const[b];
-    if (ca && cb) continue;
-    nres += 6;
-    if (!ca) pose_used[a] = 1;
-    if (!cb) pose_used[b] = 1;
-  }
-  for (int64_t i = 0; i < h->n_mp; ++i) {
-    if (!h->h_mp_active[i]) continue;
-    const uint32_t a = h->h_mp_a[i], b = h->h_mp_b[i];
-    const bool ca = h->h_object_const[a], cb = h->h_object_const[b];
-    if (ca && cb) continue;
-    nres += 2 * h->od;
-    if (!ca) obj_used[a] = 1;
-    if (!cb) obj_used[b] = 1;
-  }
-  for (int64_t g = 0; g < h->n_mg; ++g) {   // map group priors: the whole residual block counts as soon as one member varies; every such member is a variable
-    if (!h->h_mg_active[g]) continue;
-    bool any = false;
-    for (int64_t k = h->h_mg_ptr[g]; k < h->h_mg_ptr[g + 1]; ++k) if (!h->h_object_const[h->h_mg_obj[k]]) { obj_used[h->h_mg_obj[k]] = 1; any = true; }
-    if (any) nres += h->od * (h->h_mg_ptr[g + 1] - h->h_mg_ptr[g]);
-  }
-  if (!h->h_is_shared.empty()) for (int64_t o = 0; o < O; ++o) if (h->h_is_shared[o]) obj_used[o] = 1;
+  nres += reduce_small_families(h, pose_used.data(), obj_used.data());
   std::vector<int32_t>& pose_vid = h->scr_pose_vid; std::vector<int32_t>& obj_vid = h->scr_obj_vid;
   std::vector<uint8_t>& point_var = h->scr_point_var; std::vector<uint8_t>& is_pad = h->scr_is_pad;
   pose_vid.assign(P, -1); obj_vid.assign(O, -1); point_var.assign(L, 0); is_pad = h->plan_is_pad;

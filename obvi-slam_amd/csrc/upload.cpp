@@ -460,22 +460,17 @@ int obvi_ba_set_active_mask(obvi_ba_handle* h, int32_t type, const uint8_t* mask
   OBVI_API_BEGIN
   OBVI_HIP(hipSetDevice(h->device));
   hipStream_t s = h->stream;
-  switch (type) {
-    case OBVI_FACTOR_REPROJECTION: {
-      set_mask(h->h_rp_active, h->d_rp_active, mask, h->n_rp, s, h->h_rp_perm.data());
-      std::vector<uint8_t> q(h->n_rp);
-      for (int64_t k = 0; k < h->n_rp; ++k) q[k] = h->h_rp_active[h->h_rq_src[k]];
-      h->d_rq_active.upload(q, s);
-      finish_upload(h);
-      break;
-    }
-    case OBVI_FACTOR_BBOX: set_mask<uint32_t>(h->h_bb_active, h->d_bb_active, mask, h->n_bb, s, nullptr); break;
-    case OBVI_FACTOR_SHAPE_PRIOR: set_mask<uint32_t>(h->h_sp_active, h->d_sp_active, mask, h->n_sp, s, nullptr); break;
-    case OBVI_FACTOR_LTM_PRIOR: set_mask<uint32_t>(h->h_lt_active, h->d_lt_active, mask, h->n_lt, s, nullptr); break;
-    case OBVI_FACTOR_REL_POSE: set_mask<uint32_t>(h->h_rl_active, h->d_rl_active, mask, h->n_rl, s, nullptr); break;
-    case OBVI_FACTOR_MAP_PAIR_PRIOR: set_mask<uint32_t>(h->h_mp_active, h->d_mp_active, mask, h->n_mp, s, nullptr); break;
-    case OBVI_FACTOR_MAP_GROUP_PRIOR: set_mask<uint32_t>(h->h_mg_active, h->d_mg_active, mask, h->n_mg, s, nullptr); break;
-    default: return fail(h, OBVI_ERR_INVALID_ARGUMENT, "set_active_mask: unknown factor type");
+  const FamilyTable fams = families(h);
+  const FactorFamily* f = fams.find(type);
+  if (!f) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "set_active_mask: unknown factor type");
+  if (type == OBVI_FACTOR_REPROJECTION) {   // the caller's order -> the sorted one, and the by-pose copy
+    set_mask(h->h_rp_active, h->d_rp_active, mask, h->n_rp, s, h->h_rp_perm.data());
+    std::vector<uint8_t> q(h->n_rp);
+    for (int64_t k = 0; k < h->n_rp; ++k) q[k] = h->h_rp_active[h->h_rq_src[k]];
+    h->d_rq_active.upload(q, s);
+    finish_upload(h);
+  } else {
+    set_mask<uint32_t>(*f->h_active, *f->d_active, mask, f->n, s, nullptr);
   }
   finish_upload(h);
   h->mask_dirty = true;   // prepare() keeps the symbolic plan if the new masks select a subset of what it was built for
@@ -485,12 +480,10 @@ int obvi_ba_set_active_mask(obvi_ba_handle* h, int32_t type, const uint8_t* mask
 
 int64_t obvi_ba_num_factors(const obvi_ba_handle* h, int32_t type) {
   if (!h) return -1;
-  switch (type) {
-    case OBVI_FACTOR_REPROJECTION: return h->n_rp; case OBVI_FACTOR_BBOX: return h->n_bb; case OBVI_FACTOR_SHAPE_PRIOR: return h->n_sp;
-    case OBVI_FACTOR_LTM_PRIOR: return h->n_lt; case OBVI_FACTOR_REL_POSE: return h->n_rl;
-    case OBVI_FACTOR_MAP_PAIR_PRIOR: return h->n_mp; case OBVI_FACTOR_MAP_GROUP_PRIOR: return h->n_mg; default: return -1;
-  }
+  const FamilyTable fams = families(h);
+  const FactorFamily* f = fams.find(type);
+  return f ? f->n : -1;
 }
-int64_t obvi_ba_num_residuals(const obvi_ba_handle* h) { return h ? 2 * h->n_rp + 4 * h->n_bb + 3 * h->n_sp + h->od * h->n_lt + 6 * h->n_rl + 2 * h->od * h->n_mp + h->mg_rows : -1; }
+int64_t obvi_ba_num_residuals(const obvi_ba_handle* h) { return h ? families(h).layout().row[FAM_COUNT] : -1; }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 """Ragged observation structures through the HIP path, checked against the oracle (reduced system + one LM step):
 tracks longer than a wavefront, tracks with gaps, loop closures (pairs far outside the Schur strip), three observations of a
 point from one pose, points and poses without observations."""
+import ctypes as C
 import os
 
 import numpy as np
@@ -9,6 +10,7 @@ import pytest
 import helpers
 import obvi_ba
 import synth
+from test_gpu_map_pair_priors import product, spd
 
 pytestmark = pytest.mark.gpu
 
@@ -490,3 +492,95 @@ def test_update_state_and_prepare_refuse_what_they_cannot_do():
     with pytest.raises(obvi_ba.ObviError):
         g.restore()                                                                  # the snapshot was dropped with the values it belonged to
     assert np.array_equal(g.get_points(), prob["points"] + 1.0) and np.array_equal(g.get_poses(), prob["poses"])
+
+
+# factor type -> factors of the problem below, in the order obvi_ba_evaluate lays the families out
+SEVEN_FAMILIES = {obvi_ba.FACTOR_REPROJECTION: 37, obvi_ba.FACTOR_BBOX: 5, obvi_ba.FACTOR_SHAPE_PRIOR: 3, obvi_ba.FACTOR_LTM_PRIOR: 2, obvi_ba.FACTOR_REL_POSE: 5,
+                  obvi_ba.FACTOR_MAP_PAIR_PRIOR: 2, obvi_ba.FACTOR_MAP_GROUP_PRIOR: 2}
+SEVEN_GROUPS = ([0, 2, 4], [5])
+
+
+def _seven_families(od):
+    """6 poses, 40 features, 6 objects and every factor family at once, none of the counts a multiple of 4 or 64: 37 observations, 5 boxes, 3 shape priors,
+    2 LTM priors, 5 relative poses, 2 map pair priors, map group priors of 3 and 1 members (no pair inside a group); a different Huber width per family."""
+    prob = synth.make_problem(P=6, L=40, O=6, seed=7, object_classes=("bench",), bbox_noise=5.0, min_obj_obs=3, outlier_frac=0.0)
+    rng = np.random.default_rng(31)
+    keep = np.sort(rng.choice(len(prob["rp_pose"]), 37, replace=False))
+    for k in ("rp_pose", "rp_point", "rp_cam", "rp_pixel", "rp_is_outlier"):
+        prob[k] = prob[k][keep]
+    keep = np.sort(rng.choice(len(prob["bb_obj"]), 5, replace=False))
+    for k in ("bb_obj", "bb_pose", "bb_cam", "bb_corners", "bb_cov"):
+        prob[k] = prob[k][keep]
+    for k in ("sp_obj", "sp_mean", "sp_cov"):
+        prob[k] = prob[k][[1, 3, 4]]
+    prob.update(lt_obj=np.array([5, 2], np.uint32), lt_mean=prob["objects"][[5, 2]] + rng.normal(scale=0.05, size=(2, 7)),
+                lt_cov=np.stack([spd(rng, 7), spd(rng, 7)]).reshape(2, 49))
+    prob.update(rp_huber=1.25, bb_huber=0.5, sp_huber=10.0, lt_huber=3.0, rl_huber=0.75)
+    if od == 9:
+        prob = synth.nine_dof(prob, tilt=0.3, seed=2)
+    obj = prob["objects"]
+    a, b = np.array([0, 2], np.uint32), np.array([1, 3], np.uint32)
+    pairs = dict(a=a, b=b, mean_a=obj[a] - rng.normal(scale=0.1, size=(2, od)), mean_b=obj[b] - rng.normal(scale=0.1, size=(2, od)),
+                 cov=np.stack([spd(rng, 2 * od), spd(rng, 2 * od)]), huber=2.0)
+    groups = dict(groups=[list(g) for g in SEVEN_GROUPS], means=[obj[list(g)] - rng.normal(scale=0.1, size=(len(g), od)) for g in SEVEN_GROUPS],
+                  covs=[spd(rng, od * len(g)) for g in SEVEN_GROUPS], huber=1.5)
+    ba = product(prob)
+    ba.set_map_pair_priors(pairs["a"], pairs["b"], pairs["mean_a"], pairs["mean_b"], pairs["cov"], None, pairs["huber"])
+    ba.set_map_group_priors(groups["groups"], groups["means"], groups["covs"], groups["huber"])
+    return ba
+
+
+@pytest.mark.parametrize("od", [7, 9])
+def test_seven_factor_families_in_one_evaluate_layout(od):
+    """Every factor family on one handle: counts, the evaluate layout (norms and residual rows family after family: reprojection, boxes, shape priors, LTM
+    priors, relative poses, map pair priors, map group priors), outlier selection per family on its own segment of the norms, and masks that take out one
+    factor and nothing else.  The un-robustified residuals of a family are also what obvi_ba_debug_linearize computes for it in another kernel: the same
+    fp64 formula, and a block norm sums at most 27 squares here, so both comparisons hold to 1e-12."""
+    ba = _seven_families(od)
+    types = list(SEVEN_FAMILIES)
+    n = np.array([SEVEN_FAMILIES[t] for t in types])
+    members = [len(g) for g in SEVEN_GROUPS]
+    rows_of = {0: [2] * 37, 2: [4] * 5, 3: [3] * 3, 4: [od] * 2, 5: [6] * 5, 9: [2 * od] * 2, 10: [od * k for k in members]}   # residual rows of every factor
+    for t in types:
+        assert ba._fn("ba_num_factors")(ba._h, C.c_int32(t)) == ba.num_factors(t) == SEVEN_FAMILIES[t] == len(rows_of[t])
+    assert ba._fn("ba_num_factors")(ba._h, C.c_int32(7)) == -1
+    assert ba._fn("ba_num_residuals")(ba._h) == ba.num_residuals() == sum(sum(rows_of[t]) for t in types)
+    slot0 = np.concatenate([[0], np.cumsum(n)])
+    row0 = np.concatenate([[0], np.cumsum([sum(rows_of[t]) for t in types])])
+    cost, res, sq = ba.evaluate(False)
+    assert len(res) == row0[-1] and len(sq) == slot0[-1] and np.all(sq > 0.0)
+    for f, t in enumerate(types):
+        seg, q = res[row0[f]:row0[f + 1]], sq[slot0[f]:slot0[f + 1]]
+        ends = np.concatenate([[0], np.cumsum(rows_of[t])])
+        sums = np.array([(seg[ends[i]:ends[i + 1]] ** 2).sum() for i in range(n[f])])
+        r = ba.debug_linearize(t)[0]
+        r = np.concatenate([np.ravel(x) for x in r]) if t == obvi_ba.FACTOR_MAP_GROUP_PRIOR else r.ravel()
+        print("od %d type %2d: norms %.2e  debug_linearize %.2e" % (od, t, np.abs(q / sums - 1.0).max(), helpers.rel_err(seg, r)))
+        assert np.all(np.abs(q - sums) <= 1e-12 * sums) and r.shape == seg.shape and helpers.rel_err(seg, r) <= 1e-12
+    assert abs(cost - 0.5 * sq.sum()) <= 1e-12 * cost
+    # selection: the family's own segment of the norms and its own mask, exactly its length written
+    for f, t in enumerate(types):
+        want, want_n = helpers.map_rule(sq[slot0[f]:slot0[f + 1]], np.ones(n[f]), 0.5)
+        mask, n_out = ba.select_outliers(t, 0.5)
+        assert len(mask) == n[f] and n_out == want_n == n[f] // 2 and np.array_equal(mask, want), (t, mask, want)
+        buf, nex = np.full(n[f] + 8, 7, np.uint8), C.c_int64(-1)
+        ba._check(ba._fn("ba_select_outliers")(ba._h, C.c_int32(t), C.c_double(0.5), buf.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(nex)), "select_outliers")
+        assert np.array_equal(buf[:n[f]], want) and np.all(buf[n[f]:] == 7) and nex.value == want_n
+    with pytest.raises(obvi_ba.ObviError, match="status -1 select_outliers: unknown factor type"):
+        ba._check(ba._fn("ba_select_outliers")(ba._h, C.c_int32(7), C.c_double(0.5), buf.ctypes.data_as(C.POINTER(C.c_uint8)), None), "select_outliers")
+    # masks: one factor of one family out, family after family
+    for f, t in enumerate(types):
+        k = n[f] // 2
+        mask = np.ones(n[f], np.uint8); mask[k] = 0
+        ba.set_active_mask(t, mask)
+        _, res1, sq1 = ba.evaluate(False)
+        ends = row0[f] + np.concatenate([[0], np.cumsum(rows_of[t])])
+        gone_rows = np.zeros(len(res), bool); gone_rows[ends[k]:ends[k + 1]] = True
+        gone = np.zeros(len(sq), bool); gone[slot0[f] + k] = True
+        assert np.all(res1[gone_rows] == 0.0) and np.all(sq1[gone] == 0.0), t
+        assert np.array_equal(res1[~gone_rows], res[~gone_rows]) and np.array_equal(sq1[~gone], sq[~gone]), t
+        ba.set_active_mask(t, None)
+    _, res2, sq2 = ba.evaluate(False)
+    assert np.array_equal(res2, res) and np.array_equal(sq2, sq)
+    with pytest.raises(obvi_ba.ObviError, match="status -1 set_active_mask: unknown factor type"):
+        ba.set_active_mask(7, None)
