@@ -613,6 +613,7 @@ struct PlanBuilder {
     for (const WgRange& g : wgs) { wg_f0.push_back(g.chunk * SR); wg_group.push_back(g.group); }
     h->schur_twins = any_twin ? 1 : 0;
     h->nchunks = (int64_t)wg_f0.size();
+    h->nbatches = (int64_t)bslot.size() - 1;
     h->npairs_window = n_window_pairs;
 
     if (stage_times)
