@@ -189,6 +189,24 @@ struct MapGroupDev {
   double* partial;   // [n_slabs] the slabs' sum d_i y_i (or sum r_i^2: k_map_group_eval)
 };
 
+// Group priors cut from a device-resident map (include/obvi_map_resident.h; map_kernels.hip).  Group g of a call: N rows in nt = ceil(N / 64) tile rows; its
+// tile workspaces (A -> L and Wt: nt x nt tiles each) start at tile tile0, the inverses of its diagonal tiles at tile diag0; members [member0, member0 + N / od)
+// of map_idx; Lambda / Csym (N rows of ld doubles) at lam_off, W (N x N) at w_off -- the offsets of MapGroupDev.
+constexpr int kMapGroupMaxRows = 2048;   // OBVI_MAP_GROUP_MAX_ROWS
+constexpr int kMapPowerSteps = 40;       // power steps of the condition estimate, on C and on Lambda
+enum MapStatus { MS_BAD = 0, MS_PIV_MIN, MS_PIV_MAX, MS_EV_C, MS_EV_LAMBDA, kMapStatusDoubles = 8 };   // one record per group, read back once per call
+struct MapCutGroup { int32_t N, nt, ld, pad; int64_t tile0, diag0, member0, lam_off, w_off; };
+struct MapCutDev {
+  int64_t n; int32_t od; int64_t rows;   // groups of the call; rows of all of them
+  const MapCutGroup* groups; const uint32_t* map_idx;
+  double* A; double* Li; double* Wt; double* Csym;   // workspaces
+  double* mean; double* W; double* Lambda;           // the outputs: the layout of MapGroupDev
+  double* x; double* partial; double* status;        // power iterates [2][2][rows], Rayleigh parts [n][2][kMapGroupMaxRows / 16], status [n][kMapStatusDoubles]
+};
+// gather, Cholesky by tile column (three launches per column of the largest group), W = L^-1, Lambda = W^T W, kMapPowerSteps power steps, the status records.
+// W and the padding of Lambda must have been zeroed on the stream.  x0: kMapGroupMaxRows doubles, the fixed start of the power iterations.
+void launch_map_cut(hipStream_t s, const MapCutDev& m, int nt_max, const double* map_mean, const double* map_cov, int64_t ldc, const double* x0);
+
 struct ReducedDev {         // accumulators of the reduced system
   double* Hdiag;            // pose v: 36 doubles at 36 v; object w: od^2 doubles at 36 nPv + od^2 w (row-major, lower part used)
   double* g;                // [6 nPv + od nOv] gradient J^T r (compact index: pose v at 6v, object w at 6 nPv + od w)

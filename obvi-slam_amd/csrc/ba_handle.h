@@ -175,6 +175,13 @@ struct obvi_ba_handle {
   DevBuf<int64_t> d_mg_ptr, d_mg_lam_off, d_mg_w_off; DevBuf<uint32_t> d_mg_obj; DevBuf<uint8_t> d_mg_active;
   DevBuf<double> d_mg_mean, d_mg_Lambda, d_mg_W, d_mg_y, d_mg_partial;
   DevBuf<int32_t> d_mg_slab_ptr, d_mg_slab_grp, d_mg_tile_ptr, d_mg_tile_grp, d_mg_tile_ij;   // work lists of the group kernels (ba_device.h, MapGroupDev)
+  // obvi_map_set_group_priors_from_map (map_resident.cpp): the buffers a call builds its groups in -- swapped with the d_mg_* ones on success, so that a refused
+  // call leaves the handle's groups as they were -- and the scratch of map_kernels.hip (MapCutDev, ba_device.h)
+  DevBuf<int64_t> d_mgn_ptr, d_mgn_lam_off, d_mgn_w_off; DevBuf<uint32_t> d_mgn_obj; DevBuf<uint8_t> d_mgn_active;
+  DevBuf<double> d_mgn_mean, d_mgn_Lambda, d_mgn_W;
+  DevBuf<int32_t> d_mgn_slab_ptr, d_mgn_slab_grp, d_mgn_tile_ptr, d_mgn_tile_grp, d_mgn_tile_ij;
+  DevBuf<MapCutGroup> d_mc_groups; DevBuf<uint32_t> d_mc_map_idx;
+  DevBuf<double> d_mc_A, d_mc_Li, d_mc_Wt, d_mc_Csym, d_mc_x, d_mc_partial, d_mc_status;
   DevBuf<double> d_bb_blk;                                    // per-factor blocks of the bounding-box factors (k_bbox_gather)
   DevBuf<double> d_sm_blk; DevBuf<uint32_t> d_smt_ptr, d_smt_idx;   // deterministic mode: the same for the priors and relative-pose factors (k_small_gather)
   int32_t bb_pairs_unique = 1;

@@ -1,0 +1,345 @@
+// map_kernels.hip -- group priors cut from a device-resident map (include/obvi_map_resident.h): gather of the groups' covariance sub-blocks, blocked right-looking
+// Cholesky by tile column, W = L^-1 by tile columns, Lambda = W^T W, and the two power iterations of the condition estimate.  Every group of a call shares every
+// launch (grid over work item x group); launch boundaries are the only synchronisation between workgroups; no floating-point atomics: every sum has a fixed order.
+// Workspace per group (MapCutGroup): nt x nt tiles of 64 x 64 doubles (tile-major, chol_tile.h), the ragged last tile padded with the identity --
+//   A  : the symmetrised sub-block, lower triangle of tiles; overwritten by L
+//   Li : nt tiles, the inverses of the diagonal tiles of L
+//   Wt : tile (i, k), k <= i, holds (W_ik)^T -- the operand order tile_abt_mfma (C += A B^T) wants in stages 3 and 4
+// and Csym, the sub-block again as N rows of ld doubles (the layout of Lambda), for the power steps on C.
+#include "chol_tile.h"
+
+namespace obvi {
+namespace {
+
+__device__ __forceinline__ double wave_sum(double v) {   // butterfly: every lane ends with the same bits
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+// accumulators of tile_abt_mfma -> a row-major tile in LDS (leading dimension LDM), scaled
+__device__ __forceinline__ void acc_to_lds(double* dst, const f64x4 acc[4], double scale) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) dst[(16 * rt + (lane >> 4) + 4 * r) * LDM + 16 * wv + (lane & 15)] = scale * acc[rt][r];
+}
+__device__ __forceinline__ void acc_to_tile(double* tile, const f64x4 acc[4]) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) tile[(16 * rt + (lane >> 4) + 4 * r) * T + 16 * wv + (lane & 15)] = acc[rt][r];
+}
+
+// ---- stage 1: gather ---------------------------------------------------------------------------------------------------------------------
+// workgroup (ti, tj <= ti, group): A_ij = (C[rows i][rows j] + C[rows j][rows i]^T) / 2.  Both blocks of the map are read along their rows and meet in LDS.
+__global__ void __launch_bounds__(kThreads) k_map_gather(MapCutDev m, const double* __restrict__ map_mean, const double* __restrict__ map_cov, int64_t ldc) {
+  __shared__ double P[T * LDM];
+  __shared__ double Q[T * LDM];
+  __shared__ int32_t rows_i[T], rows_j[T];
+  const int ti = blockIdx.x, tj = blockIdx.y;
+  if (tj > ti) return;
+  for (int64_t g = blockIdx.z; g < m.n; g += gridDim.z) {
+    const MapCutGroup G = m.groups[g];
+    if (ti >= G.nt) continue;
+    const int od = m.od, tid = threadIdx.x;
+    __syncthreads();
+    if (tid < 2 * T) {   // map row of every row of the two tile rows; -1: padding
+      const int gi = T * (tid < T ? ti : tj) + (tid & (T - 1));
+      int32_t mr = -1;
+      if (gi < G.N) mr = (int32_t)m.map_idx[G.member0 + gi / od] * od + gi % od;
+      (tid < T ? rows_i : rows_j)[tid & (T - 1)] = mr;
+    }
+    __syncthreads();
+    for (int e = tid; e < T * T; e += kThreads) {
+      const int r = e >> 6, c = e & 63;
+      const int32_t ai = rows_i[r], aj = rows_j[c], bj = rows_j[r], bi = rows_i[c];
+      P[r * LDM + c] = (ai >= 0 && aj >= 0) ? map_cov[(int64_t)ai * ldc + aj] : 0.0;   // C[row i_r][col j_c]
+      Q[r * LDM + c] = (bj >= 0 && bi >= 0) ? map_cov[(int64_t)bj * ldc + bi] : 0.0;   // C[row j_r][col i_c]
+    }
+    __syncthreads();
+    double* tile = tile_ptr(m.A + G.tile0 * (T * T), G.nt, ti, tj);
+    double* Cs = m.Csym + G.lam_off;
+    for (int e = tid; e < T * T; e += kThreads) {
+      const int r = e >> 6, c = e & 63, gi = T * ti + r, gj = T * tj + c;
+      const bool in = gi < G.N && gj < G.N;
+      const double v = in ? 0.5 * (P[r * LDM + c] + Q[c * LDM + r]) : (gi == gj ? 1.0 : 0.0);
+      tile[e] = v;
+      if (in) Cs[(int64_t)gi * G.ld + gj] = v;
+    }
+    if (ti != tj) {   // the upper triangle of Csym, written along its rows
+      for (int e = tid; e < T * T; e += kThreads) {
+        const int r = e >> 6, c = e & 63, gj = T * tj + r, gi = T * ti + c;
+        if (gi < G.N && gj < G.N) Cs[(int64_t)gj * G.ld + gi] = 0.5 * (P[c * LDM + r] + Q[r * LDM + c]);
+      }
+    }
+    if (tj == 0 && tid < T && rows_i[tid] >= 0) m.mean[(int64_t)od * G.member0 + T * ti + tid] = map_mean[rows_i[tid]];
+  }
+}
+
+// ---- stage 2: Cholesky by tile column ------------------------------------------------------------------------------------------------------
+// One workgroup per group: factor the diagonal tile k (unblocked, right-looking, in LDS), form its inverse by forward substitution, record the pivots.
+// A pivot that is not positive and finite sets the flag and is replaced by 1: a select, never a branch.  Padding rows (identity) stay out of the extremes.
+__global__ void __launch_bounds__(kThreads) k_map_potrf(MapCutDev m, int k) {
+  __shared__ double Ls[T * LDM];
+  __shared__ double X[T * LDM];
+  for (int64_t g = blockIdx.x; g < m.n; g += gridDim.x) {
+    const MapCutGroup G = m.groups[g];
+    if (k >= G.nt) continue;
+    const int tid = threadIdx.x;
+    double* tile = tile_ptr(m.A + G.tile0 * (T * T), G.nt, k, k);
+    __syncthreads();
+    stage_tile(Ls, tile);
+    double* st = m.status + kMapStatusDoubles * g;
+    double bad = 0.0, pmin = INFINITY, pmax = 0.0;
+    if (k > 0) { bad = st[MS_BAD]; pmin = st[MS_PIV_MIN]; pmax = st[MS_PIV_MAX]; }
+    __syncthreads();
+    const int row = tid >> 2, part = tid & 3;
+    for (int j = 0; j < T; ++j) {
+      const double d = Ls[j * LDM + j];
+      const bool ok = d > 0.0 && isfinite(d);
+      const double dj = sqrt(ok ? d : 1.0);
+      if (T * k + j < G.N) { bad = ok ? bad : 1.0; pmin = fmin(pmin, dj); pmax = fmax(pmax, dj); }
+      if (tid > j && tid < T) Ls[tid * LDM + j] = Ls[tid * LDM + j] / dj;
+      __syncthreads();
+      if (row > j) {   // row `row`, columns j < c <= row, c = part mod 4
+        const double l = Ls[row * LDM + j];
+        for (int c = j + 1 + ((part - (j + 1)) & 3); c <= row; c += 4) Ls[row * LDM + c] -= l * Ls[c * LDM + j];
+      }
+      __syncthreads();
+    }
+    if (tid < T) { const double d = Ls[tid * LDM + tid]; Ls[tid * LDM + tid] = sqrt((d > 0.0 && isfinite(d)) ? d : 1.0); }
+    __syncthreads();
+    // X = L^-1: column c = tid / 4, row after row; the four threads of a column split the dot product by j mod 4
+    const int c = tid >> 2;
+    for (int i = 0; i < T; ++i) {
+      double s = 0.0;
+      for (int j = (c & ~3) + part; j < i; j += 4) s += Ls[i * LDM + j] * X[j * LDM + c];
+      s += __shfl_xor(s, 1, 64);
+      s += __shfl_xor(s, 2, 64);
+      if (part == 0) X[i * LDM + c] = i < c ? 0.0 : ((i == c ? 1.0 : 0.0) - s) / Ls[i * LDM + i];
+      __syncthreads();
+    }
+    double* Li = m.Li + (G.diag0 + k) * (T * T);
+    for (int e = tid; e < T * T; e += kThreads) {
+      const int r = e >> 6, cc = e & 63;
+      tile[e] = cc <= r ? Ls[r * LDM + cc] : 0.0;
+      Li[e] = X[r * LDM + cc];
+    }
+    if (tid == 0) { st[MS_BAD] = bad; st[MS_PIV_MIN] = pmin; st[MS_PIV_MAX] = pmax; }
+  }
+}
+
+// tiles below the diagonal: A_ik <- A_ik L_kk^-T
+__global__ void __launch_bounds__(kThreads) k_map_trsm(MapCutDev m, int k) {
+  __shared__ double A[T * LDM];
+  __shared__ double B[T * LDM];
+  const int i = k + 1 + blockIdx.x;
+  for (int64_t g = blockIdx.y; g < m.n; g += gridDim.y) {
+    const MapCutGroup G = m.groups[g];
+    if (i >= G.nt) continue;
+    double* tile = tile_ptr(m.A + G.tile0 * (T * T), G.nt, i, k);
+    __syncthreads();
+    stage_tiles(A, tile, B, m.Li + (G.diag0 + k) * (T * T));
+    __syncthreads();
+    f64x4 acc[4] = {};
+    tile_abt_mfma(A, B, acc);
+    acc_to_tile(tile, acc);
+  }
+}
+
+// trailing update, lower triangle of tiles: A_ij -= L_ik L_jk^T
+__global__ void __launch_bounds__(kThreads) k_map_syrk(MapCutDev m, int k) {
+  __shared__ double A[T * LDM];
+  __shared__ double B[T * LDM];
+  const int i = k + 1 + blockIdx.x, j = k + 1 + blockIdx.y;
+  if (j > i) return;
+  for (int64_t g = blockIdx.z; g < m.n; g += gridDim.z) {
+    const MapCutGroup G = m.groups[g];
+    if (i >= G.nt) continue;
+    double* S = m.A + G.tile0 * (T * T);
+    __syncthreads();
+    if (i != j) stage_tiles(A, tile_ptr(S, G.nt, i, k), B, tile_ptr(S, G.nt, j, k));
+    else stage_tile(A, tile_ptr(S, G.nt, i, k));
+    __syncthreads();
+    f64x4 acc[4] = {};
+    tile_abt_mfma(A, i != j ? B : A, acc);
+    double* C = tile_ptr(S, G.nt, i, j);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    double v[4][4];
+#pragma unroll
+    for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) v[rt][r] = C[(16 * rt + (lane >> 4) + 4 * r) * T + 16 * wv + (lane & 15)];
+#pragma unroll
+    for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) C[(16 * rt + (lane >> 4) + 4 * r) * T + 16 * wv + (lane & 15)] = v[rt][r] - acc[rt][r];
+  }
+}
+
+// ---- stage 3: W = L^-1, one workgroup per tile column ----------------------------------------------------------------------------------------
+// Column k depends on no other column: Wt_kk = (L_kk^-1)^T, then for i > k:  Wt_ik = -(sum_{k <= j < i} Wt_jk L_ij^T) L_ii^-T.  The workgroup reads back the tiles of
+// its own column that it wrote (behind its own barrier); W goes out row-major N x N without the padding.
+__global__ void __launch_bounds__(kThreads) k_map_winv(MapCutDev m) {
+  __shared__ double A[T * LDM];
+  __shared__ double B[T * LDM];
+  const int k = blockIdx.x, tid = threadIdx.x;
+  for (int64_t g = blockIdx.y; g < m.n; g += gridDim.y) {
+    const MapCutGroup G = m.groups[g];
+    if (k >= G.nt) continue;
+    const double* L = m.A + G.tile0 * (T * T);
+    double* Wt = m.Wt + G.tile0 * (T * T);
+    const double* Li = m.Li + G.diag0 * (T * T);
+    double* W = m.W + G.w_off;
+    const int N = G.N;
+    __syncthreads();
+    stage_tile(A, Li + (int64_t)k * (T * T));
+    __syncthreads();
+    {
+      double* wt = tile_ptr(Wt, G.nt, k, k);
+      for (int e = tid; e < T * T; e += kThreads) {
+        const int r = e >> 6, c = e & 63, gi = T * k + r, gj = T * k + c;
+        wt[e] = A[c * LDM + r];
+        if (gi < N && gj < N) W[(int64_t)gi * N + gj] = A[r * LDM + c];
+      }
+    }
+    for (int i = k + 1; i < G.nt; ++i) {
+      f64x4 acc[4] = {};
+      for (int j = k; j < i; ++j) {
+        __syncthreads();
+        stage_tiles(A, tile_ptr(Wt, G.nt, j, k), B, tile_ptr(const_cast<double*>(L), G.nt, i, j));
+        __syncthreads();
+        tile_abt_mfma(A, B, acc);   // (sum_j L_ij W_jk)^T
+      }
+      __syncthreads();
+      {
+        TileRegs rb;
+        tile_fetch(rb, Li + (int64_t)i * (T * T));
+        acc_to_lds(A, acc, -1.0);
+        tile_put(B, rb);
+      }
+      __syncthreads();
+      f64x4 w[4] = {};
+      tile_abt_mfma(A, B, w);        // Wt_ik
+      acc_to_tile(tile_ptr(Wt, G.nt, i, k), w);
+      __syncthreads();
+      acc_to_lds(A, w, 1.0);
+      __syncthreads();
+      for (int e = tid; e < T * T; e += kThreads) {
+        const int r = e >> 6, c = e & 63, gi = T * i + r;
+        if (gi < N) W[(int64_t)gi * N + T * k + c] = A[c * LDM + r];
+      }
+    }
+  }
+}
+
+// ---- stage 4: Lambda = W^T W ---------------------------------------------------------------------------------------------------------------------
+// tile (i, j <= i): sum_{k >= i} W_ki^T W_kj = sum_k Wt_ki Wt_kj^T ... with Wt_ki the tile of W_ki^T.  Both triangles, rows of ld doubles (the padding was zeroed).
+__global__ void __launch_bounds__(kThreads) k_map_lambda(MapCutDev m) {
+  __shared__ double A[T * LDM];
+  __shared__ double B[T * LDM];
+  const int i = blockIdx.x, j = blockIdx.y, tid = threadIdx.x;
+  if (j > i) return;
+  for (int64_t g = blockIdx.z; g < m.n; g += gridDim.z) {
+    const MapCutGroup G = m.groups[g];
+    if (i >= G.nt) continue;
+    double* Wt = m.Wt + G.tile0 * (T * T);
+    f64x4 acc[4] = {};
+    for (int k = i; k < G.nt; ++k) {
+      __syncthreads();
+      if (i != j) stage_tiles(A, tile_ptr(Wt, G.nt, k, i), B, tile_ptr(Wt, G.nt, k, j));
+      else stage_tile(A, tile_ptr(Wt, G.nt, k, i));
+      __syncthreads();
+      tile_abt_mfma(A, i != j ? B : A, acc);
+    }
+    __syncthreads();
+    acc_to_lds(A, acc, 1.0);
+    __syncthreads();
+    double* Lam = m.Lambda + G.lam_off;
+    const int N = G.N;
+    for (int e = tid; e < T * T; e += kThreads) {
+      const int r = e >> 6, c = e & 63;
+      const int gi = T * i + r, gj = T * j + c;
+      if (gi < N && gj < N) Lam[(int64_t)gi * G.ld + gj] = (i == j && c > r) ? A[c * LDM + r] : A[r * LDM + c];   // a diagonal tile: its lower triangle, mirrored
+      const int hj = T * j + r, hi = T * i + c;
+      if (i != j && hi < N && hj < N) Lam[(int64_t)hj * G.ld + hi] = A[c * LDM + r];
+    }
+  }
+}
+
+// ---- stage 5: power steps ------------------------------------------------------------------------------------------------------------------------
+// One step of x <- M x / |x| on Csym (which = 0) and on Lambda (which = 1): workgroup (16 rows, group, which) normalises x itself (every workgroup the same sum in
+// the same order), writes its rows of M x and its part of the Rayleigh quotient x^T M x / |x|^2.
+constexpr int kPowRows = 16;
+__global__ void __launch_bounds__(kThreads) k_map_power(MapCutDev m, const double* __restrict__ x0, int step) {
+  __shared__ double xs[kMapGroupMaxRows];
+  __shared__ double red[kThreads];
+  __shared__ double part[kPowRows];
+  const int which = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  for (int64_t g = blockIdx.y; g < m.n; g += gridDim.y) {
+    const MapCutGroup G = m.groups[g];
+    const int N = G.N, r0 = kPowRows * blockIdx.x;
+    if (r0 >= N) continue;
+    const double* M = (which ? m.Lambda : m.Csym) + G.lam_off;
+    const int64_t xoff = (int64_t)which * m.rows + (int64_t)m.od * G.member0;
+    const double* xin = step == 0 ? x0 : m.x + (int64_t)(step & 1) * 2 * m.rows + xoff;
+    double* xout = m.x + (int64_t)((step + 1) & 1) * 2 * m.rows + xoff;
+    __syncthreads();
+    double s = 0.0;
+    for (int c = tid; c < N; c += kThreads) { const double v = xin[c]; xs[c] = v; s += v * v; }
+    red[tid] = s;
+    __syncthreads();
+    for (int w = kThreads / 2; w >= 1; w >>= 1) { if (tid < w) red[tid] += red[tid + w]; __syncthreads(); }
+    const double nx = sqrt(red[0]);
+    for (int c = tid; c < N; c += kThreads) xs[c] = xs[c] / nx;
+    __syncthreads();
+#pragma unroll
+    for (int rr = 0; rr < kPowRows / 4; ++rr) {
+      const int row = r0 + 4 * wv + rr;
+      double y = 0.0;
+      if (row < N) for (int c = lane; c < N; c += 64) y += M[(int64_t)row * G.ld + c] * xs[c];
+      y = wave_sum(y);
+      if (lane == 0) { part[4 * wv + rr] = row < N ? xs[row] * y : 0.0; if (row < N) xout[row] = y; }
+    }
+    __syncthreads();
+    if (tid == 0) {
+      double e = 0.0;
+      for (int q = 0; q < kPowRows; ++q) e += part[q];
+      m.partial[((int64_t)g * 2 + which) * (kMapGroupMaxRows / kPowRows) + blockIdx.x] = e;
+    }
+  }
+}
+// the last step's Rayleigh quotients into the status records
+__global__ void __launch_bounds__(64) k_map_power_finish(MapCutDev m) {
+  const int64_t g = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (g >= m.n) return;
+  const int nb = (m.groups[g].N + kPowRows - 1) / kPowRows;
+  for (int which = 0; which < 2; ++which) {
+    double e = 0.0;
+    for (int b = 0; b < nb; ++b) e += m.partial[(g * 2 + which) * (kMapGroupMaxRows / kPowRows) + b];
+    m.status[kMapStatusDoubles * g + (which ? MS_EV_LAMBDA : MS_EV_C)] = e;
+  }
+}
+
+}  // namespace
+
+void launch_map_cut(hipStream_t s, const MapCutDev& m, int nt_max, const double* map_mean, const double* map_cov, int64_t ldc, const double* x0) {
+  if (m.n <= 0) return;
+  const unsigned gz = (unsigned)std::min<int64_t>(m.n, 65535);
+  hipLaunchKernelGGL(k_map_gather, dim3(nt_max, nt_max, gz), dim3(kThreads), 0, s, m, map_mean, map_cov, ldc);
+  for (int k = 0; k < nt_max; ++k) {
+    hipLaunchKernelGGL(k_map_potrf, dim3(gz), dim3(kThreads), 0, s, m, k);
+    if (k + 1 == nt_max) break;
+    hipLaunchKernelGGL(k_map_trsm, dim3(nt_max - k - 1, gz), dim3(kThreads), 0, s, m, k);
+    hipLaunchKernelGGL(k_map_syrk, dim3(nt_max - k - 1, nt_max - k - 1, gz), dim3(kThreads), 0, s, m, k);
+  }
+  hipLaunchKernelGGL(k_map_winv, dim3(nt_max, gz), dim3(kThreads), 0, s, m);
+  hipLaunchKernelGGL(k_map_lambda, dim3(nt_max, nt_max, gz), dim3(kThreads), 0, s, m);
+  const int nb = (std::min(nt_max * T, kMapGroupMaxRows) + kPowRows - 1) / kPowRows;
+  for (int step = 0; step < kMapPowerSteps; ++step) hipLaunchKernelGGL(k_map_power, dim3(nb, gz, 2), dim3(kThreads), 0, s, m, x0, step);
+  hipLaunchKernelGGL(k_map_power_finish, dim3((unsigned)((m.n + 63) / 64)), dim3(64), 0, s, m);
+}
+
+}  // namespace obvi

@@ -104,6 +104,59 @@ def _ptr(a, ctype):
     return None if a is None else a.ctypes.data_as(C.POINTER(ctype))
 
 
+class Map:
+    """A long-term map on the device (include/obvi_map_resident.h): means [n][od] and the joint covariance [n od][n od] of its n objects, uploaded once and
+    immutable; any BundleAdjuster on the same device cuts its group priors from it (set_map_group_priors_from_map)."""
+
+    def __init__(self, mean, cov, device_id=0, object_block_size=7, library=None, prefix="obvi_"):
+        path = library or default_library_path()
+        if not os.path.exists(path):
+            raise ObviError("%s not found: build it with __graft_entry__.build() -- there is no CPU fallback" % path)
+        self._lib = C.CDLL(path)
+        self._pre = prefix
+        self._m = C.c_void_p()
+        try:
+            f = getattr(self._lib, prefix + "map_create")
+        except AttributeError:
+            raise ObviError("%smap_create: this library has no device-resident map (include/obvi_map_resident.h is served by libobvi_ba.so only)" % prefix)
+        f.restype = C.c_int
+        self.od = int(object_block_size) or 7
+        mu = _f64(mean, (-1, self.od))
+        cv = _f64(cov, (len(mu) * self.od, len(mu) * self.od))
+        rc = f(C.c_int32(device_id), C.c_int32(int(object_block_size)), C.c_int64(len(mu)), _ptr(mu, C.c_double), _ptr(cv, C.c_double), C.byref(self._m))
+        if rc != 0:
+            raise ObviError("%smap_create failed: status %d" % (prefix, rc))
+
+    @classmethod
+    def create(cls, mean, cov, **kw):
+        return cls(mean, cov, **kw)
+
+    @property
+    def n_objects(self):
+        f = getattr(self._lib, self._pre + "map_num_objects")
+        f.restype = C.c_int64
+        return int(f(self._m))
+
+    def close(self):
+        if self._m:
+            f = getattr(self._lib, self._pre + "map_destroy")
+            f.restype = None
+            f(self._m)
+            self._m = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class BundleAdjuster:
     """One handle == one GPU == one HIP stream (include/obvi_ba.h)."""
 
@@ -255,6 +308,25 @@ class BundleAdjuster:
             raise ObviError("map_set_group_priors: means / covs do not match the groups")
         self._check(f(self._h, C.c_int64(len(sizes)), _ptr(ptr, C.c_int64), _ptr(idx, C.c_uint32), _ptr(mu, C.c_double), _ptr(cv, C.c_double), C.c_double(huber)),
                     "map_set_group_priors")
+        self._n[FACTOR_MAP_GROUP_PRIOR] = len(sizes)
+        self._mg_sizes = sizes
+
+    def set_map_group_priors_from_map(self, map, groups, map_idx, huber=1.0):
+        """Group priors cut from a device-resident map (include/obvi_map_resident.h): groups = a list of object-index lists, map_idx = per group the members' map
+        objects; means and covariances are the map's, gathered and factored on the device.  Empty lists clear the factors."""
+        try:
+            f = getattr(self._lib, self._pre + "map_set_group_priors_from_map")
+        except AttributeError:
+            raise ObviError("%smap_set_group_priors_from_map: this library has no map group priors (include/obvi_map_resident.h is served by libobvi_ba.so only)" % self._pre)
+        f.restype = C.c_int
+        sizes = [len(g) for g in groups]
+        ptr = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        idx = np.ascontiguousarray(np.concatenate([np.asarray(g, dtype=np.uint32).ravel() for g in groups]) if groups else np.zeros(0), dtype=np.uint32)
+        mid = np.ascontiguousarray(np.concatenate([np.asarray(g, dtype=np.uint32).ravel() for g in map_idx]) if groups else np.zeros(0), dtype=np.uint32)
+        if len(mid) != len(idx) or [len(g) for g in map_idx] != sizes:
+            raise ObviError("map_set_group_priors_from_map: map_idx does not match the groups")
+        self._check(f(self._h, map._m, C.c_int64(len(sizes)), _ptr(ptr, C.c_int64), _ptr(idx, C.c_uint32), _ptr(mid, C.c_uint32), C.c_double(huber)),
+                    "map_set_group_priors_from_map")
         self._n[FACTOR_MAP_GROUP_PRIOR] = len(sizes)
         self._mg_sizes = sizes
 
