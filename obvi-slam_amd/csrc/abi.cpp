@@ -40,6 +40,7 @@ Knobs read_knobs() {
   set_i64("OBVI_SMALL_LANES_BELOW", k.small_lanes_below);
   if (const char* v = std::getenv("OBVI_BACKSUB_LANES")) { const int n = std::atoi(v); if (n == 1 || n == 2 || n == 4 || n == 8 || n == 16 || n == 32) k.backsub_lanes = n; }
   set_int("OBVI_DET_MIN_STRIDE", k.det_min_stride); k.det_min_stride = std::max(1, k.det_min_stride);
+  set_flag("OBVI_POSE_LIN_REUSE", k.pose_lin_reuse);
   set_flag("OBVI_FUSED_POTRF", k.fused_potrf);
   set_flag("OBVI_DETERMINISTIC", k.deterministic);
   k.debug_create = std::getenv("OBVI_DEBUG_CREATE") != nullptr;
@@ -164,7 +165,7 @@ int obvi_ba_reset(obvi_ba_handle* h) {
   OBVI_API_BEGIN
   h->h_is_shared.clear(); h->h_shared_ov.clear(); h->rank = 0; h->world = 1; h->tail_t0 = -1; h->tail_level0 = -1;
   h->allreduce = nullptr; h->allreduce_user = nullptr;
-  h->have_snapshot = false; h->use_extra = false; h->pc_valid = false; h->tiles_cleared = false;
+  h->have_snapshot = false; h->use_extra = false; h->pc_valid = false; h->lin_valid = false; h->tiles_cleared = false;
   h->iterations.clear();
   h->profiling = 0; h->ck_used = 0;
   for (auto& v : h->phase_ms) v = 0.0;

@@ -148,6 +148,10 @@ struct BlocksDev {          // parameter blocks + reduced-program bookkeeping
   int32_t deterministic;     // obvi_ba_options.deterministic: 0, or the stride of the per-workgroup partial sums behind the scalar block that replace the fp64 atomics
   int32_t od;                // parameters of an ellipsoid block: 7 (x y z yaw dx dy dz: the reference's build) or 9 (x y z ax ay az dx dy dz; obvi_ba_options.object_block_size)
 };
+// k_pose_pass runs one workgroup per pose (no slices, no atomics) above this many poses and on every deterministic handle: the form whose sums can be
+// staged per pose, and that the trial cost can produce at the candidate (launch_pose_pass, launch_cost)
+constexpr int64_t kPoseSliceBelow = 256;
+inline bool pose_pass_unsliced(const BlocksDev& b) { return b.deterministic != 0 || b.P > kPoseSliceBelow; }
 
 struct SmallFactorsDev {    // N <= ~3e4 each; arrays in caller order
   int32_t od;               // parameters of an ellipsoid block (BlocksDev.od)
@@ -239,8 +243,10 @@ void launch_pose_cache(hipStream_t s, int64_t P, const double* poses, PoseCache*
 void launch_point_pass(hipStream_t s, const BlocksDev& b, const ReprojDev& rp, const DevCam* cams, const PoseCache* pc, const double* points,
                        const ReducedDev& rd, const PointDev& pt, double radius, int first_iter, double* scal, const uint32_t* wave_obs, int64_t n_waves,
                        const uint32_t* long_points, int64_t n_long);
+// lin: NULL, or (unsliced pose pass only) 27 doubles per pose that take the sums instead of Hdiag / g; launch_pose_lin_add adds such a set
 void launch_pose_pass(hipStream_t s, const BlocksDev& b, const ReprojPoseDev& rq, const DevCam* cams, const PoseCache* pc,
-                      const double* points, const ReducedDev& rd);
+                      const double* points, const ReducedDev& rd, double* lin = nullptr);
+void launch_pose_lin_add(hipStream_t s, const BlocksDev& b, const double* lin, const ReducedDev& rd);
 void launch_small_factors(hipStream_t s, const BlocksDev& b, const SmallFactorsDev& sf, const DevCam* cams,
                           const double* poses, const double* objects, const ReducedDev& rd, double* scal, int64_t lanes_below /* Knobs::small_lanes_below */);
 void launch_reduced_diag(hipStream_t s, const BlocksDev& b, const double* poses, const double* objects,
@@ -281,7 +287,7 @@ void launch_backsub_apply(hipStream_t s, const BlocksDev& b, const ReprojDev& rp
 void launch_cost(hipStream_t s, const BlocksDev& b, const ReprojPoseDev& rq, const SmallFactorsDev& sf, const DevCam* cams,
                  const PoseCache* pc_cur, const double* poses_cur, const double* points_cur, const double* objects_cur,
                  const PoseCache* pc_cand, const double* poses_cand, const double* points_cand, const double* objects_cand,
-                 int mode, double* scal);
+                 int mode, double* scal, double* lin = nullptr /* mode 0, unsliced pose pass: the pose-side sums at the candidate, 27 per pose */);
 // problem->Evaluate: raw / robustified residuals of every factor in caller order, family after family as `lay` places them (the map group priors: launch_map_group_eval)
 void launch_evaluate(hipStream_t s, const BlocksDev& b, const ReprojDev& rp, const uint32_t* rp_perm, const SmallFactorsDev& sf,
                      const DevCam* cams, const PoseCache* pc, const double* poses, const double* points, const double* objects,

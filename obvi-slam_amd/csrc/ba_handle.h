@@ -38,8 +38,8 @@ namespace obvi_lib {
 
 inline double wall_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-enum Phase { PH_POSE_CACHE = 0, PH_POINT_PASS, PH_POSE_PASS, PH_SMALL, PH_MAP_QUAD, PH_MAP_SCATTER, PH_DIAG, PH_SCHUR, PH_SCHUR_BLOCKS, PH_CHOL, PH_BACKSUB, PH_APPLY, PH_COST, PH_COUNT };
-inline const char* const kPhaseNames[PH_COUNT] = {"pose_cache", "point_pass", "pose_pass", "small_factors", "map_group_quad", "map_group_scatter", "reduced_diag", "schur_window", "schur_blocks",
+enum Phase { PH_POSE_CACHE = 0, PH_POINT_PASS, PH_POSE_PASS, PH_POSE_LIN_ADD, PH_SMALL, PH_MAP_QUAD, PH_MAP_SCATTER, PH_DIAG, PH_SCHUR, PH_SCHUR_BLOCKS, PH_CHOL, PH_BACKSUB, PH_APPLY, PH_COST, PH_COUNT };
+inline const char* const kPhaseNames[PH_COUNT] = {"pose_cache", "point_pass", "pose_pass", "pose_lin_add", "small_factors", "map_group_quad", "map_group_scatter", "reduced_diag", "schur_window", "schur_blocks",
                                      "cholesky_solve", "point_backsub", "apply_step", "cost"};
 
 // The tuning knobs of a handle.  read_knobs() is the only reader of the environment: obvi_ba_create takes one
@@ -69,6 +69,7 @@ struct Knobs {
   int64_t small_lanes_below = 4096;     // OBVI_SMALL_LANES_BELOW: bounding-box factors below which the small factors take 16 lanes each
   int backsub_lanes = 0;                // OBVI_BACKSUB_LANES: lanes per feature of the back-substitution, 1, 2, 4, 8, 16 or 32 (0: by sightings per feature)
   int det_min_stride = 4096;            // OBVI_DET_MIN_STRIDE: deterministic mode, first size of the partial-sum slots (at least 1)
+  bool pose_lin_reuse = true;           // OBVI_POSE_LIN_REUSE: the trial cost stages the pose side of the next linearisation (0: a pose pass in every step)
   // obvi_ba_create
   bool fused_potrf = true;              // OBVI_FUSED_POTRF: 0 = the two-launch schedule of the tile Cholesky from the start
   bool deterministic = false;           // OBVI_DETERMINISTIC: the handle is deterministic whatever its options say
@@ -152,6 +153,12 @@ struct obvi_ba_handle {
   DevBuf<PoseCache> d_pc, d_pc_c;
   bool pc_valid = false;                 // d_pc belongs to the poses in d_pose (an accepted step hands the candidate's cache over)
   bool tiles_cleared = false;            // the tiles and step accumulators were already cleared behind the previous LM step
+  // Pose side of the reprojection linearisation, 27 sums per pose (k_pose_pass), staged: of the current point and of the candidate.  The trial cost
+  // fills the candidate's set on its walk over the same sightings (launch_cost), an accepted step swaps the two with d_pc / d_pc_c, and a step
+  // whose current set is valid adds it instead of running the pose pass (assemble_step).  Only where the pose pass is unsliced (lin_reuse()).
+  DevBuf<double> d_lin, d_lin_c;
+  bool lin_valid = false;                // d_lin belongs to the current point, masks and constness flags; cleared with pc_valid and at the start of every solve
+  bool lin_c_valid = false;              // d_lin_c was filled by the trial cost of the step just submitted
   DevBuf<int32_t> d_pose_vid, d_obj_vid;
   DevBuf<uint8_t> d_point_var;
   // ---- device: factors ----
@@ -279,6 +286,7 @@ struct obvi_ba_handle {
   hipEvent_t ev[PH_COUNT + 1] = {};       // start of each phase (+ end of the step) on the main stream
   hipEvent_t ev_end[PH_COUNT] = {};       // end of a phase that ran on the side stream
   bool phase_on_side[PH_COUNT] = {};
+  bool phase_recorded[PH_COUNT + 1] = {}; // the phase's start event was recorded in the step being submitted (the pose pass runs in the first step of a solve only)
   hipStream_t stream2 = nullptr;          // side stream: kernels that do not depend on the point pass / Schur complement run beside them
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int ck_used = 0;
@@ -665,6 +673,7 @@ inline StepClear step_clear(obvi_ba_handle* h, double fixed_cost) {
 inline void record(obvi_ba_handle* h, int idx, hipStream_t on = nullptr) {
   if (h->profiling < 1) return;
   OBVI_HIP(hipEventRecord(h->ev[idx], on ? on : h->stream));
+  h->phase_recorded[idx] = true;
   if (idx < PH_COUNT) h->phase_on_side[idx] = on != nullptr && on != h->stream;
 }
 inline void record_end(obvi_ba_handle* h, int idx, hipStream_t on) { if (h->profiling >= 1) OBVI_HIP(hipEventRecord(h->ev_end[idx], on)); }
@@ -682,8 +691,8 @@ inline bool exchanging(const obvi_ba_handle* h) { return h->allreduce != nullptr
 // parameter priors' diagonals are added (`use_extra`) for this step only -- also when a launch throws.
 struct QuietStep {
   obvi_ba_handle* h; const int profiling;
-  explicit QuietStep(obvi_ba_handle* hh, bool use_extra = false) : h(hh), profiling(hh->profiling) { h->profiling = 0; h->use_extra = use_extra; h->pc_valid = h->tiles_cleared = false; h->cov_valid = false; }
-  ~QuietStep() { h->profiling = profiling; h->use_extra = h->pc_valid = h->tiles_cleared = false; }
+  explicit QuietStep(obvi_ba_handle* hh, bool use_extra = false) : h(hh), profiling(hh->profiling) { h->profiling = 0; h->use_extra = use_extra; h->pc_valid = h->lin_valid = h->tiles_cleared = false; h->cov_valid = false; }
+  ~QuietStep() { h->profiling = profiling; h->use_extra = h->pc_valid = h->lin_valid = h->tiles_cleared = false; }
 };
 
 inline double scal_gmax(const obvi_ba_handle* h) { double v; std::memcpy(&v, &h->h_scal[SC_GMAX_BITS], sizeof(v)); return v; }
@@ -696,7 +705,7 @@ inline void copy_current(obvi_ba_handle* h, DevBuf<double>& dp, DevBuf<double>& 
 inline void restore_from(obvi_ba_handle* h, const DevBuf<double>& dp, const DevBuf<double>& dl, const DevBuf<double>& dobj) {
   hipStream_t s = h->stream;
   launch_copy3(s, h->d_pose.get(), dp.get(), 6 * h->P, h->d_point.get(), dl.get(), 3 * h->L, h->d_obj.get(), dobj.get(), h->od * h->O);
-  h->pc_valid = false;
+  h->pc_valid = false; h->lin_valid = false;
 }
 
 inline bool check_ready(obvi_ba_handle* h) {

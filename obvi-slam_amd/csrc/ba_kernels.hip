@@ -406,10 +406,19 @@ __global__ void __launch_bounds__(kBlock, kPointImageDoubles <= 1264 ? 4 : 3) k_
 // contiguous (CSR by pose copy of the observation arrays).  Each thread accumulates the 21 unique
 // entries of rho' Jp^T Jp and the 6 of rho' Jp^T r over its observations; one deterministic
 // wavefront/LDS reduction per pose, no atomics.
+// `lin` (unsliced only): the 27 sums are stored at lin[27 p ..] instead of added to Hdiag / g -- the handle's staged set, which
+// k_pose_lin_add adds and which k_cost<PIPE, true> fills at the candidate.
 // ---------------------------------------------------------------------------------------
+// entry k of a pose's 27 sums -> its place in Hdiag (k < 21: packed lower triangle of the 6x6 block) or g
+__device__ __forceinline__ double* pose_lin_target(const ReducedDev& rd, int32_t vid, int k) {
+  if (k >= 21) return &rd.g[6 * (int64_t)vid + (k - 21)];
+  int x = 0, base = 0;
+  while (base + x + 1 <= k) { base += x + 1; ++x; }
+  return &rd.Hdiag[36 * (int64_t)vid + 6 * x + (k - base)];
+}
 template <bool PIPE>
 __global__ void __launch_bounds__(kBlock) k_pose_pass(BlocksDev b, ReprojPoseDev rq, const DevCam* __restrict__ cams, const PoseCache* __restrict__ pc,
-                                                     const double* __restrict__ points, ReducedDev rd, int slices) {
+                                                     const double* __restrict__ points, ReducedDev rd, int slices, double* __restrict__ lin) {
   // slices > 1 (a sliding window: tens of poses with a thousand sightings each): `slices` workgroups share a pose, so that a thread has one
   // or two sightings instead of a chain of dependent gathers, and add their sums atomically
   const int64_t p = blockIdx.x / slices;
@@ -482,17 +491,18 @@ __global__ void __launch_bounds__(kBlock) k_pose_pass(BlocksDev b, ReprojPoseDev
   if (threadIdx.x < 27) {
     double t = 0.0;
     for (int i = 0; i < kBlock / 64; ++i) t += red[i][threadIdx.x];
-    const int k = threadIdx.x;
-    if (k < 21) {
-      // packed lower-triangular index -> (x, y)
-      int x = 0, base = 0;
-      while (base + x + 1 <= k) { base += x + 1; ++x; }
-      const int y = k - base;
-      if (slices > 1) atomic_add_f64(&rd.Hdiag[36 * (int64_t)vid + 6 * x + y], t); else rd.Hdiag[36 * (int64_t)vid + 6 * x + y] += t;
-    } else {
-      if (slices > 1) atomic_add_f64(&rd.g[6 * (int64_t)vid + (k - 21)], t); else rd.g[6 * (int64_t)vid + (k - 21)] += t;
-    }
+    double* dst = pose_lin_target(rd, vid, threadIdx.x);
+    if (lin) lin[27 * p + threadIdx.x] = t;
+    else if (slices > 1) atomic_add_f64(dst, t);
+    else *dst += t;
   }
+}
+// the staged sums of the current point into the freshly cleared Hdiag / g: a thread per entry, one writer each
+__global__ void __launch_bounds__(kBlock) k_pose_lin_add(BlocksDev b, const double* __restrict__ lin, ReducedDev rd) {
+  const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (t >= 27 * b.P) return;
+  const int32_t vid = b.pose_vid[t / 27];
+  if (vid >= 0) *pose_lin_target(rd, vid, (int)(t % 27)) += lin[t];
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1479,6 +1489,91 @@ __device__ __forceinline__ void cost_reproj_block(int64_t p, const BlocksDev& b,
   block_accumulate(cost, scal, mode == 0 ? SC_COST_CAND : SC_COST_FIXED, b.deterministic);
 }
 
+// The trial cost of a pose's sightings and, in the same walk, the pose side of the linearisation at the candidate: an accepted candidate is
+// the next step's current point, and k_pose_pass there would read the same arrays at the same values.  A variable pose: the loop, the
+// per-thread order and the reduction of k_pose_pass (unsliced), the 27 sums stored at lin[27 p ..]; every active sighting of it counts
+// for the cost.  A constant pose has no sums: cost_reproj_block.
+template <bool PIPE>
+__device__ __forceinline__ void cost_lin_block(int64_t p, const BlocksDev& b, const ReprojPoseDev& rq, const DevCam* __restrict__ cams,
+                                               const PoseCache* __restrict__ pc, const double* __restrict__ points, double* __restrict__ lin, double* scal) {
+  if (b.pose_vid[p] < 0) { cost_reproj_block<PIPE>(p, b, rq, cams, pc, points, 0, scal); return; }   // uniform per workgroup
+  __shared__ double red[kBlock / 64][27];
+  const PoseCache cache = pc[p];
+  double acc[27], cost = 0.0;
+#pragma unroll
+  for (int k = 0; k < 27; ++k) acc[k] = 0.0;
+  const uint32_t beg = rq.pose_ptr[p], end = rq.pose_ptr[p + 1];
+  if (PIPE) {
+    struct ByK { uint32_t l; double2 px; double sg; uint16_t cam; uint8_t act; };
+    auto by_k = [&](uint32_t k) { ByK o; o.act = rq.active[k]; o.l = rq.point[k]; o.px = rq.pixel[k]; o.cam = rq.cam[k]; o.sg = rq.sigma[k]; return o; };
+    uint32_t k = beg + threadIdx.x;
+    ByK cur = {};
+    if (k < end) cur = by_k(k);
+    for (; k < end; k += kBlock) {
+      ByK nxt = {};
+      if (k + kBlock < end) nxt = by_k(k + kBlock);
+      const ByK o = cur;
+      cur = nxt;
+      const uint32_t l = o.l;
+      const double X[3] = {points[3 * (int64_t)l], points[3 * (int64_t)l + 1], points[3 * (int64_t)l + 2]};
+      double r[2], Jp[12], Jl[6];
+      reproj_eval<true>(cache, cams[o.cam], X, o.px.x, o.px.y, o.sg, r, Jp, Jl);
+      double rho0, w;
+      huber_eval(r[0] * r[0] + r[1] * r[1], rq.huber, &rho0, &w);
+      if (o.act) {
+        cost += 0.5 * rho0;
+        int e = 0;
+  #pragma unroll
+        for (int x = 0; x < 6; ++x) {
+  #pragma unroll
+          for (int y = 0; y <= x; ++y) acc[e++] += w * (Jp[x] * Jp[y] + Jp[6 + x] * Jp[6 + y]);
+        }
+  #pragma unroll
+        for (int x = 0; x < 6; ++x) acc[21 + x] += w * (Jp[x] * r[0] + Jp[6 + x] * r[1]);
+      }
+    }
+  } else {
+    // (the flag and the feature index of the next sighting are in flight during this one's arithmetic: two of the three dependent loads of a sighting)
+    uint32_t k = beg + threadIdx.x, l_next = 0;
+    uint8_t act_next = 0;
+    if (k < end) { act_next = rq.active[k]; l_next = rq.point[k]; }
+    for (; k < end; k += kBlock) {
+      const uint8_t act = act_next;
+      const uint32_t l = l_next;
+      if (k + kBlock < end) { act_next = rq.active[k + kBlock]; l_next = rq.point[k + kBlock]; }
+      if (!act) continue;
+      const double X[3] = {points[3 * (int64_t)l], points[3 * (int64_t)l + 1], points[3 * (int64_t)l + 2]};
+      const double2 px = rq.pixel[k];
+      double r[2], Jp[12], Jl[6];
+      reproj_eval<true>(cache, cams[rq.cam[k]], X, px.x, px.y, rq.sigma[k], r, Jp, Jl);
+      double rho0, w;
+      huber_eval(r[0] * r[0] + r[1] * r[1], rq.huber, &rho0, &w);
+      cost += 0.5 * rho0;
+      int e = 0;
+  #pragma unroll
+      for (int x = 0; x < 6; ++x) {
+  #pragma unroll
+        for (int y = 0; y <= x; ++y) acc[e++] += w * (Jp[x] * Jp[y] + Jp[6 + x] * Jp[6 + y]);
+      }
+  #pragma unroll
+      for (int x = 0; x < 6; ++x) acc[21 + x] += w * (Jp[x] * r[0] + Jp[6 + x] * r[1]);
+    }
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < 27; ++k) {
+    const double v = wave_sum(acc[k]);
+    if (lane == 0) red[wv][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < 27) {
+    double t = 0.0;
+    for (int i = 0; i < kBlock / 64; ++i) t += red[i][threadIdx.x];
+    lin[27 * p + threadIdx.x] = t;
+  }
+  block_accumulate(cost, scal, SC_COST_CAND, b.deterministic);
+}
+
 // small factors: one kernel, thread ranges [bbox | shape | ltm | relpose | map pair]
 __device__ __forceinline__ void cost_small_block(int64_t block, const BlocksDev& b, const SmallFactorsDev& sf, const DevCam* __restrict__ cams,
                                                  const double* __restrict__ poses, const double* __restrict__ objects, int mode, double* scal) {
@@ -1536,11 +1631,15 @@ __device__ __forceinline__ void cost_small_block(int64_t block, const BlocksDev&
   block_accumulate(cost, scal, mode == 0 ? SC_COST_CAND : SC_COST_FIXED, b.deterministic);
 }
 // one launch: workgroups [0, n_pose_blocks) take the reprojection factors of a pose, the rest the small factor families
-template <bool PIPE>
-__global__ void __launch_bounds__(kBlock) k_cost(BlocksDev b, ReprojPoseDev rq, SmallFactorsDev sf, const DevCam* __restrict__ cams, const PoseCache* __restrict__ pc,
+// (LIN: mode 0 with the pose side of the linearisation staged at `lin`, cost_lin_block)
+template <bool PIPE, bool LIN>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PIPE ? 3 : 4))) k_cost(BlocksDev b, ReprojPoseDev rq, SmallFactorsDev sf, const DevCam* __restrict__ cams, const PoseCache* __restrict__ pc,
                                                 const double* __restrict__ poses, const double* __restrict__ points, const double* __restrict__ objects, int mode,
-                                                int n_pose_blocks, double* scal) {
-  if ((int)blockIdx.x < n_pose_blocks) cost_reproj_block<PIPE>(blockIdx.x, b, rq, cams, pc, points, mode, scal);
+                                                int n_pose_blocks, double* scal, double* __restrict__ lin) {
+  if ((int)blockIdx.x < n_pose_blocks) {
+    if (LIN) cost_lin_block<PIPE>(blockIdx.x, b, rq, cams, pc, points, lin, scal);
+    else cost_reproj_block<PIPE>(blockIdx.x, b, rq, cams, pc, points, mode, scal);
+  }
   else cost_small_block((int64_t)blockIdx.x - n_pose_blocks, b, sf, cams, poses, objects, mode, scal);
 }
 
@@ -1994,19 +2093,23 @@ void launch_point_pass(hipStream_t s, const BlocksDev& b, const ReprojDev& rp, c
     hipLaunchKernelGGL(k_point_pass_long, g, dim3(kBlock), 0, s, b, rp, cams, pc, points, rd, pt, radius, first_iter, scal, long_points, n_long); });
 }
 void launch_pose_pass(hipStream_t s, const BlocksDev& b, const ReprojPoseDev& rq, const DevCam* cams, const PoseCache* pc, const double* points,
-                      const ReducedDev& rd) {
+                      const ReducedDev& rd, double* lin) {
   if (b.P <= 0 || rq.n <= 0) return;
+  if (lin && !pose_pass_unsliced(b)) throw std::invalid_argument("launch_pose_pass: a staged set with a sliced pose pass");
   // a pose's workgroup walks its sightings 256 at a time; with few poses (a window) that loop is the latency of the launch: cut it
   // (not in the deterministic mode: one writer per block)
   constexpr int max_slices = 8;
   const int64_t per_pose = (rq.n + b.P - 1) / b.P;
   int slices = 1;
-  constexpr int64_t slice_below = 256;   // (poses)
-  if (!b.deterministic && b.P <= slice_below) slices = (int)std::max<int64_t>(1, std::min<int64_t>(max_slices, (per_pose + kBlock - 1) / kBlock));
+  constexpr int64_t slice_below = kPoseSliceBelow;   // (poses)
+  if (!pose_pass_unsliced(b)) slices = (int)std::max<int64_t>(1, std::min<int64_t>(max_slices, (per_pose + kBlock - 1) / kBlock));
   // few poses: the loads of a sighting in two rounds with the next sighting's first round in flight (150 registers); many poses: the plain loop
   // (120 registers: beside the strip kernel the side stream is otherwise the longer one -- 2.02 vs 1.95 ms per LM iteration)
-  if (b.P <= slice_below) hipLaunchKernelGGL(k_pose_pass<true>, dim3((unsigned)(b.P * slices)), dim3(kBlock), 0, s, b, rq, cams, pc, points, rd, slices);
-  else hipLaunchKernelGGL(k_pose_pass<false>, dim3((unsigned)(b.P * slices)), dim3(kBlock), 0, s, b, rq, cams, pc, points, rd, slices);
+  if (b.P <= slice_below) hipLaunchKernelGGL(k_pose_pass<true>, dim3((unsigned)(b.P * slices)), dim3(kBlock), 0, s, b, rq, cams, pc, points, rd, slices, lin);
+  else hipLaunchKernelGGL(k_pose_pass<false>, dim3((unsigned)(b.P * slices)), dim3(kBlock), 0, s, b, rq, cams, pc, points, rd, slices, lin);
+}
+void launch_pose_lin_add(hipStream_t s, const BlocksDev& b, const double* lin, const ReducedDev& rd) {
+  if (b.P > 0) hipLaunchKernelGGL(k_pose_lin_add, dim3(grid_for(27 * b.P, kBlock)), dim3(kBlock), 0, s, b, lin, rd);
 }
 void launch_small_factors(hipStream_t s, const BlocksDev& b, const SmallFactorsDev& sf, const DevCam* cams, const double* poses,
                           const double* objects, const ReducedDev& rd, double* scal, int64_t lanes_below) {
@@ -2090,16 +2193,23 @@ void launch_backsub_apply(hipStream_t s, const BlocksDev& b, const ReprojDev& rp
 }
 void launch_cost(hipStream_t s, const BlocksDev& b, const ReprojPoseDev& rq, const SmallFactorsDev& sf, const DevCam* cams, const PoseCache* pc_cur,
                  const double* poses_cur, const double* points_cur, const double* objects_cur, const PoseCache* pc_cand, const double* poses_cand,
-                 const double* points_cand, const double* objects_cand, int mode, double* scal) {
+                 const double* points_cand, const double* objects_cand, int mode, double* scal, double* lin) {
   // mode 0: cost of the variable residual blocks at the candidate; mode 1: cost of the all-constant blocks at the current point
+  // lin (mode 0, unsliced pose pass): the candidate's staged set, filled by the same walk
+  if (lin && (mode != 0 || !pose_pass_unsliced(b))) throw std::invalid_argument("launch_cost: a staged set outside the trial cost of an unsliced pose pass");
   const PoseCache* pc = mode == 0 ? pc_cand : pc_cur;
   const double* poses = mode == 0 ? poses_cand : poses_cur;
   const double* points = mode == 0 ? points_cand : points_cur;
   const double* objects = mode == 0 ? objects_cand : objects_cur;
   const int n_pose_blocks = (int)cost_grid(b.P, rq.n, 0);
   launch_reducing(s, b, scal, cost_grid(b.P, rq.n, num_small_factors(sf)), mode == 0 ? OBVI_SC(SC_COST_CAND) : OBVI_SC(SC_COST_FIXED), [&](dim3 g) {
-    if (b.P <= 256) hipLaunchKernelGGL(k_cost<true>, g, dim3(kBlock), 0, s, b, rq, sf, cams, pc, poses, points, objects, mode, n_pose_blocks, scal);   // (few poses: cost_reproj_block)
-    else hipLaunchKernelGGL(k_cost<false>, g, dim3(kBlock), 0, s, b, rq, sf, cams, pc, poses, points, objects, mode, n_pose_blocks, scal); });
+    if (b.P <= 256) {   // (few poses: cost_reproj_block)
+      if (lin) hipLaunchKernelGGL((k_cost<true, true>), g, dim3(kBlock), 0, s, b, rq, sf, cams, pc, poses, points, objects, mode, n_pose_blocks, scal, lin);
+      else hipLaunchKernelGGL((k_cost<true, false>), g, dim3(kBlock), 0, s, b, rq, sf, cams, pc, poses, points, objects, mode, n_pose_blocks, scal, lin);
+    } else {
+      if (lin) hipLaunchKernelGGL((k_cost<false, true>), g, dim3(kBlock), 0, s, b, rq, sf, cams, pc, poses, points, objects, mode, n_pose_blocks, scal, lin);
+      else hipLaunchKernelGGL((k_cost<false, false>), g, dim3(kBlock), 0, s, b, rq, sf, cams, pc, poses, points, objects, mode, n_pose_blocks, scal, lin);
+    } });
 }
 void launch_evaluate(hipStream_t s, const BlocksDev& b, const ReprojDev& rp, const uint32_t* rp_perm, const SmallFactorsDev& sf, const DevCam* cams,
                      const PoseCache* pc, const double* poses, const double* points, const double* objects, int apply_loss, const EvalLayout& lay,

@@ -14,6 +14,9 @@ namespace obvi_lib {
 static std::atomic<int> g_active_solves{0};
 struct ActiveSolve { ActiveSolve() { g_active_solves.fetch_add(1, std::memory_order_relaxed); } ~ActiveSolve() { g_active_solves.fetch_sub(1, std::memory_order_relaxed); } };
 
+// The pose side of the linearisation is staged (ba_handle.h, d_lin): where the pose pass runs one workgroup per pose, unless OBVI_POSE_LIN_REUSE=0
+static bool lin_reuse(const obvi_ba_handle* h, const BlocksDev& b) { return h->knobs.pose_lin_reuse && b.P > 0 && h->n_rp > 0 && pose_pass_unsliced(b); }
+
 // Stage 1 of an LM step, up to the join: linearise and assemble the damped reduced system (`schur` false: no Schur complement; `exchange`: sum the shared objects' blocks)
 void assemble_step(obvi_ba_handle* h, double radius, bool first_iter, bool schur, bool exchange) {
   hipStream_t s = h->stream; double* scal = h->d_scal.get();
@@ -39,6 +42,20 @@ void assemble_step(obvi_ba_handle* h, double radius, bool first_iter, bool schur
   // it forks in front of the point pass.
   const bool fork_early = side && h->n_rp < fork_early_below;
   auto side_pose_pass = [&] {
+    if (lin_reuse(h, b)) {
+      // the 27 sums per pose of the current point: left by the trial cost of the step that was accepted, or by the step before a rejected one (they do not
+      // depend on the radius); the pose pass itself only where there are none, the first step of a solve.  Hdiag and g are freshly cleared: one add per entry.
+      if (!h->lin_valid) {
+        record(h, PH_POSE_PASS, s2);
+        launch_pose_pass(s2, b, reproj_pose_dev(h), h->d_cams.get(), h->d_pc.get(), h->d_point.get(), rd, h->d_lin.get());
+        if (side) record_end(h, PH_POSE_PASS, s2);
+        h->lin_valid = true;
+      }
+      record(h, PH_POSE_LIN_ADD, s2);
+      launch_pose_lin_add(s2, b, h->d_lin.get(), rd);
+      if (side) record_end(h, PH_POSE_LIN_ADD, s2);
+      return;
+    }
     record(h, PH_POSE_PASS, s2);
     launch_pose_pass(s2, b, reproj_pose_dev(h), h->d_cams.get(), h->d_pc.get(), h->d_point.get(), rd);
     if (side) record_end(h, PH_POSE_PASS, s2);
@@ -133,8 +150,10 @@ static void trial_point_step(obvi_ba_handle* h, bool solve, bool exchange) {
   if (solve) launch_backsub_apply(s, b, reproj_dev(h), point_dev(h), reduced_dev(h), h->d_point.get(), h->d_point_c.get(), h->d_pose.get(), h->d_obj.get(), h->d_pose_c.get(), h->d_obj_c.get(), h->d_pc_c.get(), scal, h->knobs.backsub_lanes);
   record(h, PH_APPLY);   // (the candidate poses / objects are formed in the same launch)
   record(h, PH_COST);
+  // (where the pose side is staged, the same walk leaves the candidate's 27 sums per pose: what the next step's pose pass would compute if the candidate is accepted)
+  h->lin_c_valid = solve && lin_reuse(h, b);
   if (solve) launch_cost(s, b, reproj_pose_dev(h), small_dev(h), h->d_cams.get(), h->d_pc.get(), h->d_pose.get(), h->d_point.get(), h->d_obj.get(), h->d_pc_c.get(),
-                         h->d_pose_c.get(), h->d_point_c.get(), h->d_obj_c.get(), 0, scal);
+                         h->d_pose_c.get(), h->d_point_c.get(), h->d_obj_c.get(), 0, scal, h->lin_c_valid ? h->d_lin_c.get() : nullptr);
   if (solve) launch_map_group_cost(s, b, map_group_dev(h), h->d_obj_c.get(), 0, scal);
   record(h, PH_COUNT);
   if (exchange) {   // (3) every rank must take the same decision: the sums and every rank's gradient maximum in one collective
@@ -164,11 +183,13 @@ static bool publish_and_wait(obvi_ba_handle* h, bool keep_factor, double t_submi
     // cleared behind it), so the same step is submitted again on the schedule that cannot wait -- and the handle stays on it
     if (!h->fused_potrf) throw HipError{hipErrorLaunchTimeOut, "tile Cholesky: wait time-out on the two-launch schedule", __FILE__, __LINE__};
     h->fused_potrf = false; h->potrf_wait_timeouts++;
+    std::fill(std::begin(h->phase_recorded), std::end(h->phase_recorded), false);
     return false;
   }
   for (int p = 0; p < PH_COUNT && h->profiling >= 1; ++p) {   // phase timings are opt-in: a dozen event queries per LM iteration are not free
+    if (!h->phase_recorded[p]) continue;   // (not in this step: the pose pass where its sums were staged)
     int q = p + 1;
-    while (q < PH_COUNT && h->phase_on_side[q]) ++q;   // next phase boundary on the main stream (a side-stream phase ends at its own event)
+    while (q < PH_COUNT && (h->phase_on_side[q] || !h->phase_recorded[q])) ++q;   // next phase boundary on the main stream (a side-stream phase ends at its own event)
     float ms = 0.f;
     OBVI_HIP(hipEventElapsedTime(&ms, h->ev[p], h->phase_on_side[p] ? h->ev_end[p] : h->ev[q]));
     h->phase_ms[p] += ms; h->phase_launches[p] += 1;
@@ -180,6 +201,7 @@ static bool publish_and_wait(obvi_ba_handle* h, bool keep_factor, double t_submi
     OBVI_HIP(hipEventElapsedTime(&ms, h->ck_pool[i - 1], h->ck_pool[i]));
     h->ck_ms[tag] += ms; h->ck_launches[tag] += 1;
   }
+  std::fill(std::begin(h->phase_recorded), std::end(h->phase_recorded), false);
   return true;
 }
 
@@ -226,8 +248,8 @@ int obvi_ba_solve(obvi_ba_handle* h, const obvi_solver_params* prm, obvi_summary
   h->iterations.clear();
   { const int vrc = validate_indices(h); if (vrc != OBVI_OK) return vrc; }
   prepare(h);
-  h->pc_valid = false; h->tiles_cleared = false; h->cov_valid = false;
-  const double ms0[3] = {h->phase_ms[PH_POINT_PASS] + h->phase_ms[PH_POSE_PASS] + h->phase_ms[PH_SMALL] + h->phase_ms[PH_MAP_QUAD] + h->phase_ms[PH_MAP_SCATTER] + h->phase_ms[PH_DIAG] + h->phase_ms[PH_POSE_CACHE],
+  h->pc_valid = false; h->lin_valid = false; h->tiles_cleared = false; h->cov_valid = false;
+  const double ms0[3] = {h->phase_ms[PH_POINT_PASS] + h->phase_ms[PH_POSE_PASS] + h->phase_ms[PH_POSE_LIN_ADD] + h->phase_ms[PH_SMALL] + h->phase_ms[PH_MAP_QUAD] + h->phase_ms[PH_MAP_SCATTER] + h->phase_ms[PH_DIAG] + h->phase_ms[PH_POSE_CACHE],
                          h->phase_ms[PH_SCHUR] + h->phase_ms[PH_SCHUR_BLOCKS] + h->phase_ms[PH_CHOL] + h->phase_ms[PH_BACKSUB] + h->phase_ms[PH_APPLY], h->phase_ms[PH_COST]};
   hipStream_t s = h->stream;
 
@@ -266,7 +288,7 @@ int obvi_ba_solve(obvi_ba_handle* h, const obvi_solver_params* prm, obvi_summary
     for (const auto& it : h->iterations) sum->final_cost = std::min(sum->final_cost, it.cost);
     sum->is_solution_usable = (term == OBVI_CONVERGENCE || term == OBVI_NO_CONVERGENCE) ? 1 : 0;
     sum->total_time_in_seconds = wall_s() - t_start;
-    sum->jacobian_evaluation_time_in_seconds = 1e-3 * (h->phase_ms[PH_POINT_PASS] + h->phase_ms[PH_POSE_PASS] + h->phase_ms[PH_SMALL] + h->phase_ms[PH_MAP_QUAD] + h->phase_ms[PH_MAP_SCATTER] + h->phase_ms[PH_DIAG] + h->phase_ms[PH_POSE_CACHE] - ms0[0]);
+    sum->jacobian_evaluation_time_in_seconds = 1e-3 * (h->phase_ms[PH_POINT_PASS] + h->phase_ms[PH_POSE_PASS] + h->phase_ms[PH_POSE_LIN_ADD] + h->phase_ms[PH_SMALL] + h->phase_ms[PH_MAP_QUAD] + h->phase_ms[PH_MAP_SCATTER] + h->phase_ms[PH_DIAG] + h->phase_ms[PH_POSE_CACHE] - ms0[0]);
     sum->linear_solver_time_in_seconds = 1e-3 * (h->phase_ms[PH_SCHUR] + h->phase_ms[PH_SCHUR_BLOCKS] + h->phase_ms[PH_CHOL] + h->phase_ms[PH_BACKSUB] + h->phase_ms[PH_APPLY] - ms0[1]);
     sum->residual_evaluation_time_in_seconds = 1e-3 * (h->phase_ms[PH_COST] - ms0[2]);
   };
@@ -374,6 +396,7 @@ int obvi_ba_solve(obvi_ba_handle* h, const obvi_solver_params* prm, obvi_summary
     if (it.relative_decrease > kMinRelDecrease) {
       // HandleSuccessfulStep: the candidate becomes the current point
       h->d_pose.swap(h->d_pose_c); h->d_point.swap(h->d_point_c); h->d_obj.swap(h->d_obj_c); h->d_pc.swap(h->d_pc_c);   // the candidate's pose cache comes along
+      h->d_lin.swap(h->d_lin_c); h->lin_valid = h->lin_c_valid; h->lin_c_valid = false;   // ... and the pose side of its linearisation, where the trial cost staged it
       if (best_is_current) {   // the point just left is the best so far: it stays where it is, the old best buffers take the next candidate
         h->d_pose_c.swap(h->d_pose_b); h->d_point_c.swap(h->d_point_b); h->d_obj_c.swap(h->d_obj_b);
         best_is_current = false;
@@ -400,7 +423,7 @@ int obvi_ba_solve(obvi_ba_handle* h, const obvi_solver_params* prm, obvi_summary
   }
   // hand back the minimum-cost iterate; after a FAILURE the state at entry
   if (sum->termination_type == OBVI_FAILURE) restore_from(h, h->d_pose_e, h->d_point_e, h->d_obj_e);
-  else if (have_best && !best_is_current) { restore_from(h, h->d_pose_b, h->d_point_b, h->d_obj_b); h->pc_valid = false; }
+  else if (have_best && !best_is_current) { restore_from(h, h->d_pose_b, h->d_point_b, h->d_obj_b); h->pc_valid = false; h->lin_valid = false; }
   sync(h);
   return OBVI_OK;
   OBVI_API_END(h)

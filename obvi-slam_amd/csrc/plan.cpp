@@ -992,11 +992,12 @@ struct PlanBuilder {
     h->d_pose_c.resize((size_t)6 * P + 1); h->d_point_c.resize((size_t)3 * L + 1); h->d_obj_c.resize((size_t)h->od * O + 1);
     h->d_pose_b.resize((size_t)6 * P + 1); h->d_point_b.resize((size_t)3 * L + 1); h->d_obj_b.resize((size_t)h->od * O + 1);
     h->d_pc.resize(2 * ((size_t)P + 1)); h->d_pc_c.resize(2 * ((size_t)P + 1));   // records, then the field-major copy (k_pose_cache)
+    h->d_lin.resize((size_t)27 * P + 1); h->d_lin_c.resize((size_t)27 * P + 1);
     finish_upload(h);  // host vectors above go out of scope
   }
 
   void remember_what_the_plan_was_built_for() {
-    h->dirty = false; h->mask_dirty = false; h->pc_valid = false; h->tiles_cleared = false;
+    h->dirty = false; h->mask_dirty = false; h->pc_valid = false; h->lin_valid = false; h->tiles_cleared = false;
     h->plan_serial++; h->cov_valid = false;
     h->plan_pose_vid = pose_vid; h->plan_obj_vid = obj_vid; h->plan_point_var = point_var; h->plan_is_pad = h->h_is_pad;
     const FamilyTable fams = families(h);
@@ -1085,7 +1086,7 @@ bool prepare_masks(obvi_ba_handle* h) {
   h->num_params = h->live_rows + 3 * nL;
   h->num_residuals = nres;
   finish_upload(h);   // (the copies went through the pinned arena: nothing to wait for; the solve's first launches follow on the same stream)
-  h->mask_dirty = false; h->pc_valid = false; h->tiles_cleared = false; h->cov_valid = false;
+  h->mask_dirty = false; h->pc_valid = false; h->lin_valid = false; h->tiles_cleared = false; h->cov_valid = false;
   return true;
 }
 
