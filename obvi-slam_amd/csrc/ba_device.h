@@ -76,6 +76,7 @@ inline __host__ __device__ int det_scalar_of(int slot) {
 // The grid of every kernel that leaves partial sums, defined once: its launcher in ba_kernels.hip launches it, det_slots_needed sizes the slots by it.
 // A grid made of parts adds up over them: with the other parts' counts at 0 it is one part's workgroups (the boundaries the launchers hand the kernels).
 constexpr int kBaBlock = 256;   // threads per workgroup of the ba_kernels.hip kernels (kBlock there) but k_small_lin_lanes and k_eval_small (64)
+// (k_bbox_lin_dense packs four workgroups of k_small_lin_lanes' bounding-box part into one and leaves their four partial sums: the grid below counts for both)
 inline int64_t blocks_of(int64_t n, int64_t per) { return (n + per - 1) / per; }
 inline int64_t point_pass_grid(int64_t n_waves) { return blocks_of(n_waves, kBaBlock / 64); }   // k_point_pass: a wavefront per piece of the observation list
 inline int64_t point_pass_long_grid(int64_t n_long) { return blocks_of(n_long, kBaBlock); }     // k_point_pass_long: a thread per long-track point
@@ -248,7 +249,8 @@ void launch_pose_pass(hipStream_t s, const BlocksDev& b, const ReprojPoseDev& rq
                       const double* points, const ReducedDev& rd, double* lin = nullptr);
 void launch_pose_lin_add(hipStream_t s, const BlocksDev& b, const double* lin, const ReducedDev& rd);
 void launch_small_factors(hipStream_t s, const BlocksDev& b, const SmallFactorsDev& sf, const DevCam* cams,
-                          const double* poses, const double* objects, const ReducedDev& rd, double* scal, int64_t lanes_below /* Knobs::small_lanes_below */);
+                          const double* poses, const double* objects, const ReducedDev& rd, double* scal, int64_t lanes_below /* Knobs::small_lanes_below */,
+                          bool packed /* Knobs::side_packed */);
 void launch_reduced_diag(hipStream_t s, const BlocksDev& b, const double* poses, const double* objects,
                          const ReducedDev& rd, double radius, int first_iter, double* scal);
 // map group priors; every launcher returns at once when there are no groups.  Linearisation: y = Lambda d and the slabs' partial sums (launch_map_group_quad,

@@ -60,10 +60,12 @@ __device__ __forceinline__ double wave_max(double v) {
 // a workgroup's total for scalar `sc`, one thread per workgroup: an fp64 atomic, or -- deterministic mode, ba_device.h -- the
 // workgroup's slot of the partial sums behind the scalar block (every workgroup of the grid must get here: the slots are not cleared).
 // `det` is BlocksDev.deterministic: 0, or the number of workgroups each slot has room for
-__device__ __forceinline__ void scal_add(double* scal, int det, int sc, double t) {
-  if (det) scal[SC_COUNT + (int64_t)det_slot_of(sc) * det + blockIdx.x] = t;
+// (`slot`: the workgroup's index in the grid the slots are counted by, where that is not the launch's own)
+__device__ __forceinline__ void scal_add(double* scal, int det, int sc, double t, int64_t slot) {
+  if (det) scal[SC_COUNT + (int64_t)det_slot_of(sc) * det + slot] = t;
   else if (t != 0.0) atomic_add_f64(scal + sc, t);
 }
+__device__ __forceinline__ void scal_add(double* scal, int det, int sc, double t) { scal_add(scal, det, sc, t, blockIdx.x); }
 // block-wide sum -> one atomic (or one partial-sum slot) per block
 __device__ __forceinline__ void block_accumulate(double v, double* scal, int sc, int det = 0) {
   __shared__ double sm[kBlock / 64];
@@ -538,7 +540,7 @@ __device__ __forceinline__ void store_diag_block(double* slot, int d, const doub
 }
 constexpr int kSmBlk = 62, kSmSecond = 35;   // scratch slot of a prior / relative-pose factor: first block at 0 (an object's: 35 entries, 54 for the 9-parameter block), a relative-pose factor's second block at 35
 
-__device__ __forceinline__ void object_priors_lin(int64_t block, const BlocksDev& b, const SmallFactorsDev& sf, const double* __restrict__ objects, const ReducedDev& rd, double* scal) {
+__device__ __forceinline__ void object_priors_lin(int64_t block, const BlocksDev& b, const SmallFactorsDev& sf, const double* __restrict__ objects, const ReducedDev& rd, double* scal, int64_t slot) {
   const int64_t t = block * 64LL + threadIdx.x;
   const int od = b.od;   // 7, or 9 for the unconstrained ellipsoid block
   double cost = 0.0;
@@ -581,7 +583,7 @@ __device__ __forceinline__ void object_priors_lin(int64_t block, const BlocksDev
     for (int e = 0; e < od * (od + 1) / 2 + od; ++e) slot[e] = 0.0;
   }
   cost = wave_sum(cost);
-  if (threadIdx.x == 0) scal_add(scal, b.deterministic, SC_COST, cost);
+  if (threadIdx.x == 0) scal_add(scal, b.deterministic, SC_COST, cost, slot);
 }
 
 // Small problems (a sliding window holds a few hundred of these factors): the thread-per-factor kernels above are then a handful of
@@ -600,8 +602,10 @@ static_assert(kBbBlk == 62 && kBbGo == 28 && kBbHpp == 35 && kBbGp == 56 && BbSl
 template <bool STORE, int OD>
 __device__ __forceinline__ void bbox_lin_lanes(int64_t block, const BlocksDev& b, const SmallFactorsDev& sf, const DevCam* __restrict__ cams, const double* __restrict__ poses,
                                                const double* __restrict__ objects, const ReducedDev& rd, double* scal) {
-  const int64_t i = block * 4LL + (threadIdx.x >> 4);
-  const int dir = threadIdx.x & 15, base = threadIdx.x & 48;
+  // `block`: the wavefront's four factors, and its partial-sum slot (k_small_lin_lanes: the workgroup; k_bbox_lin_dense: wavefront block % 4 of workgroup block / 4)
+  const int lane = threadIdx.x & 63;
+  const int64_t i = block * 4LL + (lane >> 4);
+  const int dir = lane & 15, base = lane & 48;
   uint32_t o = 0, p = 0;
   int32_t ov = -1, pv = -1;
   if (i < sf.n_bb && sf.bb_active[i]) { o = sf.bb_obj[i]; p = sf.bb_pose[i]; ov = b.obj_vid[o]; pv = b.pose_vid[p]; }
@@ -699,10 +703,10 @@ __device__ __forceinline__ void bbox_lin_lanes(int64_t block, const BlocksDev& b
     atomic_add_f64(rd.g + 6 * (int64_t)pv + x, w * acc);
   }
   cost = wave_sum(cost);
-  if (threadIdx.x == 0) scal_add(scal, b.deterministic, SC_COST, cost);
+  if (lane == 0) scal_add(scal, b.deterministic, SC_COST, cost, block);
 }
 // lanes 0..5 own the columns of the first pose, 6..11 of the second
-__device__ __forceinline__ void relpose_lin_lanes(int64_t block, const BlocksDev& b, const SmallFactorsDev& sf, const double* __restrict__ poses, const ReducedDev& rd, double* scal) {
+__device__ __forceinline__ void relpose_lin_lanes(int64_t block, const BlocksDev& b, const SmallFactorsDev& sf, const double* __restrict__ poses, const ReducedDev& rd, double* scal, int64_t slot) {
   const int64_t i = block * 4LL + (threadIdx.x >> 4);
   const int dir = threadIdx.x & 15, base = threadIdx.x & 48;
   uint32_t pa = 0, pb = 0;
@@ -773,7 +777,7 @@ __device__ __forceinline__ void relpose_lin_lanes(int64_t block, const BlocksDev
     }
   }
   cost = wave_sum(cost);
-  if (threadIdx.x == 0) scal_add(scal, b.deterministic, SC_COST, cost);
+  if (threadIdx.x == 0) scal_add(scal, b.deterministic, SC_COST, cost, slot);
 }
 
 // Map pair priors (include/obvi_map_prior.h).  The factor is linear in the raw parameters, so there is no dual arithmetic: lane x of the factor's
@@ -783,7 +787,7 @@ __device__ __forceinline__ void relpose_lin_lanes(int64_t block, const BlocksDev
 // slot of its lists); the lanes of the later-eliminated object add the off-diagonal block into the lower triangle -- one factor per unordered pair
 // (the upload refuses a second), so that block has one writer in either mode.
 template <int OD>
-__device__ __forceinline__ void map_pair_lin_lanes(int64_t block, const BlocksDev& b, const SmallFactorsDev& sf, const double* __restrict__ objects, const ReducedDev& rd, double* scal) {
+__device__ __forceinline__ void map_pair_lin_lanes(int64_t block, const BlocksDev& b, const SmallFactorsDev& sf, const double* __restrict__ objects, const ReducedDev& rd, double* scal, int64_t slot) {
   constexpr int G = OD == 7 ? 16 : 32, N = 2 * OD, NH = OD * (OD + 1) / 2;
   static_assert(N <= G && NH + OD <= kSmBlk, "a row per lane, a block per scratch slot");
   const int64_t i = block * (int64_t)(64 / G) + (threadIdx.x / G);
@@ -835,18 +839,29 @@ __device__ __forceinline__ void map_pair_lin_lanes(int64_t block, const BlocksDe
     }
   }
   cost = wave_sum(cost);
-  if (threadIdx.x == 0) scal_add(scal, b.deterministic, SC_COST, cost);
+  if (threadIdx.x == 0) scal_add(scal, b.deterministic, SC_COST, cost, slot);
 }
 
 // the four small-factor families of a small problem in one launch (at this size an iteration's first half is bound by the host's launches)
 template <bool STORE, int OD>
 __global__ void __launch_bounds__(64) k_small_lin_lanes(BlocksDev b, SmallFactorsDev sf, const DevCam* __restrict__ cams, const double* __restrict__ poses,
-                                                       const double* __restrict__ objects, ReducedDev rd, double* scal, int nb_bbox, int nb_priors, int nb_relpose) {
-  const int blk = blockIdx.x;
+                                                       const double* __restrict__ objects, ReducedDev rd, double* scal, int nb_bbox, int nb_priors, int nb_relpose, int blk0) {
+  // blk0 = nb_bbox where the bounding boxes have a launch of their own (k_bbox_lin_dense): the grid starts at the priors, the partial-sum slots stay where they were
+  const int blk = blockIdx.x + blk0;
   if (blk < nb_bbox) bbox_lin_lanes<STORE, OD>(blk, b, sf, cams, poses, objects, rd, scal);
-  else if (blk < nb_bbox + nb_priors) object_priors_lin(blk - nb_bbox, b, sf, objects, rd, scal);
-  else if (blk < nb_bbox + nb_priors + nb_relpose) relpose_lin_lanes(blk - nb_bbox - nb_priors, b, sf, poses, rd, scal);
-  else map_pair_lin_lanes<OD>(blk - nb_bbox - nb_priors - nb_relpose, b, sf, objects, rd, scal);
+  else if (blk < nb_bbox + nb_priors) object_priors_lin(blk - nb_bbox, b, sf, objects, rd, scal, blk);
+  else if (blk < nb_bbox + nb_priors + nb_relpose) relpose_lin_lanes(blk - nb_bbox - nb_priors, b, sf, poses, rd, scal, blk);
+  else map_pair_lin_lanes<OD>(blk - nb_bbox - nb_priors - nb_relpose, b, sf, objects, rd, scal, blk);
+}
+
+// Big problems (the STORE route): the bounding boxes alone, 16 factors per 256-thread workgroup -- each wavefront is one workgroup of the launch above,
+// lane for lane (its four factors, its partial-sum slot).  Beside the Schur strips a workgroup of four waves takes the place of one strip workgroup
+// on a CU; 64-thread workgroups were spread a wave per CU, and every CU that held one had room for one strip workgroup instead of two.
+template <int OD>
+__global__ void __launch_bounds__(kBlock) k_bbox_lin_dense(BlocksDev b, SmallFactorsDev sf, const DevCam* __restrict__ cams, const double* __restrict__ poses,
+                                                          const double* __restrict__ objects, ReducedDev rd, double* scal, int nb_bbox) {
+  const int64_t blk = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+  if (blk < nb_bbox) bbox_lin_lanes<true, OD>(blk, b, sf, cams, poses, objects, rd, scal);   // (uniform per wavefront; no barrier inside)
 }
 
 // The sums behind k_small_lin_lanes<true>: the diagonal blocks.  Workgroups [0, O): one per object, its factors' H_oo | g_o (CSR by
@@ -990,7 +1005,9 @@ __global__ void __launch_bounds__(kBlock) k_reduced_diag(BlocksDev b, const doub
 // (observation a of pose p, observation b of pose q, same point) is contiguous.
 // lanes 0..35: element (x,y); lanes 36..41 on diagonal blocks: rhs component x.
 // ---------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kBlock) k_schur_blocks(int64_t nblk, const uint32_t* __restrict__ blk_row, const uint32_t* __restrict__ blk_col,
+// Register budget: the kernel runs on the side stream beside k_schur_window, whose two workgroups per CU leave 512 - 2 x 216 = 80 registers
+// on every SIMD; six waves per SIMD is the occupancy band that holds an allocation to 80 (tests/test_side_register_budget.py reads the code object)
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(6))) k_schur_blocks(int64_t nblk, const uint32_t* __restrict__ blk_row, const uint32_t* __restrict__ blk_col,
                                                         const uint32_t* __restrict__ blk_ptr, const uint32_t* __restrict__ pair_a,
                                                         const uint32_t* __restrict__ pair_b, const uint32_t* __restrict__ obs_point,
                                                         PointDev pt, ReducedDev rd) {
@@ -2112,30 +2129,43 @@ void launch_pose_lin_add(hipStream_t s, const BlocksDev& b, const double* lin, c
   if (b.P > 0) hipLaunchKernelGGL(k_pose_lin_add, dim3(grid_for(27 * b.P, kBlock)), dim3(kBlock), 0, s, b, lin, rd);
 }
 void launch_small_factors(hipStream_t s, const BlocksDev& b, const SmallFactorsDev& sf, const DevCam* cams, const double* poses,
-                          const double* objects, const ReducedDev& rd, double* scal, int64_t lanes_below) {
+                          const double* objects, const ReducedDev& rd, double* scal, int64_t lanes_below, bool packed) {
   // few factors (below lanes_below: a sliding window): 16 lanes per factor, the latency of a handful of wavefronts is the whole side stream; one launch
   const int64_t grid = small_lin_grid(sf.n_bb, sf.n_sp + sf.n_lt, sf.n_rl, sf.n_mp, b.od);
   const int nb_bbox = (int)small_lin_grid(sf.n_bb, 0, 0), nb_priors = (int)small_lin_grid(0, sf.n_sp + sf.n_lt, 0), nb_relpose = (int)small_lin_grid(0, 0, sf.n_rl);
   if (grid == 0) return;
   // (the bounding-box lanes are compiled per ellipsoid block size: 13 or 15 directions on the factor's 16 lanes)
-#define OBVI_SMALL_LIN(STORE) launch_reducing(s, b, scal, grid, OBVI_SC(SC_COST), [&](dim3 g) { \
-    if (b.od == 9) hipLaunchKernelGGL((k_small_lin_lanes<STORE, 9>), g, dim3(64), 0, s, b, sf, cams, poses, objects, rd, scal, nb_bbox, nb_priors, nb_relpose); \
-    else hipLaunchKernelGGL((k_small_lin_lanes<STORE, 7>), g, dim3(64), 0, s, b, sf, cams, poses, objects, rd, scal, nb_bbox, nb_priors, nb_relpose); })
+#define OBVI_SMALL_LIN(STORE, BLK0) do { const dim3 g_((unsigned)(grid - (BLK0))); \
+    if (b.od == 9) hipLaunchKernelGGL((k_small_lin_lanes<STORE, 9>), g_, dim3(64), 0, s, b, sf, cams, poses, objects, rd, scal, nb_bbox, nb_priors, nb_relpose, BLK0); \
+    else hipLaunchKernelGGL((k_small_lin_lanes<STORE, 7>), g_, dim3(64), 0, s, b, sf, cams, poses, objects, rd, scal, nb_bbox, nb_priors, nb_relpose, BLK0); } while (0)
+  // the STORE route (big problems, deterministic handles): the bounding boxes in 256-thread workgroups of their own (k_bbox_lin_dense), the other families
+  // behind them from their first workgroup on; the partial-sum slots are those of the one launch (`packed` false: that launch, Knobs::side_packed)
+  auto store_route = [&] {
+    launch_reducing(s, b, scal, grid, OBVI_SC(SC_COST), [&](dim3) {
+      if (!packed) { OBVI_SMALL_LIN(true, 0); return; }
+      if (nb_bbox > 0) {
+        const dim3 g(grid_for(nb_bbox, kBlock / 64));
+        if (b.od == 9) hipLaunchKernelGGL(k_bbox_lin_dense<9>, g, dim3(kBlock), 0, s, b, sf, cams, poses, objects, rd, scal, nb_bbox);
+        else hipLaunchKernelGGL(k_bbox_lin_dense<7>, g, dim3(kBlock), 0, s, b, sf, cams, poses, objects, rd, scal, nb_bbox);
+      }
+      if (grid > nb_bbox) OBVI_SMALL_LIN(true, nb_bbox);
+    });
+  };
   if (b.deterministic) {
     // no fp64 atomics on the diagonal blocks: every factor leaves its blocks in a scratch slot, the gathers add them per target in list order
-    OBVI_SMALL_LIN(true);
+    store_route();
     if (sf.n_bb > 0) hipLaunchKernelGGL(k_bbox_gather, dim3((unsigned)b.O + grid_for(b.P, kBlock / 64)), dim3(kBlock), 0, s, b, sf, rd);
     if (sf.n_sp + sf.n_lt + sf.n_rl + sf.n_mp > 0) hipLaunchKernelGGL(k_small_gather, dim3(grid_for(b.O + b.P, kBlock / 64)), dim3(kBlock), 0, s, b, sf, rd);
     return;
   }
   if (sf.n_bb < lanes_below) {
-    OBVI_SMALL_LIN(false);
+    launch_reducing(s, b, scal, grid, OBVI_SC(SC_COST), [&](dim3) { OBVI_SMALL_LIN(false, 0); });
     return;
   }
   // many bounding boxes: per-factor blocks into the scratch, then one wavefront per object / pose sums them (no atomics); the priors and
-  // the relative-pose factors ride in the first launch, 16 lanes per factor at every size (a thread per factor left the 2 000 odometry
+  // the relative-pose factors keep 16 lanes per factor at every size (a thread per factor left the 2 000 odometry
   // factors of the global problem as 32 wavefronts dragging a 12-direction dual: 250 us)
-  OBVI_SMALL_LIN(true);
+  store_route();
   hipLaunchKernelGGL(k_bbox_gather, dim3((unsigned)b.O + grid_for(b.P, kBlock / 64)), dim3(kBlock), 0, s, b, sf, rd);
 #undef OBVI_SMALL_LIN
 }

@@ -62,7 +62,7 @@ void assemble_step(obvi_ba_handle* h, double radius, bool first_iter, bool schur
   };
   auto side_small_factors = [&] {
     record(h, PH_SMALL, s2);
-    launch_small_factors(s2, b, small_dev(h), h->d_cams.get(), h->d_pose.get(), h->d_obj.get(), rd, scal, h->knobs.small_lanes_below);
+    launch_small_factors(s2, b, small_dev(h), h->d_cams.get(), h->d_pose.get(), h->d_obj.get(), rd, scal, h->knobs.small_lanes_below, h->knobs.side_packed);
     if (side) record_end(h, PH_SMALL, s2);
     // map group priors (include/obvi_map_group_prior.h): behind the small factors' gathers, in front of the diagonal-block kernel that reads Hdiag and g
     const MapGroupDev mg = map_group_dev(h);
@@ -110,7 +110,8 @@ void assemble_step(obvi_ba_handle* h, double radius, bool first_iter, bool schur
     side_small_factors();
     side_diagonal();
     // the pairs outside every strip (loop closures, very long tracks) only need the point pass: beside the strip kernel as well (both add
-    // to the tile grid with atomics)
+    // to the tile grid with atomics).  Last on the side stream: first, where their kernel fits in the registers the strip waves leave
+    // (DESIGN.md section 3), measured 0.3 % slower per step (profiles/EXPERIMENTS.md, round 9)
     if (side && schur) schur_blocks_on(s2);
     if (side) OBVI_HIP(hipEventRecord(h->ev_join, s2));
     main_schur_window();
