@@ -64,6 +64,52 @@ const ProcessKnobs& process_knobs() {
   return p;
 }
 
+int object_cov_forward(obvi_ba_handle* h, int64_t n_pairs, const char* what, int64_t* ldt_out, CovTables& keep) {
+  *ldt_out = 0;
+  const int od = h->od;
+  // objects shared across ranks and an exchange hook: a collective call (include/obvi_ba.h) -- a member with no pairs of its own still takes part in the step's collectives
+  const bool collective = exchanging(h);
+  if ((n_pairs == 0 && !collective) || h->nOv == 0 || h->m == 0) return OBVI_OK;
+  if (collective) { const int trc = prove_tail_order(h, what); if (trc != OBVI_OK) return trc; }
+  // the undamped reduced system S = J_c^T J_c - (Schur complement of the features) at the current point, factorised: one
+  // LM step's linearisation and factorisation with the trust-region radius at infinity (its candidate point is not used)
+  upload_parameter_prior_diagonals(h);
+  { QuietStep quiet(h, /*use_extra=*/!h->h_pp_kind.empty()); submit_step(h, 1e300, true, true, /*keep_factor=*/true); }
+  if (h->h_scal[SC_CHOL_FAIL] != 0.0 || h->h_scal[SC_NONFINITE] != 0.0 || !std::isfinite(h->h_scal[SC_STEPSQ]))
+    return fail(h, OBVI_ERR_NUMERICAL, std::string(what) + ": the normal equations are rank deficient at the current estimate");
+  if (n_pairs == 0) return OBVI_OK;
+  hipStream_t s = h->stream;
+  const int nslabs = (int)((od * h->nOv + kTile - 1) / kTile);
+  const int64_t ldt = (int64_t)h->nt * kTile, nrhs = (int64_t)nslabs * kTile;   // Y = L^-1 E transposed: [nrhs][ldt]
+  std::vector<int32_t>& slab_first = keep.slab_first;
+  slab_first.assign(nslabs, h->nt);
+  for (int64_t w = 0; w < h->nOv; ++w) {
+    const int sl0 = (int)(od * w / kTile), sl1 = (int)((od * w + od - 1) / kTile);
+    for (int sl = sl0; sl <= sl1; ++sl) slab_first[sl] = std::min(slab_first[sl], h->h_obj_row[w] / kTile);
+  }
+  h->d_cov_Y.resize((size_t)(nrhs * ldt));
+  OBVI_HIP(hipMemsetAsync(h->d_cov_Y.get(), 0, sizeof(double) * (size_t)(nrhs * ldt), s));
+  h->d_cov_slab.upload(slab_first, s);
+  const CholPlan plan = chol_plan(h);
+  launch_forward_multi(s, plan, h->d_S.get(), h->d_Linv.get(), h->d_cov_Y.get(), ldt, nslabs, h->d_cov_slab.get(), h->d_obj_row.get(), (int32_t)h->nOv, h->h_row_split.data(), od);
+  *ldt_out = ldt;
+  return OBVI_OK;
+}
+
+void object_cov_pair_blocks(obvi_ba_handle* h, int64_t n_pairs, const uint32_t* obj_a, const uint32_t* obj_b, int64_t ldt, CovTables& keep) {
+  const int od = h->od;
+  std::vector<int32_t>& cols = keep.cols; std::vector<int32_t>& first_row = keep.first_row;
+  cols.assign(2 * n_pairs, 0); first_row.assign(n_pairs, 0);
+  for (int64_t i = 0; i < n_pairs; ++i) {
+    const int32_t va = h->h_obj_vid[obj_a[i]], vb = h->h_obj_vid[obj_b[i]];
+    cols[2 * i] = va >= 0 && vb >= 0 ? od * va : -1; cols[2 * i + 1] = va >= 0 && vb >= 0 ? od * vb : -1;
+    first_row[i] = va >= 0 && vb >= 0 ? std::max(h->h_obj_row[va], h->h_obj_row[vb]) / kTile * kTile : 0;   // both columns are zero above
+  }
+  h->d_cov_cols.upload(cols, h->stream); h->d_cov_first.upload(first_row, h->stream);
+  h->d_cov_out.resize((size_t)(od * od * n_pairs));
+  launch_cov_pairs(h->stream, h->d_cov_Y.get(), ldt, n_pairs, h->d_cov_cols.get(), h->d_cov_first.get(), h->d_cov_out.get(), od);
+}
+
 }  // namespace obvi_lib
 
 extern "C" {
@@ -304,38 +350,11 @@ int obvi_ba_object_covariances(obvi_ba_handle* h, int64_t n_pairs, const uint32_
   prepare(h);
   const int od = h->od, od2 = od * od;
   std::fill(cov49, cov49 + od2 * n_pairs, 0.0);
-  // objects shared across ranks and an exchange hook: a collective call (include/obvi_ba.h) -- a member with no pairs of its own still takes part in the step's collectives
-  const bool collective = exchanging(h);
-  if ((n_pairs == 0 && !collective) || h->nOv == 0 || h->m == 0) return OBVI_OK;
-  if (collective) { const int trc = prove_tail_order(h, "object_covariances"); if (trc != OBVI_OK) return trc; }
-  // the undamped reduced system S = J_c^T J_c - (Schur complement of the features) at the current point, factorised: one
-  // LM step's linearisation and factorisation with the trust-region radius at infinity (its candidate point is not used)
-  upload_parameter_prior_diagonals(h);
-  { QuietStep quiet(h, /*use_extra=*/!h->h_pp_kind.empty()); submit_step(h, 1e300, true, true, /*keep_factor=*/true); }
-  if (h->h_scal[SC_CHOL_FAIL] != 0.0 || h->h_scal[SC_NONFINITE] != 0.0 || !std::isfinite(h->h_scal[SC_STEPSQ]))
-    return fail(h, OBVI_ERR_NUMERICAL, "object_covariances: the normal equations are rank deficient at the current estimate");
-  if (n_pairs == 0) return OBVI_OK;
+  int64_t ldt = 0;
+  CovTables tables;   // alive until the wait below
+  { const int rc = object_cov_forward(h, n_pairs, "object_covariances", &ldt, tables); if (rc != OBVI_OK || ldt == 0) return rc; }
   hipStream_t s = h->stream;
-  const int nslabs = (int)((od * h->nOv + kTile - 1) / kTile);
-  const int64_t ldt = (int64_t)h->nt * kTile, nrhs = (int64_t)nslabs * kTile;   // Y = L^-1 E transposed: [nrhs][ldt]
-  std::vector<int32_t> slab_first(nslabs, h->nt);
-  for (int64_t w = 0; w < h->nOv; ++w) {
-    const int sl0 = (int)(od * w / kTile), sl1 = (int)((od * w + od - 1) / kTile);
-    for (int sl = sl0; sl <= sl1; ++sl) slab_first[sl] = std::min(slab_first[sl], h->h_obj_row[w] / kTile);
-  }
-  std::vector<int32_t> cols(2 * n_pairs), first_row(n_pairs);
-  for (int64_t i = 0; i < n_pairs; ++i) {
-    const int32_t va = h->h_obj_vid[obj_a[i]], vb = h->h_obj_vid[obj_b[i]];
-    cols[2 * i] = va >= 0 && vb >= 0 ? od * va : -1; cols[2 * i + 1] = va >= 0 && vb >= 0 ? od * vb : -1;
-    first_row[i] = va >= 0 && vb >= 0 ? std::max(h->h_obj_row[va], h->h_obj_row[vb]) / kTile * kTile : 0;   // both columns are zero above
-  }
-  h->d_cov_Y.resize((size_t)(nrhs * ldt));
-  OBVI_HIP(hipMemsetAsync(h->d_cov_Y.get(), 0, sizeof(double) * (size_t)(nrhs * ldt), s));
-  h->d_cov_slab.upload(slab_first, s); h->d_cov_cols.upload(cols, s); h->d_cov_first.upload(first_row, s);
-  h->d_cov_out.resize((size_t)(od2 * n_pairs));
-  const CholPlan plan = chol_plan(h);
-  launch_forward_multi(s, plan, h->d_S.get(), h->d_Linv.get(), h->d_cov_Y.get(), ldt, nslabs, h->d_cov_slab.get(), h->d_obj_row.get(), (int32_t)h->nOv, h->h_row_split.data(), od);
-  launch_cov_pairs(s, h->d_cov_Y.get(), ldt, n_pairs, h->d_cov_cols.get(), h->d_cov_first.get(), h->d_cov_out.get(), od);
+  object_cov_pair_blocks(h, n_pairs, obj_a, obj_b, ldt, tables);
   OBVI_HIP(hipGetLastError());
   h->d_cov_out.download(cov49, (size_t)(od2 * n_pairs), s);
   sync(h);

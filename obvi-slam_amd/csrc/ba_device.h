@@ -199,7 +199,7 @@ struct MapGroupDev {
 // of map_idx; Lambda / Csym (N rows of ld doubles) at lam_off, W (N x N) at w_off -- the offsets of MapGroupDev.
 constexpr int kMapGroupMaxRows = 2048;   // OBVI_MAP_GROUP_MAX_ROWS
 constexpr int kMapPowerSteps = 40;       // power steps of the condition estimate, on C and on Lambda
-enum MapStatus { MS_BAD = 0, MS_PIV_MIN, MS_PIV_MAX, MS_EV_C, MS_EV_LAMBDA, kMapStatusDoubles = 8 };   // one record per group, read back once per call
+enum MapStatus { MS_BAD = 0, MS_PIV_MIN, MS_PIV_MAX, MS_EV_C, MS_EV_LAMBDA, MS_NONFINITE, kMapStatusDoubles = 8 };   // one record per group, read back once per call (MS_NONFINITE: the map update's alone)
 struct MapCutGroup { int32_t N, nt, ld, pad; int64_t tile0, diag0, member0, lam_off, w_off; };
 struct MapCutDev {
   int64_t n; int32_t od; int64_t rows;   // groups of the call; rows of all of them
@@ -211,6 +211,31 @@ struct MapCutDev {
 // gather, Cholesky by tile column (three launches per column of the largest group), W = L^-1, Lambda = W^T W, kMapPowerSteps power steps, the status records.
 // W and the padding of Lambda must have been zeroed on the stream.  x0: kMapGroupMaxRows doubles, the fixed start of the power iterations.
 void launch_map_cut(hipStream_t s, const MapCutDev& m, int nt_max, const double* map_mean, const double* map_cov, int64_t ldc, const double* x0);
+// ... its two halves, which launch_map_cut runs one after the other: gather, Cholesky and W (the factor); Lambda, the power steps and the status records (what
+// the condition test reads).
+void launch_map_factor(hipStream_t s, const MapCutDev& m, int nt_max, const double* map_mean, const double* map_cov, int64_t ldc);
+void launch_map_condition_estimate(hipStream_t s, const MapCutDev& m, int nt_max, const double* x0);
+
+// A map conditioned on the posterior of some of its objects (include/obvi_map_update.h; map_kernels.hip): C' = Cs - Z Y^T, mu' = mu + Y v with Y = Cs[:, A] W^T,
+// Z = Y (I - W Ps W^T), v = W (m - mu_A), W = L^-1 of Cs_AA = L L^T -- the factor of a one-group cut of the window's objects A, which ran before on the stream and
+// left Wt (its tiles of W^T), W (dense, N_A x N_A), mean_A and the status record.  N map rows in nN tile rows, N_A window rows in nA; every tile operand is
+// [tile rows][nA] tiles of 64 x 64, tile-major (chol_tile.h), the ragged last tiles padded with zeros (Wn: with the identity, as the cut pads).
+struct MapUpdateDev {
+  int32_t od, N, NA, nN, nA;
+  const uint32_t* map_idx;                                   // [N_A / od] the window's map objects
+  const double* map_mean; const double* map_cov;             // the old map: [N], [N][N]
+  const double* P; const double* pm;                         // the posterior: covariance [N_A][N_A] as given (not symmetrised), mean [N_A]
+  const double* Wt; const double* W; const double* mean_A;   // of the cut
+  double* Wn; double* Ps; double* U; double* M;              // [nA][nA] tiles: W, (P + P^T) / 2, W Ps, I - W Ps W^T
+  double* G; double* Y; double* Z;                           // [nN][nA] tiles: Cs[:, A], G W^T, Y M
+  double* v;                                                 // [64 nA]
+  double* out_mean; double* out_cov;                         // the new map
+  double* status;                                            // the cut's record: MS_NONFINITE is set to 1 by whoever writes a non-finite entry of the new map
+};
+// ten launches; status[MS_NONFINITE] must have been zeroed on the stream
+void launch_map_update(hipStream_t s, const MapUpdateDev& u);
+// the posterior of the handle form: the k x k blocks of launch_cov_pairs (pair a k + b: objects a, b) -> dense P, and the objects' current values -> pm
+void launch_map_posterior_layout(hipStream_t s, const double* blocks, const double* objects, const uint32_t* obj_idx, int32_t k, int32_t od, double* P, double* pm);
 
 struct ReducedDev {         // accumulators of the reduced system
   double* Hdiag;            // pose v: 36 doubles at 36 v; object w: od^2 doubles at 36 nPv + od^2 w (row-major, lower part used)

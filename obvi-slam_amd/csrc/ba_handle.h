@@ -5,6 +5,7 @@
 //   upload.cpp  obvi_ba_set_* (parameter blocks, factors, masks)
 //   plan.cpp    the symbolic phase: reduced program, elimination order, Schur work lists, tile plan (prepare_plan), mask-only re-plan
 //   lm.cpp      one LM step on the device (submit_step: assemble, factor, trial point, publish and wait) and the trust-region loop (obvi_ba_solve)
+//   map_resident.cpp, map_update.cpp   the device-resident map (struct obvi_map): group priors cut from it, and the map conditioned on a window's posterior
 #ifndef OBVI_BA_HANDLE_H_
 #define OBVI_BA_HANDLE_H_
 #include "../../include/obvi_ba.h"
@@ -190,6 +191,8 @@ struct obvi_ba_handle {
   DevBuf<int32_t> d_mgn_slab_ptr, d_mgn_slab_grp, d_mgn_tile_ptr, d_mgn_tile_grp, d_mgn_tile_ij;
   DevBuf<MapCutGroup> d_mc_groups; DevBuf<uint32_t> d_mc_map_idx;
   DevBuf<double> d_mc_A, d_mc_Li, d_mc_Wt, d_mc_Csym, d_mc_x, d_mc_partial, d_mc_status;
+  // obvi_map_condition* (map_update.cpp): the posterior as uploaded or laid out (covariance, then mean), the window's session objects, the tile operands of MapUpdateDev
+  DevBuf<double> d_mu_post, d_mu_tiles; DevBuf<uint32_t> d_mu_obj;
   DevBuf<double> d_bb_blk;                                    // per-factor blocks of the bounding-box factors (k_bbox_gather)
   DevBuf<double> d_sm_blk; DevBuf<uint32_t> d_smt_ptr, d_smt_idx;   // deterministic mode: the same for the priors and relative-pose factors (k_small_gather)
   int32_t bb_pairs_unique = 1;
@@ -296,6 +299,15 @@ struct obvi_ba_handle {
   double ck_ms[CK_COUNT] = {}; int64_t ck_launches[CK_COUNT] = {};
   double phase_ms[PH_COUNT] = {};
   int64_t phase_launches[PH_COUNT] = {};
+};
+
+// include/obvi_map_resident.h: a map on the device (map_resident.cpp creates and cuts, map_update.cpp reads and conditions)
+struct obvi_map {
+  int device = 0, od = 7;
+  int64_t n = 0;
+  double* d_mean = nullptr;   // [n][od]
+  double* d_cov = nullptr;    // [n od][n od]
+  double* d_x0 = nullptr;     // [kMapGroupMaxRows] the fixed start of the power iterations (map_group_weights, host_util.h)
 };
 
 namespace obvi_lib {
@@ -683,6 +695,14 @@ inline void record_end(obvi_ba_handle* h, int idx, hipStream_t on) { if (h->prof
 void prepare(obvi_ba_handle* h);
 void prepare_plan(obvi_ba_handle* h);
 bool prepare_masks(obvi_ba_handle* h);
+// ---- abi.cpp
+// What obvi_ba_object_covariances and obvi_map_condition_on_handle share, after prepare(): the undamped reduced system at the current point, factorised, and
+// Yt = (L^-1 E)^T of the variable objects' unit vectors in d_cov_Y ([*nrhs][*ldt]; *ldt = 0: nothing was solved -- no pairs, or no variable objects).
+// CovTables: the host tables the two stages upload; the caller keeps them until its wait for the stream (an upload that missed the staging arena reads them then).
+struct CovTables { std::vector<int32_t> slab_first, cols, first_row; };
+int object_cov_forward(obvi_ba_handle* h, int64_t n_pairs, const char* what, int64_t* ldt, CovTables& keep);
+// ... and the od x od blocks of the pairs (obj_a[i], obj_b[i]) from that Yt into d_cov_out, pair after pair; a pair with an object that is no variable: zeros
+void object_cov_pair_blocks(obvi_ba_handle* h, int64_t n_pairs, const uint32_t* obj_a, const uint32_t* obj_b, int64_t ldt, CovTables& keep);
 // ---- lm.cpp
 void submit_step(obvi_ba_handle* h, double radius, bool first_iter, bool solve, bool keep_factor = false);
 void assemble_step(obvi_ba_handle* h, double radius, bool first_iter, bool schur, bool exchange);

@@ -6,6 +6,8 @@
 //   Li : nt tiles, the inverses of the diagonal tiles of L
 //   Wt : tile (i, k), k <= i, holds (W_ik)^T -- the operand order tile_abt_mfma (C += A B^T) wants in stages 3 and 4
 // and Csym, the sub-block again as N rows of ld doubles (the layout of Lambda), for the power steps on C.
+// Second half of the file: a map conditioned on the posterior of a window's objects (include/obvi_map_update.h, MapUpdateDev): tile products on the factor of a
+// one-group cut, under the same rules.
 #include "chol_tile.h"
 
 namespace obvi {
@@ -323,9 +325,214 @@ __global__ void __launch_bounds__(64) k_map_power_finish(MapCutDev m) {
   }
 }
 
+// ==== the map conditioned on a window's posterior (include/obvi_map_update.h; MapUpdateDev, ba_device.h) ==================================================
+// Every kernel below writes tiles or rows that no other workgroup of its launch writes, reads only what earlier launches wrote, and sums in a fixed order.
+__device__ __forceinline__ int32_t window_map_row(const MapUpdateDev& u, int w) { return w < u.NA ? (int32_t)u.map_idx[w / u.od] * u.od + w % u.od : -1; }
+
+// (ti, tj, 0): Wn_ij = (Wt_ij)^T for j <= i, zero above;  (ti, tj, 1): Ps_ij = (P + P^T) / 2, zero in the padding
+__global__ void __launch_bounds__(kThreads) k_mu_operands(MapUpdateDev u) {
+  __shared__ double A[T * LDM];
+  const int ti = blockIdx.x, tj = blockIdx.y, tid = threadIdx.x;
+  if (blockIdx.z == 0) {
+    double* wn = tile_ptr(u.Wn, u.nA, ti, tj);
+    if (tj <= ti) stage_tile(A, tile_ptr(const_cast<double*>(u.Wt), u.nA, ti, tj));
+    __syncthreads();
+    for (int e = tid; e < T * T; e += kThreads) wn[e] = tj <= ti ? A[(e & 63) * LDM + (e >> 6)] : 0.0;
+    return;
+  }
+  double* ps = tile_ptr(u.Ps, u.nA, ti, tj);
+  for (int e = tid; e < T * T; e += kThreads) {
+    const int gi = T * ti + (e >> 6), gj = T * tj + (e & 63);
+    ps[e] = (gi < u.NA && gj < u.NA) ? 0.5 * (u.P[(int64_t)gi * u.NA + gj] + u.P[(int64_t)gj * u.NA + gi]) : 0.0;
+  }
+}
+
+// (ti, tj): G_ij = Cs[rows of tile row i][window columns of tile column j]; the two blocks of the map are read along their rows and meet in LDS, as in k_map_gather
+__global__ void __launch_bounds__(kThreads) k_mu_gather(MapUpdateDev u) {
+  __shared__ double P[T * LDM];
+  __shared__ double Q[T * LDM];
+  __shared__ int32_t cols[T];
+  const int ti = blockIdx.x, tj = blockIdx.y, tid = threadIdx.x;
+  if (tid < T) cols[tid] = window_map_row(u, T * tj + tid);
+  __syncthreads();
+  const int64_t ldc = u.N;
+  for (int e = tid; e < T * T; e += kThreads) {
+    const int a = e >> 6, b = e & 63;
+    const int gr = T * ti + a, gb = T * ti + b;
+    P[a * LDM + b] = (gr < u.N && cols[b] >= 0) ? u.map_cov[(int64_t)gr * ldc + cols[b]] : 0.0;   // C[row r_a][col A_b]
+    Q[a * LDM + b] = (cols[a] >= 0 && gb < u.N) ? u.map_cov[(int64_t)cols[a] * ldc + gb] : 0.0;   // C[row A_a][col r_b]
+  }
+  __syncthreads();
+  double* g = tile_ptr(u.G, u.nA, ti, tj);
+  for (int e = tid; e < T * T; e += kThreads) { const int r = e >> 6, c = e & 63; g[e] = 0.5 * (P[r * LDM + c] + Q[c * LDM + r]); }
+}
+
+// C_ij = sum_k A_ik B_jk^T over tiles; kmode 0: k < kn, 1: k <= j, 2: k <= i (the lower triangular W as B, as A).  sym: C = I - sum, the tiles j <= i computed
+// and mirrored, a diagonal tile from its lower triangle -- C is symmetric bit for bit.
+struct MuGemm { const double* A; const double* B; double* C; int32_t nt, kn, kmode, sym; };
+__global__ void __launch_bounds__(kThreads) k_mu_gemm(MuGemm g) {
+  __shared__ double A[T * LDM];
+  __shared__ double B[T * LDM];
+  const int i = blockIdx.x, j = blockIdx.y, tid = threadIdx.x;
+  if (g.sym && j > i) return;
+  const int k1 = g.kmode == 0 ? g.kn : (g.kmode == 1 ? j + 1 : i + 1);
+  f64x4 acc[4] = {};
+  for (int k = 0; k < k1; ++k) {
+    __syncthreads();
+    stage_tiles(A, tile_ptr(const_cast<double*>(g.A), g.nt, i, k), B, tile_ptr(const_cast<double*>(g.B), g.nt, j, k));
+    __syncthreads();
+    tile_abt_mfma(A, B, acc);
+  }
+  __syncthreads();
+  acc_to_lds(A, acc, g.sym ? -1.0 : 1.0);
+  __syncthreads();
+  double* c_ij = tile_ptr(g.C, g.nt, i, j);
+  double* c_ji = tile_ptr(g.C, g.nt, j, i);
+  for (int e = tid; e < T * T; e += kThreads) {
+    const int r = e >> 6, c = e & 63;
+    if (!g.sym) { c_ij[e] = A[r * LDM + c]; continue; }
+    if (i == j) c_ij[e] = (r == c ? 1.0 : 0.0) + (c > r ? A[c * LDM + r] : A[r * LDM + c]);
+    else { c_ij[e] = A[r * LDM + c]; c_ji[e] = A[c * LDM + r]; }
+  }
+}
+
+// The hot launch.  (ti, tj <= ti): C'_ij = Cs_ij - sum_k Z_ik Y_jk^T, k ascending; written along the rows of both triangles, a diagonal tile from its lower triangle.
+__global__ void __launch_bounds__(kThreads) k_mu_cov(MapUpdateDev u) {
+  __shared__ double A[T * LDM];
+  __shared__ double B[T * LDM];
+  const int ti = blockIdx.x, tj = blockIdx.y, tid = threadIdx.x;
+  if (tj > ti) return;
+  f64x4 acc[4] = {};
+  for (int k = 0; k < u.nA; ++k) {
+    __syncthreads();
+    stage_tiles(A, tile_ptr(u.Z, u.nA, ti, k), B, tile_ptr(u.Y, u.nA, tj, k));
+    __syncthreads();
+    tile_abt_mfma(A, B, acc);
+  }
+  __syncthreads();
+  const int N = u.N;
+  const int64_t ldc = N;
+  for (int e = tid; e < T * T; e += kThreads) {   // the old map's two blocks, each along its rows
+    const int a = e >> 6, b = e & 63;
+    const int ia = T * ti + a, jb = T * tj + b, ja = T * tj + a, ib = T * ti + b;
+    A[a * LDM + b] = (ia < N && jb < N) ? u.map_cov[(int64_t)ia * ldc + jb] : 0.0;
+    B[a * LDM + b] = (ja < N && ib < N) ? u.map_cov[(int64_t)ja * ldc + ib] : 0.0;
+  }
+  __syncthreads();
+  const int lane = tid & 63, wv = tid >> 6;
+  double v[4][4];
+#pragma unroll
+  for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = 16 * rt + (lane >> 4) + 4 * r, col = 16 * wv + (lane & 15);
+      v[rt][r] = 0.5 * (A[row * LDM + col] + B[col * LDM + row]) - acc[rt][r];
+    }
+  __syncthreads();
+#pragma unroll
+  for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) A[(16 * rt + (lane >> 4) + 4 * r) * LDM + 16 * wv + (lane & 15)] = v[rt][r];
+  __syncthreads();
+  bool bad = false;
+  for (int e = tid; e < T * T; e += kThreads) {
+    const int r = e >> 6, c = e & 63;
+    const int gi = T * ti + r, gj = T * tj + c;
+    if (gi < N && gj < N) {
+      const double x = (ti == tj && c > r) ? A[c * LDM + r] : A[r * LDM + c];
+      u.out_cov[(int64_t)gi * ldc + gj] = x;
+      bad = bad || !isfinite(x);
+    }
+    const int hj = T * tj + r, hi = T * ti + c;
+    if (ti != tj && hi < N && hj < N) u.out_cov[(int64_t)hj * ldc + hi] = A[c * LDM + r];
+  }
+  if (bad) u.status[MS_NONFINITE] = 1.0;
+}
+
+// v = W (m - mu_A): workgroup b its 64 rows, four threads per row, the dot product split by column mod 4
+__global__ void __launch_bounds__(kThreads) k_mu_v(MapUpdateDev u) {
+  const int row = T * blockIdx.x + (threadIdx.x >> 2), part = threadIdx.x & 3;
+  double s = 0.0;
+  if (row < u.NA) for (int c = part; c <= row; c += 4) s += u.W[(int64_t)row * u.NA + c] * (u.pm[c] - u.mean_A[c]);
+  s += __shfl_xor(s, 1, 64);
+  s += __shfl_xor(s, 2, 64);
+  if (part == 0) u.v[row] = s;
+}
+// mu' = mu + Y v: workgroup b its 64 map rows
+__global__ void __launch_bounds__(kThreads) k_mu_mean(MapUpdateDev u) {
+  const int r = threadIdx.x >> 2, part = threadIdx.x & 3, row = T * blockIdx.x + r;
+  double s = 0.0;
+  for (int k = 0; k < u.nA; ++k) {
+    const double* y = tile_ptr(u.Y, u.nA, blockIdx.x, k) + r * T;
+    for (int c = part; c < T; c += 4) s += y[c] * u.v[T * k + c];
+  }
+  s += __shfl_xor(s, 1, 64);
+  s += __shfl_xor(s, 2, 64);
+  if (part == 0 && row < u.N) {
+    const double x = u.map_mean[row] + s;
+    u.out_mean[row] = x;
+    if (!isfinite(x)) u.status[MS_NONFINITE] = 1.0;
+  }
+}
+// the window's own block and means: the posterior itself, bit for bit
+__global__ void __launch_bounds__(kThreads) k_mu_scatter(MapUpdateDev u) {
+  __shared__ int32_t rows[T], cols[T];
+  const int ti = blockIdx.x, tj = blockIdx.y, tid = threadIdx.x;
+  if (tid < 2 * T) (tid < T ? rows : cols)[tid & (T - 1)] = window_map_row(u, T * (tid < T ? ti : tj) + (tid & (T - 1)));
+  __syncthreads();
+  const double* ps = tile_ptr(u.Ps, u.nA, ti, tj);
+  bool bad = false;
+  for (int e = tid; e < T * T; e += kThreads) {
+    const int r = e >> 6, c = e & 63;
+    if (rows[r] < 0 || cols[c] < 0) continue;
+    const double x = ps[e];
+    u.out_cov[(int64_t)rows[r] * u.N + cols[c]] = x;
+    bad = bad || !isfinite(x);
+  }
+  if (tj == 0 && tid < T && rows[tid] >= 0) {
+    const double x = u.pm[T * ti + tid];
+    u.out_mean[rows[tid]] = x;
+    bad = bad || !isfinite(x);
+  }
+  if (bad) u.status[MS_NONFINITE] = 1.0;
+}
+
+// P[od a + r][od b + c] = blocks[a k + b][r][c], pm[od a + r] = objects[obj_idx[a]][r]
+__global__ void __launch_bounds__(kThreads) k_mu_posterior_layout(const double* __restrict__ blocks, const double* __restrict__ objects, const uint32_t* __restrict__ obj_idx,
+                                                                 int32_t k, int32_t od, double* __restrict__ P, double* __restrict__ pm) {
+  const int64_t NA = (int64_t)k * od, e = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (e >= NA * NA) return;
+  const int64_t i = e / NA, j = e % NA;
+  P[e] = blocks[((i / od) * k + j / od) * (od * od) + (i % od) * od + j % od];
+  if (j == 0) pm[i] = objects[(int64_t)obj_idx[i / od] * od + i % od];
+}
+
 }  // namespace
 
+void launch_map_update(hipStream_t s, const MapUpdateDev& u) {
+  const int nA = u.nA, nN = u.nN;
+  hipLaunchKernelGGL(k_mu_operands, dim3(nA, nA, 2), dim3(kThreads), 0, s, u);
+  hipLaunchKernelGGL(k_mu_gather, dim3(nN, nA), dim3(kThreads), 0, s, u);
+  hipLaunchKernelGGL(k_mu_gemm, dim3(nN, nA), dim3(kThreads), 0, s, MuGemm{u.G, u.Wn, u.Y, nA, nA, 1, 0});    // Y = G W^T
+  hipLaunchKernelGGL(k_mu_gemm, dim3(nA, nA), dim3(kThreads), 0, s, MuGemm{u.Wn, u.Ps, u.U, nA, nA, 2, 0});   // U = W Ps (Ps = Ps^T)
+  hipLaunchKernelGGL(k_mu_gemm, dim3(nA, nA), dim3(kThreads), 0, s, MuGemm{u.U, u.Wn, u.M, nA, nA, 1, 1});    // M = I - U W^T
+  hipLaunchKernelGGL(k_mu_gemm, dim3(nN, nA), dim3(kThreads), 0, s, MuGemm{u.Y, u.M, u.Z, nA, nA, 0, 0});     // Z = Y M (M = M^T)
+  hipLaunchKernelGGL(k_mu_cov, dim3(nN, nN), dim3(kThreads), 0, s, u);
+  hipLaunchKernelGGL(k_mu_v, dim3(nA), dim3(kThreads), 0, s, u);
+  hipLaunchKernelGGL(k_mu_mean, dim3(nN), dim3(kThreads), 0, s, u);
+  hipLaunchKernelGGL(k_mu_scatter, dim3(nA, nA), dim3(kThreads), 0, s, u);
+}
+void launch_map_posterior_layout(hipStream_t s, const double* blocks, const double* objects, const uint32_t* obj_idx, int32_t k, int32_t od, double* P, double* pm) {
+  const int64_t n = (int64_t)k * od * k * od;
+  hipLaunchKernelGGL(k_mu_posterior_layout, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, blocks, objects, obj_idx, k, od, P, pm);
+}
+
 void launch_map_cut(hipStream_t s, const MapCutDev& m, int nt_max, const double* map_mean, const double* map_cov, int64_t ldc, const double* x0) {
+  launch_map_factor(s, m, nt_max, map_mean, map_cov, ldc);
+  launch_map_condition_estimate(s, m, nt_max, x0);
+}
+
+void launch_map_factor(hipStream_t s, const MapCutDev& m, int nt_max, const double* map_mean, const double* map_cov, int64_t ldc) {
   if (m.n <= 0) return;
   const unsigned gz = (unsigned)std::min<int64_t>(m.n, 65535);
   hipLaunchKernelGGL(k_map_gather, dim3(nt_max, nt_max, gz), dim3(kThreads), 0, s, m, map_mean, map_cov, ldc);
@@ -336,6 +543,11 @@ void launch_map_cut(hipStream_t s, const MapCutDev& m, int nt_max, const double*
     hipLaunchKernelGGL(k_map_syrk, dim3(nt_max - k - 1, nt_max - k - 1, gz), dim3(kThreads), 0, s, m, k);
   }
   hipLaunchKernelGGL(k_map_winv, dim3(nt_max, gz), dim3(kThreads), 0, s, m);
+}
+
+void launch_map_condition_estimate(hipStream_t s, const MapCutDev& m, int nt_max, const double* x0) {
+  if (m.n <= 0) return;
+  const unsigned gz = (unsigned)std::min<int64_t>(m.n, 65535);
   hipLaunchKernelGGL(k_map_lambda, dim3(nt_max, nt_max, gz), dim3(kThreads), 0, s, m);
   const int nb = (std::min(nt_max * T, kMapGroupMaxRows) + kPowRows - 1) / kPowRows;
   for (int step = 0; step < kMapPowerSteps; ++step) hipLaunchKernelGGL(k_map_power, dim3(nb, gz, 2), dim3(kThreads), 0, s, m, x0, step);

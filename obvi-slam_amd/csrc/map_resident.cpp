@@ -4,14 +4,6 @@
 #include "ba_handle.h"
 #include "../../include/obvi_map_resident.h"
 
-struct obvi_map {
-  int device = 0, od = 7;
-  int64_t n = 0;
-  double* d_mean = nullptr;   // [n][od]
-  double* d_cov = nullptr;    // [n od][n od]
-  double* d_x0 = nullptr;     // [kMapGroupMaxRows] the fixed start of the power iterations (map_group_weights, host_util.h)
-};
-
 extern "C" {
 
 int obvi_map_create(int32_t device_id, int32_t object_block_size, int64_t n_objects, const double* mean, const double* cov, obvi_map** out) {

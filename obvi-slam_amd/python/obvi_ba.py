@@ -137,6 +137,48 @@ class Map:
         f.restype = C.c_int64
         return int(f(self._m))
 
+    # ---- the way back (include/obvi_map_update.h) ----
+    def _update_fn(self, name):
+        try:
+            f = getattr(self._lib, self._pre + name)
+        except AttributeError:
+            raise ObviError("%s%s: this library cannot read or condition a map (include/obvi_map_update.h is served by libobvi_ba.so only)" % (self._pre, name))
+        f.restype = C.c_int
+        return f
+
+    def _conditioned(self, ba, rc, new, what):
+        ba._check(rc, what)
+        m = Map.__new__(Map)
+        m._lib, m._pre, m._m, m.od = self._lib, self._pre, new, self.od
+        return m
+
+    def get(self):
+        """(mean [n][od], cov [n od][n od]) as the device holds them."""
+        n = self.n_objects
+        mean, cov = np.zeros((n, self.od)), np.zeros((n * self.od, n * self.od))
+        rc = self._update_fn("map_get")(self._m, _ptr(mean, C.c_double), _ptr(cov, C.c_double))
+        if rc != 0:
+            raise ObviError("%smap_get failed: status %d" % (self._pre, rc))
+        return mean, cov
+
+    def condition(self, ba, map_idx, post_mean, post_cov):
+        """A new Map: this one conditioned on the posterior N(post_mean [k][od], post_cov [k od][k od]) of its objects map_idx; `ba` lends its stream and workspaces."""
+        mid = np.ascontiguousarray(map_idx, dtype=np.uint32)
+        mu = _f64(post_mean, (len(mid), self.od))
+        cv = _f64(post_cov, (len(mid) * self.od, len(mid) * self.od))
+        new = C.c_void_p()
+        rc = self._update_fn("map_condition")(ba._h, self._m, C.c_int64(len(mid)), _ptr(mid, C.c_uint32), _ptr(mu, C.c_double), _ptr(cv, C.c_double), C.byref(new))
+        return self._conditioned(ba, rc, new, "map_condition")
+
+    def condition_on(self, ba, obj_idx, map_idx):
+        """A new Map: this one conditioned on the current estimates and joint covariance of `ba`'s objects obj_idx, which are the map objects map_idx."""
+        oid, mid = np.ascontiguousarray(obj_idx, dtype=np.uint32), np.ascontiguousarray(map_idx, dtype=np.uint32)
+        if len(oid) != len(mid):
+            raise ObviError("map_condition_on_handle: obj_idx and map_idx differ in length")
+        new = C.c_void_p()
+        rc = self._update_fn("map_condition_on_handle")(ba._h, self._m, C.c_int64(len(mid)), _ptr(oid, C.c_uint32), _ptr(mid, C.c_uint32), C.byref(new))
+        return self._conditioned(ba, rc, new, "map_condition_on_handle")
+
     def close(self):
         if self._m:
             f = getattr(self._lib, self._pre + "map_destroy")

@@ -3,7 +3,9 @@
 objects-only problem: median and range of five calls of obvi_map_set_group_priors (host pointers: blocked Cholesky, triangular inverse, W^T W and the power steps
 on the host's workers, then the upload) and of obvi_map_set_group_priors_from_map (the map already resident: gather, the same algebra and the condition estimate
 on the device, one read-back).  Each entry is called once before it is timed (its first call allocates).  obvi_map_create's time is printed beside them.
-usage (GPU box, repo root): python scripts/map_bench.py"""
+--update: the way back instead -- obvi_map_condition_on_handle and obvi_map_condition at 70, 210 and 1 400 window rows on the same 200-object
+map, against the round trip through the host that gives the same map without them.
+usage (GPU box, repo root): python scripts/map_bench.py [--update]"""
 import os
 import sys
 import time
@@ -63,5 +65,69 @@ def main():
     mp.close()
 
 
+def numpy_update(mean, cov, sel, m, P):
+    """The formulas of include/obvi_map_update.h on the host: what a session computes without the device entry."""
+    idx = np.concatenate([np.arange(OD * o, OD * o + OD) for o in sel])
+    Cs, Ps = 0.5 * (cov + cov.T), 0.5 * (P + P.T)
+    Caa = Cs[np.ix_(idx, idx)]
+    K = np.linalg.solve(Caa, Cs[idx]).T
+    mu = mean.ravel() + K @ (m.ravel() - mean.ravel()[idx])
+    Cn = Cs - K @ (Caa - Ps) @ K.T
+    Cn = 0.5 * (Cn + Cn.T)
+    Cn[np.ix_(idx, idx)] = Ps
+    mu[idx] = m.ravel()
+    return mu.reshape(-1, OD), Cn
+
+
+def update():
+    """a window's posterior folded back into the map.  Both device entries against the round trip a session needs without them: object_covariances
+    of the k^2 pairs, numpy_update on the host, obvi_map_create."""
+    rng = np.random.default_rng(1)
+    mean, cov = rng.normal(size=(N_MAP, OD)), spd(rng, N_MAP * OD)
+    mp = obvi_ba.Map.create(mean, cov, object_block_size=OD)
+    for k in (10, 30, 200):
+        sel = rng.permutation(N_MAP)[:k]
+        ba = obvi_ba.BundleAdjuster(object_block_size=OD)
+        ba.set_cameras(synth.K_DEFAULT[None], synth.EXT_DEFAULT[None])
+        ba.set_poses(np.zeros((1, 6)), np.ones(1, np.uint8))
+        ba.set_points(np.zeros((0, 3)), np.zeros(0, np.uint8))
+        ba.set_objects(mean[sel] + 0.05, np.zeros(k, np.uint8))
+        obj = np.arange(k)
+        ba.set_map_group_priors_from_map(mp, [list(obj)], [list(sel)], 1e6)
+        ba.set_ltm_priors(obj, mean[sel] + 0.02, np.tile((0.05 * np.eye(OD)).ravel(), (k, 1)), 1e6)      # what the window measured
+        ba.solve(obvi_ba.SolverParams(max_num_iterations=10, allow_non_monotonic_steps=True, function_tolerance=1e-6, initial_trust_region_radius=100.0,
+                                      max_trust_region_radius=1e4))
+        pa, pb = np.repeat(obj, k), np.tile(obj, k)
+
+        def posterior():
+            P = ba.object_covariances(pa, pb).reshape(k, k, OD, OD).transpose(0, 2, 1, 3).reshape(k * OD, k * OD)
+            return ba.get_objects(), P
+        m, P = posterior()
+        last = {}
+
+        def round_trip():
+            mm, PP = posterior()
+            mu, Cn = numpy_update(mean, cov, sel, mm, PP)
+            with obvi_ba.Map.create(mu, Cn, object_block_size=OD) as new:
+                last["host"] = (mu, Cn, new.n_objects)
+
+        def on_handle():
+            with mp.condition_on(ba, obj, sel) as new:
+                last["n"] = new.n_objects
+
+        def host_pointers():
+            with mp.condition(ba, sel, m, P) as new:
+                last["n"] = new.n_objects
+        base, b = timed(round_trip)
+        dev_on, d1 = timed(on_handle)
+        dev_hp, d2 = timed(host_pointers)
+        with mp.condition_on(ba, obj, sel) as new:
+            mu, Cn = new.get()
+        print("%5d window rows: round trip %s   condition_on_handle %s  (x %.1f)   condition %s  (x %.1f)   |C' - numpy's| / |C'| %.1e"
+              % (k * OD, base, dev_on, b / d1, dev_hp, b / d2, np.abs(Cn - last["host"][1]).max() / np.abs(Cn).max()))
+        ba.close()
+    mp.close()
+
+
 if __name__ == "__main__":
-    main()
+    update() if "--update" in sys.argv[1:] else main()
