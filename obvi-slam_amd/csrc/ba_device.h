@@ -198,6 +198,7 @@ struct MapGroupDev {
 // tile workspaces (A -> L and Wt: nt x nt tiles each) start at tile tile0, the inverses of its diagonal tiles at tile diag0; members [member0, member0 + N / od)
 // of map_idx; Lambda / Csym (N rows of ld doubles) at lam_off, W (N x N) at w_off -- the offsets of MapGroupDev.
 constexpr int kMapGroupMaxRows = 2048;   // OBVI_MAP_GROUP_MAX_ROWS
+constexpr int64_t kMapMaxRows = 11585;   // floor(sqrt(2^30 / 8)): rows of a map whose covariance takes 1 GiB, the largest a map may have
 constexpr int kMapPowerSteps = 40;       // power steps of the condition estimate, on C and on Lambda
 enum MapStatus { MS_BAD = 0, MS_PIV_MIN, MS_PIV_MAX, MS_EV_C, MS_EV_LAMBDA, MS_NONFINITE, kMapStatusDoubles = 8 };   // one record per group, read back once per call (MS_NONFINITE: the map update's alone)
 struct MapCutGroup { int32_t N, nt, ld, pad; int64_t tile0, diag0, member0, lam_off, w_off; };
@@ -220,8 +221,12 @@ void launch_map_condition_estimate(hipStream_t s, const MapCutDev& m, int nt_max
 // Z = Y (I - W Ps W^T), v = W (m - mu_A), W = L^-1 of Cs_AA = L L^T -- the factor of a one-group cut of the window's objects A, which ran before on the stream and
 // left Wt (its tiles of W^T), W (dense, N_A x N_A), mean_A and the status record.  N map rows in nN tile rows, N_A window rows in nA; every tile operand is
 // [tile rows][nA] tiles of 64 x 64, tile-major (chol_tile.h), the ragged last tiles padded with zeros (Wn: with the identity, as the cut pads).
+// The same launches grow the map (include/obvi_map_extend.h): the window also held N_B rows of objects B the map lacks, the posterior is over (A, B) with the
+// leading dimension ldp = N_A + N_B, and the new map has ldo = N + N_B rows, B behind the old ones: C'[old, B] = Y V^T with V = Ps_BA W^T.  A map that is only
+// conditioned has N_B = 0, ldp = N_A, ldo = N.
 struct MapUpdateDev {
   int32_t od, N, NA, nN, nA;
+  int32_t NB, nB, ldp, ldo;                                  // rows of B in nB tile rows; leading dimensions of P and of out_cov
   const uint32_t* map_idx;                                   // [N_A / od] the window's map objects
   const double* map_mean; const double* map_cov;             // the old map: [N], [N][N]
   const double* P; const double* pm;                         // the posterior: covariance [N_A][N_A] as given (not symmetrised), mean [N_A]
@@ -229,11 +234,18 @@ struct MapUpdateDev {
   double* Wn; double* Ps; double* U; double* M;              // [nA][nA] tiles: W, (P + P^T) / 2, W Ps, I - W Ps W^T
   double* G; double* Y; double* Z;                           // [nN][nA] tiles: Cs[:, A], G W^T, Y M
   double* v;                                                 // [64 nA]
-  double* out_mean; double* out_cov;                         // the new map
+  double* Pba; double* V;                                    // [nB][nA] tiles: Ps_BA, Ps_BA W^T (a map that grows)
+  double* out_mean; double* out_cov;                         // the new map: [ldo], [ldo][ldo]
   double* status;                                            // the cut's record: MS_NONFINITE is set to 1 by whoever writes a non-finite entry of the new map
 };
 // ten launches; status[MS_NONFINITE] must have been zeroed on the stream
 void launch_map_update(hipStream_t s, const MapUpdateDev& u);
+// The map grown by B: the update's launches into the larger map, then Ps_BA staged, V, the cross block Y V^T along the rows of both of its copies, and the
+// window's whole (A, B) block and means scattered last.  N_A = 0: the old block is symmetrised and copied (out_cov's cross blocks must have been zeroed on the
+// stream); N = 0 too: the scatter alone.  No grid has a zero dimension.  status[MS_NONFINITE] must have been zeroed on the stream.
+void launch_map_extend(hipStream_t s, const MapUpdateDev& u);
+// out[i][j] = cov[rows(i)][rows(j)], out_mean[i] = mean[rows(i)] for the k objects idx of a map of ldc rows: a copy, nothing is symmetrised
+void launch_map_select(hipStream_t s, const uint32_t* idx, int32_t k, int32_t od, const double* mean, const double* cov, int64_t ldc, double* out_mean, double* out_cov);
 // the posterior of the handle form: the k x k blocks of launch_cov_pairs (pair a k + b: objects a, b) -> dense P, and the objects' current values -> pm
 void launch_map_posterior_layout(hipStream_t s, const double* blocks, const double* objects, const uint32_t* obj_idx, int32_t k, int32_t od, double* P, double* pm);
 

@@ -5,7 +5,8 @@
 //   upload.cpp  obvi_ba_set_* (parameter blocks, factors, masks)
 //   plan.cpp    the symbolic phase: reduced program, elimination order, Schur work lists, tile plan (prepare_plan), mask-only re-plan
 //   lm.cpp      one LM step on the device (submit_step: assemble, factor, trial point, publish and wait) and the trust-region loop (obvi_ba_solve)
-//   map_resident.cpp, map_update.cpp   the device-resident map (struct obvi_map): group priors cut from it, and the map conditioned on a window's posterior
+//   map_resident.cpp, map_update.cpp, map_extend.cpp   the device-resident map (struct obvi_map): group priors cut from it, the map conditioned on a window's
+//                      posterior, and the map grown by a window's new objects or gathered (what the last two share: map_window.h)
 #ifndef OBVI_BA_HANDLE_H_
 #define OBVI_BA_HANDLE_H_
 #include "../../include/obvi_ba.h"
@@ -191,7 +192,7 @@ struct obvi_ba_handle {
   DevBuf<int32_t> d_mgn_slab_ptr, d_mgn_slab_grp, d_mgn_tile_ptr, d_mgn_tile_grp, d_mgn_tile_ij;
   DevBuf<MapCutGroup> d_mc_groups; DevBuf<uint32_t> d_mc_map_idx;
   DevBuf<double> d_mc_A, d_mc_Li, d_mc_Wt, d_mc_Csym, d_mc_x, d_mc_partial, d_mc_status;
-  // obvi_map_condition* (map_update.cpp): the posterior as uploaded or laid out (covariance, then mean), the window's session objects, the tile operands of MapUpdateDev
+  // obvi_map_condition* / obvi_map_extend* (map_update.cpp, map_extend.cpp): the posterior as uploaded or laid out (covariance, then mean), the window's session objects, the tile operands of MapUpdateDev
   DevBuf<double> d_mu_post, d_mu_tiles; DevBuf<uint32_t> d_mu_obj;
   DevBuf<double> d_bb_blk;                                    // per-factor blocks of the bounding-box factors (k_bbox_gather)
   DevBuf<double> d_sm_blk; DevBuf<uint32_t> d_smt_ptr, d_smt_idx;   // deterministic mode: the same for the priors and relative-pose factors (k_small_gather)
@@ -301,7 +302,7 @@ struct obvi_ba_handle {
   int64_t phase_launches[PH_COUNT] = {};
 };
 
-// include/obvi_map_resident.h: a map on the device (map_resident.cpp creates and cuts, map_update.cpp reads and conditions)
+// include/obvi_map_resident.h: a map on the device (map_resident.cpp creates and cuts, map_update.cpp reads and conditions, map_extend.cpp grows and gathers)
 struct obvi_map {
   int device = 0, od = 7;
   int64_t n = 0;

@@ -7,7 +7,8 @@
 //   Wt : tile (i, k), k <= i, holds (W_ik)^T -- the operand order tile_abt_mfma (C += A B^T) wants in stages 3 and 4
 // and Csym, the sub-block again as N rows of ld doubles (the layout of Lambda), for the power steps on C.
 // Second half of the file: a map conditioned on the posterior of a window's objects (include/obvi_map_update.h, MapUpdateDev): tile products on the factor of a
-// one-group cut, under the same rules.
+// one-group cut, under the same rules.  Third part: the map grown by the window's new objects, born from a posterior, or gathered down to some of its objects
+// (include/obvi_map_extend.h): the same launches into a larger map, the cross block, and the scatter of the window's whole block.
 #include "chol_tile.h"
 
 namespace obvi {
@@ -343,7 +344,7 @@ __global__ void __launch_bounds__(kThreads) k_mu_operands(MapUpdateDev u) {
   double* ps = tile_ptr(u.Ps, u.nA, ti, tj);
   for (int e = tid; e < T * T; e += kThreads) {
     const int gi = T * ti + (e >> 6), gj = T * tj + (e & 63);
-    ps[e] = (gi < u.NA && gj < u.NA) ? 0.5 * (u.P[(int64_t)gi * u.NA + gj] + u.P[(int64_t)gj * u.NA + gi]) : 0.0;
+    ps[e] = (gi < u.NA && gj < u.NA) ? 0.5 * (u.P[(int64_t)gi * u.ldp + gj] + u.P[(int64_t)gj * u.ldp + gi]) : 0.0;
   }
 }
 
@@ -411,7 +412,7 @@ __global__ void __launch_bounds__(kThreads) k_mu_cov(MapUpdateDev u) {
   }
   __syncthreads();
   const int N = u.N;
-  const int64_t ldc = N;
+  const int64_t ldc = N, ldo = u.ldo;
   for (int e = tid; e < T * T; e += kThreads) {   // the old map's two blocks, each along its rows
     const int a = e >> 6, b = e & 63;
     const int ia = T * ti + a, jb = T * tj + b, ja = T * tj + a, ib = T * ti + b;
@@ -440,11 +441,11 @@ __global__ void __launch_bounds__(kThreads) k_mu_cov(MapUpdateDev u) {
     const int gi = T * ti + r, gj = T * tj + c;
     if (gi < N && gj < N) {
       const double x = (ti == tj && c > r) ? A[c * LDM + r] : A[r * LDM + c];
-      u.out_cov[(int64_t)gi * ldc + gj] = x;
+      u.out_cov[(int64_t)gi * ldo + gj] = x;
       bad = bad || !isfinite(x);
     }
     const int hj = T * tj + r, hi = T * ti + c;
-    if (ti != tj && hi < N && hj < N) u.out_cov[(int64_t)hj * ldc + hi] = A[c * LDM + r];
+    if (ti != tj && hi < N && hj < N) u.out_cov[(int64_t)hj * ldo + hi] = A[c * LDM + r];
   }
   if (bad) u.status[MS_NONFINITE] = 1.0;
 }
@@ -486,7 +487,7 @@ __global__ void __launch_bounds__(kThreads) k_mu_scatter(MapUpdateDev u) {
     const int r = e >> 6, c = e & 63;
     if (rows[r] < 0 || cols[c] < 0) continue;
     const double x = ps[e];
-    u.out_cov[(int64_t)rows[r] * u.N + cols[c]] = x;
+    u.out_cov[(int64_t)rows[r] * u.ldo + cols[c]] = x;
     bad = bad || !isfinite(x);
   }
   if (tj == 0 && tid < T && rows[tid] >= 0) {
@@ -507,6 +508,109 @@ __global__ void __launch_bounds__(kThreads) k_mu_posterior_layout(const double* 
   if (j == 0) pm[i] = objects[(int64_t)obj_idx[i / od] * od + i % od];
 }
 
+// ==== the map grown by a window's new objects (include/obvi_map_extend.h) ===================================================================================
+// row of the new map of row w of the posterior over (A, B): A keeps its map rows, B follows the old map
+__device__ __forceinline__ int32_t window_new_row(const MapUpdateDev& u, int w) { return w < u.NA ? window_map_row(u, w) : (w < u.NA + u.NB ? u.N + (w - u.NA) : -1); }
+
+// (bi, aj): Pba_ij = Ps[B rows of tile row i][A columns of tile column j], zero in the padding; the two blocks of P are read along their rows and meet in LDS
+__global__ void __launch_bounds__(kThreads) k_mx_stage(MapUpdateDev u) {
+  __shared__ double P[T * LDM];
+  __shared__ double Q[T * LDM];
+  const int ti = blockIdx.x, tj = blockIdx.y, tid = threadIdx.x;
+  const int64_t ld = u.ldp;
+  for (int e = tid; e < T * T; e += kThreads) {
+    const int a = e >> 6, b = e & 63;
+    const int bi = T * ti + a, aj = T * tj + b, ai = T * tj + a, bj = T * ti + b;
+    P[a * LDM + b] = (bi < u.NB && aj < u.NA) ? u.P[(int64_t)(u.NA + bi) * ld + aj] : 0.0;   // P[B row a][A col b]
+    Q[a * LDM + b] = (ai < u.NA && bj < u.NB) ? u.P[(int64_t)ai * ld + u.NA + bj] : 0.0;     // P[A row a][B col b]
+  }
+  __syncthreads();
+  double* t = tile_ptr(u.Pba, u.nA, ti, tj);
+  for (int e = tid; e < T * T; e += kThreads) { const int r = e >> 6, c = e & 63; t[e] = 0.5 * (Q[c * LDM + r] + P[r * LDM + c]); }
+}
+
+// (ti, tj): X_ij = sum_k Y_ik V_jk^T, k ascending -- rows of tile row i of the old map against the B rows of tile row j; written along the rows of both
+// C'[old, B] and C'[B, old]
+__global__ void __launch_bounds__(kThreads) k_mx_cross(MapUpdateDev u) {
+  __shared__ double A[T * LDM];
+  __shared__ double B[T * LDM];
+  const int ti = blockIdx.x, tj = blockIdx.y, tid = threadIdx.x;
+  f64x4 acc[4] = {};
+  for (int k = 0; k < u.nA; ++k) {
+    __syncthreads();
+    stage_tiles(A, tile_ptr(u.Y, u.nA, ti, k), B, tile_ptr(u.V, u.nA, tj, k));
+    __syncthreads();
+    tile_abt_mfma(A, B, acc);
+  }
+  __syncthreads();
+  acc_to_lds(A, acc, 1.0);
+  __syncthreads();
+  const int N = u.N, NB = u.NB;
+  const int64_t ldo = u.ldo;
+  bool bad = false;
+  for (int e = tid; e < T * T; e += kThreads) {
+    const int r = e >> 6, c = e & 63;
+    const int gi = T * ti + r, gj = T * tj + c;
+    if (gi < N && gj < NB) {
+      const double x = A[r * LDM + c];
+      u.out_cov[(int64_t)gi * ldo + N + gj] = x;
+      bad = bad || !isfinite(x);
+    }
+    const int hj = T * tj + r, hi = T * ti + c;
+    if (hj < NB && hi < N) u.out_cov[(int64_t)(N + hj) * ldo + hi] = A[c * LDM + r];
+  }
+  if (bad) u.status[MS_NONFINITE] = 1.0;
+}
+
+// (ti, tj) over the tiles of the posterior: the window's whole block of the new map and its means are the posterior itself, (P + P^T) / 2 and pm bit for bit
+__global__ void __launch_bounds__(kThreads) k_mx_scatter(MapUpdateDev u) {
+  __shared__ double P[T * LDM];
+  __shared__ double Q[T * LDM];
+  __shared__ int32_t rows[T], cols[T];
+  const int ti = blockIdx.x, tj = blockIdx.y, tid = threadIdx.x;
+  if (tid < 2 * T) (tid < T ? rows : cols)[tid & (T - 1)] = window_new_row(u, T * (tid < T ? ti : tj) + (tid & (T - 1)));
+  const int NP = u.NA + u.NB;
+  const int64_t ld = u.ldp;
+  for (int e = tid; e < T * T; e += kThreads) {
+    const int a = e >> 6, b = e & 63;
+    const int ia = T * ti + a, jb = T * tj + b, ja = T * tj + a, ib = T * ti + b;
+    P[a * LDM + b] = (ia < NP && jb < NP) ? u.P[(int64_t)ia * ld + jb] : 0.0;
+    Q[a * LDM + b] = (ja < NP && ib < NP) ? u.P[(int64_t)ja * ld + ib] : 0.0;
+  }
+  __syncthreads();
+  bool bad = false;
+  for (int e = tid; e < T * T; e += kThreads) {
+    const int r = e >> 6, c = e & 63;
+    if (rows[r] < 0 || cols[c] < 0) continue;
+    const double x = 0.5 * (P[r * LDM + c] + Q[c * LDM + r]);
+    u.out_cov[(int64_t)rows[r] * u.ldo + cols[c]] = x;
+    bad = bad || !isfinite(x);
+  }
+  if (tj == 0 && tid < T && rows[tid] >= 0) {
+    const double x = u.pm[T * ti + tid];
+    u.out_mean[rows[tid]] = x;
+    bad = bad || !isfinite(x);
+  }
+  if (bad) u.status[MS_NONFINITE] = 1.0;
+}
+
+// the objects idx of a map, in that order: workgroup (64 columns, 64 rows) copies its entries as they are
+__global__ void __launch_bounds__(kThreads) k_map_select(const uint32_t* __restrict__ idx, int32_t k, int32_t od, const double* __restrict__ mean, const double* __restrict__ cov,
+                                                         int64_t ldc, double* __restrict__ out_mean, double* __restrict__ out_cov) {
+  __shared__ int64_t rows[T], cols[T];
+  const int tid = threadIdx.x, K = k * od;
+  if (tid < 2 * T) {
+    const int g = T * (tid < T ? blockIdx.y : blockIdx.x) + (tid & (T - 1));
+    (tid < T ? rows : cols)[tid & (T - 1)] = g < K ? (int64_t)idx[g / od] * od + g % od : -1;
+  }
+  __syncthreads();
+  for (int e = tid; e < T * T; e += kThreads) {
+    const int r = e >> 6, c = e & 63;
+    if (rows[r] >= 0 && cols[c] >= 0) out_cov[(int64_t)(T * blockIdx.y + r) * K + T * blockIdx.x + c] = cov[rows[r] * ldc + cols[c]];
+  }
+  if (blockIdx.x == 0 && tid < T && rows[tid] >= 0) out_mean[T * blockIdx.y + tid] = mean[rows[tid]];
+}
+
 }  // namespace
 
 void launch_map_update(hipStream_t s, const MapUpdateDev& u) {
@@ -521,6 +625,30 @@ void launch_map_update(hipStream_t s, const MapUpdateDev& u) {
   hipLaunchKernelGGL(k_mu_v, dim3(nA), dim3(kThreads), 0, s, u);
   hipLaunchKernelGGL(k_mu_mean, dim3(nN), dim3(kThreads), 0, s, u);
   hipLaunchKernelGGL(k_mu_scatter, dim3(nA, nA), dim3(kThreads), 0, s, u);
+}
+void launch_map_extend(hipStream_t s, const MapUpdateDev& u) {
+  const int nA = u.nA, nN = u.nN, nB = u.nB, nP = (u.NA + u.NB + T - 1) / T;
+  if (nA > 0) {
+    hipLaunchKernelGGL(k_mu_operands, dim3(nA, nA, 2), dim3(kThreads), 0, s, u);
+    hipLaunchKernelGGL(k_mu_gather, dim3(nN, nA), dim3(kThreads), 0, s, u);
+    hipLaunchKernelGGL(k_mu_gemm, dim3(nN, nA), dim3(kThreads), 0, s, MuGemm{u.G, u.Wn, u.Y, nA, nA, 1, 0});    // Y = G W^T
+    hipLaunchKernelGGL(k_mu_gemm, dim3(nA, nA), dim3(kThreads), 0, s, MuGemm{u.Wn, u.Ps, u.U, nA, nA, 2, 0});   // U = W Ps_AA
+    hipLaunchKernelGGL(k_mu_gemm, dim3(nA, nA), dim3(kThreads), 0, s, MuGemm{u.U, u.Wn, u.M, nA, nA, 1, 1});    // M = I - U W^T
+    hipLaunchKernelGGL(k_mu_gemm, dim3(nN, nA), dim3(kThreads), 0, s, MuGemm{u.Y, u.M, u.Z, nA, nA, 0, 0});     // Z = Y M
+    hipLaunchKernelGGL(k_mx_stage, dim3(nB, nA), dim3(kThreads), 0, s, u);
+    hipLaunchKernelGGL(k_mu_gemm, dim3(nB, nA), dim3(kThreads), 0, s, MuGemm{u.Pba, u.Wn, u.V, nA, nA, 1, 0});  // V = Ps_BA W^T
+    hipLaunchKernelGGL(k_mu_v, dim3(nA), dim3(kThreads), 0, s, u);
+  }
+  if (nN > 0) {   // with no window rows in the map both sums are empty: the old block symmetrised, the old means copied
+    hipLaunchKernelGGL(k_mu_cov, dim3(nN, nN), dim3(kThreads), 0, s, u);
+    hipLaunchKernelGGL(k_mu_mean, dim3(nN), dim3(kThreads), 0, s, u);
+  }
+  if (nA > 0) hipLaunchKernelGGL(k_mx_cross, dim3(nN, nB), dim3(kThreads), 0, s, u);
+  hipLaunchKernelGGL(k_mx_scatter, dim3(nP, nP), dim3(kThreads), 0, s, u);   // last: the A rows of the cross block give way to Ps_AB
+}
+void launch_map_select(hipStream_t s, const uint32_t* idx, int32_t k, int32_t od, const double* mean, const double* cov, int64_t ldc, double* out_mean, double* out_cov) {
+  const unsigned nt = (unsigned)(((int64_t)k * od + T - 1) / T);
+  hipLaunchKernelGGL(k_map_select, dim3(nt, nt), dim3(kThreads), 0, s, idx, k, od, mean, cov, ldc, out_mean, out_cov);
 }
 void launch_map_posterior_layout(hipStream_t s, const double* blocks, const double* objects, const uint32_t* obj_idx, int32_t k, int32_t od, double* P, double* pm) {
   const int64_t n = (int64_t)k * od * k * od;

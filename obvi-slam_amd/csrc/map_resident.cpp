@@ -1,7 +1,7 @@
 // map_resident.cpp -- include/obvi_map_resident.h: a map kept on the device, and group priors cut from it and factored there (map_kernels.hip).
 // The host checks every index, lays the groups out as obvi_map_set_group_priors does (upload.cpp), launches, reads one status record per group back, and swaps
 // the buffers the call built into the handle only when no group was refused.
-#include "ba_handle.h"
+#include "map_window.h"
 #include "../../include/obvi_map_resident.h"
 
 extern "C" {
@@ -11,8 +11,7 @@ int obvi_map_create(int32_t device_id, int32_t object_block_size, int64_t n_obje
   *out = nullptr;
   if (!mean || !cov || n_objects < 1 || (object_block_size != 0 && object_block_size != 7 && object_block_size != 9)) return OBVI_ERR_INVALID_ARGUMENT;
   const int od = object_block_size == 9 ? 9 : 7;
-  constexpr int64_t kMaxRows = 11585;   // floor(sqrt(2^30 / 8)): rows of a covariance of 1 GiB
-  if (n_objects > kMaxRows / od) return OBVI_ERR_INVALID_ARGUMENT;
+  if (n_objects > kMapMaxRows / od) return OBVI_ERR_INVALID_ARGUMENT;
   const int64_t rows = n_objects * od;
   for (int64_t k = 0; k < rows; ++k) if (!std::isfinite(mean[k])) return OBVI_ERR_NUMERICAL;
   for (int64_t k = 0; k < rows * rows; ++k) if (!std::isfinite(cov[k])) return OBVI_ERR_NUMERICAL;
@@ -21,9 +20,7 @@ int obvi_map_create(int32_t device_id, int32_t object_block_size, int64_t n_obje
   obvi_map* m = new (std::nothrow) obvi_map();
   if (!m) return OBVI_ERR_HIP;
   m->device = device_id; m->od = od; m->n = n_objects;
-  std::vector<double> x0((size_t)kMapGroupMaxRows);
-  uint64_t lcg = 0x9e3779b97f4a7c15ull;
-  for (double& v : x0) { lcg = lcg * 6364136223846793005ull + 1442695040888963407ull; v = 0.5 + (double)(lcg >> 11) / 9007199254740992.0; }
+  const std::vector<double> x0 = map_power_start();
   const bool ok = hipSetDevice(device_id) == hipSuccess
                && hipMalloc(reinterpret_cast<void**>(&m->d_mean), sizeof(double) * rows) == hipSuccess
                && hipMalloc(reinterpret_cast<void**>(&m->d_cov), sizeof(double) * rows * rows) == hipSuccess

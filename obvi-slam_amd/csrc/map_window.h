@@ -1,0 +1,123 @@
+// map_window.h -- what the entries that bring a window back into a device-resident map share (map_update.cpp: the map conditioned; map_extend.cpp: the map
+// grown or gathered): the checks of the window's map objects, the one-group cut of those objects in the handle's scratch buffers, the device view of the update,
+// the test of the cut's status record, and the start vector a map is given at birth (map_resident.cpp).
+#ifndef OBVI_MAP_WINDOW_H_
+#define OBVI_MAP_WINDOW_H_
+#include "ba_handle.h"
+#include "../../include/obvi_map_resident.h"
+
+#include <memory>
+
+namespace obvi_lib {
+
+struct MapDeleter { void operator()(obvi_map* m) const { obvi_map_destroy(m); } };
+
+// the fixed start of the power iterations, [kMapGroupMaxRows]: every map is born with the same one
+inline std::vector<double> map_power_start() {
+  std::vector<double> x0((size_t)kMapGroupMaxRows);
+  uint64_t lcg = 0x9e3779b97f4a7c15ull;
+  for (double& v : x0) { lcg = lcg * 6364136223846793005ull + 1442695040888963407ull; v = 0.5 + (double)(lcg >> 11) / 9007199254740992.0; }
+  return x0;
+}
+
+inline bool twice(const uint32_t* idx, int64_t k) {
+  std::vector<uint32_t> sorted(idx, idx + k);
+  std::sort(sorted.begin(), sorted.end());
+  return std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end();
+}
+
+// what every entry refuses about the map and the window's map objects, before anything is launched or allocated; rows: the window's rows that count against
+// OBVI_MAP_GROUP_MAX_ROWS (a gather has none: 0)
+inline int check_window(obvi_ba_handle* h, const obvi_map* map, int64_t k, const uint32_t* map_idx, int64_t rows, const std::string& what) {
+  if (map->device != h->device) return fail(h, OBVI_ERR_INVALID_ARGUMENT, what + ": the map lives on another device than the handle");
+  if (map->od != h->od) return fail(h, OBVI_ERR_INVALID_ARGUMENT, what + ": the map's object block size is not the handle's");
+  if (rows > OBVI_MAP_GROUP_MAX_ROWS) return fail(h, OBVI_ERR_INVALID_ARGUMENT, what + ": a window of more than OBVI_MAP_GROUP_MAX_ROWS rows");
+  for (int64_t i = 0; i < k; ++i) if ((int64_t)map_idx[i] >= map->n) return fail(h, OBVI_ERR_OUT_OF_RANGE, what + ": map index out of range");
+  if (twice(map_idx, k)) return fail(h, OBVI_ERR_INVALID_ARGUMENT, what + ": a map object twice");
+  return OBVI_OK;
+}
+
+// what the handle forms refuse about the window's session objects before anything is planned
+inline int check_session_objects(obvi_ba_handle* h, int64_t k, const uint32_t* obj_idx, const std::string& what) {
+  for (int64_t i = 0; i < k; ++i) if ((int64_t)obj_idx[i] >= h->O) return fail(h, OBVI_ERR_OUT_OF_RANGE, what + ": object index out of range");
+  if (twice(obj_idx, k)) return fail(h, OBVI_ERR_INVALID_ARGUMENT, what + ": a session object twice");
+  for (int64_t i = 0; i < k; ++i) if (h->h_object_const[obj_idx[i]]) return fail(h, OBVI_ERR_INVALID_ARGUMENT, what + ": a constant object has no posterior");
+  // the flags, not the plan's list: a handle that has not planned yet exchanges as soon as it does (validate_indices refuses group priors by the same test)
+  if (h->allreduce != nullptr && std::any_of(h->h_is_shared.begin(), h->h_is_shared.end(), [](uint8_t v) { return v != 0; })) return fail(h, OBVI_ERR_INVALID_ARGUMENT, what + ": the handle exchanges shared objects");
+  return OBVI_OK;
+}
+
+// The posterior of the handle forms, after the checks above and check_ready: the joint covariance of the session objects obj_idx, all k x k pairs, and their
+// current estimates, laid out in d_mu_post (covariance [k od][k od], then mean [k od]) on the handle's stream.  keep: the host tables the stages upload, alive
+// until the caller's wait, as obj_idx is.
+struct WindowPosterior { CovTables tables; std::vector<uint32_t> pa, pb; };
+inline int posterior_from_handle(obvi_ba_handle* h, int64_t k, const uint32_t* obj_idx, const std::string& what, WindowPosterior& keep) {
+  { const int vrc = validate_indices(h); if (vrc != OBVI_OK) return vrc; }
+  prepare(h);
+  for (int64_t i = 0; i < k; ++i) if (h->h_obj_vid[obj_idx[i]] < 0) return fail(h, OBVI_ERR_INVALID_ARGUMENT, what + ": an object that no active factor touches has no posterior");
+  CovTables& tables = keep.tables;
+  std::vector<uint32_t>& pa = keep.pa; std::vector<uint32_t>& pb = keep.pb;
+  pa.resize((size_t)(k * k)); pb.resize((size_t)(k * k));
+  for (int64_t a = 0; a < k; ++a) for (int64_t b = 0; b < k; ++b) { pa[(size_t)(a * k + b)] = obj_idx[a]; pb[(size_t)(a * k + b)] = obj_idx[b]; }
+  int64_t ldt = 0;
+  { const int rc = object_cov_forward(h, k * k, what.c_str(), &ldt, tables); if (rc != OBVI_OK) return rc; }
+  if (ldt == 0) return fail(h, OBVI_ERR_INVALID_ARGUMENT, what + ": the handle has no variable objects");
+  object_cov_pair_blocks(h, k * k, pa.data(), pb.data(), ldt, tables);
+  const int64_t NP = k * h->od;
+  h->d_mu_obj.upload(obj_idx, (size_t)k, h->stream);
+  h->d_mu_post.resize((size_t)(NP * NP + NP));
+  launch_map_posterior_layout(h->stream, h->d_cov_out.get(), h->d_obj.get(), h->d_mu_obj.get(), (int32_t)k, h->od, h->d_mu_post.get(), h->d_mu_post.get() + NP * NP);
+  return OBVI_OK;
+}
+
+// The window's k map objects as one group of a cut (MapCutDev, ba_device.h) in the handle's scratch buffers of obvi_map_set_group_priors_from_map -- the handle's
+// own groups are not touched -- with the status record zeroed.  k = 0: the status record alone.
+inline MapCutDev window_cut(obvi_ba_handle* h, int64_t k, const uint32_t* map_idx) {
+  const int od = h->od;
+  const int64_t NA = k * od, nA = map_group_slabs(NA), ld = (NA + 1) & ~(int64_t)1, tile = (int64_t)kTile * kTile;
+  hipStream_t s = h->stream;
+  h->d_mc_status.resize((size_t)kMapStatusDoubles);
+  h->d_mc_status.zero(s);
+  MapCutDev m{};
+  m.n = k > 0 ? 1 : 0; m.od = od; m.rows = NA; m.status = h->d_mc_status.get();
+  if (k == 0) return m;
+  const std::vector<MapCutGroup> cut{MapCutGroup{(int32_t)NA, (int32_t)nA, (int32_t)ld, 0, 0, 0, 0, 0, 0}};
+  h->d_mc_groups.upload(cut, s); h->d_mc_map_idx.upload(map_idx, (size_t)k, s);
+  h->d_mgn_mean.resize((size_t)NA); h->d_mgn_Lambda.resize((size_t)(NA * ld)); h->d_mgn_W.resize((size_t)(NA * NA));
+  h->d_mc_A.resize((size_t)(nA * nA * tile)); h->d_mc_Wt.resize((size_t)(nA * nA * tile)); h->d_mc_Li.resize((size_t)(nA * tile));
+  h->d_mc_Csym.resize((size_t)(NA * ld)); h->d_mc_x.resize((size_t)(4 * NA)); h->d_mc_partial.resize((size_t)2 * (kMapGroupMaxRows / 16));
+  h->d_mgn_W.zero(s); h->d_mgn_Lambda.zero(s);
+  m.groups = h->d_mc_groups.get(); m.map_idx = h->d_mc_map_idx.get();
+  m.A = h->d_mc_A.get(); m.Li = h->d_mc_Li.get(); m.Wt = h->d_mc_Wt.get(); m.Csym = h->d_mc_Csym.get();
+  m.mean = h->d_mgn_mean.get(); m.W = h->d_mgn_W.get(); m.Lambda = h->d_mgn_Lambda.get();
+  m.x = h->d_mc_x.get(); m.partial = h->d_mc_partial.get();
+  return m;
+}
+
+// The device view of the update (MapUpdateDev) over that cut: `map` (NULL: none) with its k window objects and k_new objects it lacks, the posterior in
+// d_mu_post, the tile operands in d_mu_tiles, the result in `fresh`.
+inline MapUpdateDev window_update(obvi_ba_handle* h, const obvi_map* map, int64_t k, int64_t k_new, const MapCutDev& m, obvi_map* fresh) {
+  const int od = h->od;
+  const int64_t NA = k * od, NB = k_new * od, N = map ? map->n * od : 0, nA = map_group_slabs(NA), nB = map_group_slabs(NB), nN = map_group_slabs(N), tile = (int64_t)kTile * kTile;
+  h->d_mu_tiles.resize((size_t)((4 * nA * nA + 3 * nN * nA + 2 * nB * nA) * tile + kTile * nA));
+  MapUpdateDev u{};
+  u.od = od; u.N = (int32_t)N; u.NA = (int32_t)NA; u.nN = (int32_t)nN; u.nA = (int32_t)nA;
+  u.NB = (int32_t)NB; u.nB = (int32_t)nB; u.ldp = (int32_t)(NA + NB); u.ldo = (int32_t)(N + NB);
+  u.map_idx = m.map_idx; u.map_mean = map ? map->d_mean : nullptr; u.map_cov = map ? map->d_cov : nullptr;
+  u.P = h->d_mu_post.get(); u.pm = h->d_mu_post.get() + (NA + NB) * (NA + NB);
+  u.Wt = m.Wt; u.W = m.W; u.mean_A = m.mean;
+  double* t = h->d_mu_tiles.get();
+  u.Wn = t; u.Ps = u.Wn + nA * nA * tile; u.U = u.Ps + nA * nA * tile; u.M = u.U + nA * nA * tile;
+  u.G = u.M + nA * nA * tile; u.Y = u.G + nN * nA * tile; u.Z = u.Y + nN * nA * tile; u.v = u.Z + nN * nA * tile;
+  u.Pba = u.v + kTile * nA; u.V = u.Pba + nB * nA * tile;
+  u.out_mean = fresh->d_mean; u.out_cov = fresh->d_cov; u.status = m.status;
+  return u;
+}
+
+// the cut's pivot and condition tests on its status record: those of obvi_map_set_group_priors_from_map
+inline bool window_cut_spd(const double* st) {
+  return st[MS_BAD] == 0.0 && st[MS_PIV_MIN] * st[MS_PIV_MIN] > 1e-13 * st[MS_PIV_MAX] * st[MS_PIV_MAX] && st[MS_EV_C] * st[MS_EV_LAMBDA] <= 1e13;
+}
+
+}  // namespace obvi_lib
+#endif  // OBVI_MAP_WINDOW_H_

@@ -179,6 +179,62 @@ class Map:
         rc = self._update_fn("map_condition_on_handle")(ba._h, self._m, C.c_int64(len(mid)), _ptr(oid, C.c_uint32), _ptr(mid, C.c_uint32), C.byref(new))
         return self._conditioned(ba, rc, new, "map_condition_on_handle")
 
+    # ---- a map that grows (include/obvi_map_extend.h) ----
+    def _extend_fn(self, name):
+        try:
+            f = getattr(self._lib, self._pre + name)
+        except AttributeError:
+            raise ObviError("%s%s: this library cannot grow or gather a map (include/obvi_map_extend.h is served by libobvi_ba.so only)" % (self._pre, name))
+        f.restype = C.c_int
+        return f
+
+    @classmethod
+    def _unborn(cls, ba):
+        """No map yet: what from_posterior / from_handle extend.  It takes the library, prefix and block size of `ba`."""
+        m = cls.__new__(cls)
+        m._lib, m._pre, m._m, m.od = ba._lib, ba._pre, C.c_void_p(), ba.od or 7
+        return m
+
+    def extend(self, ba, map_idx, post_mean, post_cov, n_new):
+        """A new Map of n + n_new objects: this one conditioned on the joint posterior N(post_mean [k + n_new][od], post_cov) of its objects map_idx (k >= 0 of
+        them) followed by n_new objects it does not hold, which are appended in that order."""
+        mid = np.ascontiguousarray(map_idx, dtype=np.uint32).ravel()
+        k = len(mid) + int(n_new)
+        mu = _f64(post_mean, (k, self.od))
+        cv = _f64(post_cov, (k * self.od, k * self.od))
+        new = C.c_void_p()
+        rc = self._extend_fn("map_extend")(ba._h, self._m, C.c_int64(len(mid)), _ptr(mid, C.c_uint32) if len(mid) else None, C.c_int64(int(n_new)),
+                                           _ptr(mu, C.c_double), _ptr(cv, C.c_double), C.byref(new))
+        return self._conditioned(ba, rc, new, "map_extend")
+
+    def extend_on(self, ba, obj_old, map_idx, obj_new):
+        """A new Map: this one grown by `ba`'s objects obj_new, from the current estimates and joint covariance of obj_old (the map objects map_idx) and obj_new."""
+        old, mid = np.ascontiguousarray(obj_old, dtype=np.uint32).ravel(), np.ascontiguousarray(map_idx, dtype=np.uint32).ravel()
+        fresh = np.ascontiguousarray(obj_new, dtype=np.uint32).ravel()
+        if len(old) != len(mid):
+            raise ObviError("map_extend_on_handle: obj_old and map_idx differ in length")
+        new = C.c_void_p()
+        rc = self._extend_fn("map_extend_on_handle")(ba._h, self._m, C.c_int64(len(mid)), _ptr(old, C.c_uint32) if len(old) else None,
+                                                     _ptr(mid, C.c_uint32) if len(mid) else None, C.c_int64(len(fresh)), _ptr(fresh, C.c_uint32), C.byref(new))
+        return self._conditioned(ba, rc, new, "map_extend_on_handle")
+
+    def select(self, ba, map_idx):
+        """A new Map of this one's objects map_idx, in that order, copied as the device holds them: a subset is the marginal, all of them a permutation."""
+        mid = np.ascontiguousarray(map_idx, dtype=np.uint32).ravel()
+        new = C.c_void_p()
+        rc = self._extend_fn("map_select")(ba._h, self._m, C.c_int64(len(mid)), _ptr(mid, C.c_uint32), C.byref(new))
+        return self._conditioned(ba, rc, new, "map_select")
+
+    @classmethod
+    def from_posterior(cls, ba, post_mean, post_cov):
+        """A first Map, born on `ba`'s device from the posterior N(post_mean [k][od], post_cov [k od][k od]) of k objects: there is no map yet."""
+        return cls._unborn(ba).extend(ba, [], post_mean, post_cov, len(_f64(post_mean, (-1, ba.od or 7))))
+
+    @classmethod
+    def from_handle(cls, ba, obj_idx):
+        """A first Map, born from the current estimates and joint covariance of `ba`'s objects obj_idx."""
+        return cls._unborn(ba).extend_on(ba, [], [], obj_idx)
+
     def close(self):
         if self._m:
             f = getattr(self._lib, self._pre + "map_destroy")

@@ -5,7 +5,9 @@ on the host's workers, then the upload) and of obvi_map_set_group_priors_from_ma
 on the device, one read-back).  Each entry is called once before it is timed (its first call allocates).  obvi_map_create's time is printed beside them.
 --update: the way back instead -- obvi_map_condition_on_handle and obvi_map_condition at 70, 210 and 1 400 window rows on the same 200-object
 map, against the round trip through the host that gives the same map without them.
-usage (GPU box, repo root): python scripts/map_bench.py [--update]"""
+--extend: a map that grows -- obvi_map_extend_on_handle and obvi_map_extend at 70 and 210 window rows of which 14 and 42 belong to objects
+the map lacks, against the round trip that grows the map without them: obvi_map_get, object_covariances of all pairs, numpy, obvi_map_create.
+usage (GPU box, repo root): python scripts/map_bench.py [--update | --extend]"""
 import os
 import sys
 import time
@@ -129,5 +131,76 @@ def update():
     mp.close()
 
 
+def numpy_extend(mean, cov, sel, m, P, k_new):
+    """The formulas of include/obvi_map_extend.h on the host."""
+    n, k_old = len(mean), len(sel)
+    N, NA = n * OD, k_old * OD
+    Ps = 0.5 * (P + P.T)
+    mu, Cn = np.zeros((n + k_new, OD)), np.zeros((N + k_new * OD, N + k_new * OD))
+    mu[:n], Cn[:N, :N] = numpy_update(mean, cov, sel, m[:k_old], P[:NA, :NA])
+    idx = np.concatenate([np.arange(OD * o, OD * o + OD) for o in sel])
+    Cs = 0.5 * (cov + cov.T)
+    K = np.linalg.solve(Cs[np.ix_(idx, idx)], Cs[idx]).T
+    Cn[:N, N:] = K @ Ps[:NA, NA:]
+    Cn[N:, :N] = Cn[:N, N:].T
+    rows = np.concatenate([idx, np.arange(N, N + k_new * OD)])
+    Cn[np.ix_(rows, rows)] = Ps
+    mu[n:] = m[k_old:]
+    return mu, Cn
+
+
+def extend():
+    """a window's new objects appended to the map.  Both device entries against the round trip a session needs without them."""
+    rng = np.random.default_rng(1)
+    mean, cov = rng.normal(size=(N_MAP, OD)), spd(rng, N_MAP * OD)
+    mp = obvi_ba.Map.create(mean, cov, object_block_size=OD)
+    for k, k_new in ((10, 2), (30, 6)):
+        k_old = k - k_new
+        sel = rng.permutation(N_MAP)[:k_old]
+        start = np.concatenate([mean[sel] + 0.05, rng.normal(size=(k_new, OD))])
+        ba = obvi_ba.BundleAdjuster(object_block_size=OD)
+        ba.set_cameras(synth.K_DEFAULT[None], synth.EXT_DEFAULT[None])
+        ba.set_poses(np.zeros((1, 6)), np.ones(1, np.uint8))
+        ba.set_points(np.zeros((0, 3)), np.zeros(0, np.uint8))
+        ba.set_objects(start, np.zeros(k, np.uint8))
+        obj = np.arange(k)
+        old, new_obj = obj[:k_old], obj[k_old:]
+        ba.set_map_group_priors_from_map(mp, [list(old)], [list(sel)], 1e6)
+        ba.set_ltm_priors(obj, start - 0.03, np.tile((0.05 * np.eye(OD)).ravel(), (k, 1)), 1e6)      # what the window measured: the new objects have nothing else
+        ba.solve(obvi_ba.SolverParams(max_num_iterations=10, allow_non_monotonic_steps=True, function_tolerance=1e-6, initial_trust_region_radius=100.0,
+                                      max_trust_region_radius=1e4))
+        pa, pb = np.repeat(obj, k), np.tile(obj, k)
+
+        def posterior():
+            P = ba.object_covariances(pa, pb).reshape(k, k, OD, OD).transpose(0, 2, 1, 3).reshape(k * OD, k * OD)
+            return ba.get_objects(), P
+        m, P = posterior()
+        last = {}
+
+        def round_trip():
+            old_mean, old_cov = mp.get()
+            mm, PP = posterior()
+            mu, Cn = numpy_extend(old_mean, old_cov, sel, mm, PP, k_new)
+            with obvi_ba.Map.create(mu, Cn, object_block_size=OD) as new:
+                last["host"] = (mu, Cn, new.n_objects)
+
+        def on_handle():
+            with mp.extend_on(ba, old, sel, new_obj) as new:
+                last["n"] = new.n_objects
+
+        def host_pointers():
+            with mp.extend(ba, sel, m, P, k_new) as new:
+                last["n"] = new.n_objects
+        base, b = timed(round_trip)
+        dev_on, d1 = timed(on_handle)
+        dev_hp, d2 = timed(host_pointers)
+        with mp.extend_on(ba, old, sel, new_obj) as new:
+            mu, Cn = new.get()
+        print("%5d window rows, %3d of them new: round trip %s   extend_on_handle %s  (x %.1f)   extend %s  (x %.1f)   |C' - numpy's| / |C'| %.1e"
+              % (k * OD, k_new * OD, base, dev_on, b / d1, dev_hp, b / d2, np.abs(Cn - last["host"][1]).max() / np.abs(Cn).max()))
+        ba.close()
+    mp.close()
+
+
 if __name__ == "__main__":
-    update() if "--update" in sys.argv[1:] else main()
+    extend() if "--extend" in sys.argv[1:] else update() if "--update" in sys.argv[1:] else main()
