@@ -199,7 +199,10 @@ int obvi_ba_set_shape_priors(obvi_ba_handle* h, int64_t n, const uint32_t* obj_i
 int obvi_ba_set_ltm_priors(obvi_ba_handle* h, int64_t n, const uint32_t* obj_idx,
                            const double* mean7 /*[n][od]*/, const double* cov49 /*[n][od*od]*/, double huber);
 /* RelPoseFactor -> RelativePoseFactor (relative_pose_factor.h:32-61, .cpp:7-19); measured
- * relative pose given as translation + axis-angle vector of Pose3D::orientation_. */
+ * relative pose given as translation + axis-angle vector of Pose3D::orientation_.
+ * The two poses of a factor are different poses: pose_idx_a[i] == pose_idx_b[i] for any i is refused
+ * with OBVI_ERR_INVALID_ARGUMENT (as Ceres refuses a residual block that names a parameter block twice);
+ * nothing is stored and the factors set before stay. */
 int obvi_ba_set_relpose(obvi_ba_handle* h, int64_t n, const uint32_t* pose_idx_a,
                         const uint32_t* pose_idx_b, const double* t3, const double* aa3,
                         const double* cov36, double huber);

@@ -329,6 +329,8 @@ int obvi_ba_set_relpose(obvi_ba_handle* h, int64_t n, const uint32_t* ia, const 
   std::vector<double> R(9 * n), si(36 * n);
   for (int64_t i = 0; i < n; ++i) {
     if (ia[i] >= h->P || ib[i] >= h->P) return fail(h, OBVI_ERR_OUT_OF_RANGE, "set_relpose: index out of range");
+    // one parameter block twice in a residual block (Ceres refuses it): the kernels have no cross term Ja^T Jb inside a diagonal block
+    if (ia[i] == ib[i]) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "set_relpose: a factor between a pose and itself");
     // measured_pose_deviation.orientation_.toRotationMatrix() (relative_pose_factor.cpp:11-12)
     const double* a = aa3 + 3 * i;
     const double th = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);

@@ -952,6 +952,8 @@ int oracle_ba_set_relpose(oracle_handle* h, int64_t n, const uint32_t* ia, const
   if (!h || n < 0 || (n > 0 && (!ia || !ib || !t3 || !aa3 || !cov36))) return OBVI_ERR_INVALID_ARGUMENT;
   OracleProblem& pb = h->pb;
   for (int64_t i = 0; i < n; ++i) if (ia[i] >= pb.P || ib[i] >= pb.P) return OBVI_ERR_OUT_OF_RANGE;
+  // a residual block with one parameter block twice: Ceres refuses it (assemble_schur relies on two distinct blocks per factor)
+  for (int64_t i = 0; i < n; ++i) if (ia[i] == ib[i]) { pb.err = "set_relpose: a factor between a pose and itself"; return OBVI_ERR_INVALID_ARGUMENT; }
   pb.n_rl = n; pb.rl_a.assign(ia, ia + n); pb.rl_b.assign(ib, ib + n); pb.rl_t.assign(t3, t3 + 3 * n);
   pb.rl_R.resize(9 * n); pb.rl_sqrt_inf.resize(36 * n);
   for (int64_t i = 0; i < n; ++i) {

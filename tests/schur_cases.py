@@ -48,9 +48,10 @@ BATCH_SLOTS, BATCH_VISITS, PAIRS_PER_ITEM = 32768 // 144, 128, 256
 IMAGE_DOUBLES = 1264
 
 
-def bound(case, what):
-    t = TABLE[case]
-    return max(8.0 * t[what], t["n_terms"] * 2.0 ** -53)
+def bound(case, what, table=None):
+    """(table: another module's case table; an entry "second_<what>" there is a second measured error of the reference's inputs, tests/object_cases.py)"""
+    t = (TABLE if table is None else table)[case]
+    return max(8.0 * max(t[what], t.get("second_" + what, 0.0)), t["n_terms"] * 2.0 ** -53)
 
 
 # ------------------------------------------------------------------------------------------
@@ -168,11 +169,11 @@ def strip_routing(prob, mask=None):
 # the case builder
 # ------------------------------------------------------------------------------------------
 class _Builder:
-    def __init__(self, name, P, stereo, seed):
+    def __init__(self, name, P, stereo, seed, const_poses=None):
         self.name, self.P, self.stereo = name, P, stereo
         self.rng = np.random.Generator(np.random.MT19937(seed))
         self.pose_const = np.zeros(P, np.uint8)
-        self.pose_const[[0, 37, 38, 39, P - 1]] = 1
+        self.pose_const[[0, 37, 38, 39, P - 1] if const_poses is None else list(const_poses)] = 1
         self.pose_of_frame = np.flatnonzero(self.pose_const == 0)       # every variable pose gets a sighting (checked in finish)
         self.n_frames = len(self.pose_of_frame)
         self.sightings = []          # (point, pose, cam, masked from the start, masked after the solve)
@@ -501,13 +502,16 @@ def _lm_lambda(colsq, radius):
     return np.clip(colsq * s * s, LD(1e-6), LD(1e32)) / LD(radius) / (s * s)
 
 
-def reference(prob, oracle_handle, radius, mask=None, want_step=True):
+def reference(prob, oracle_handle, radius, mask=None, want_step=True, side=None, lin0=None):
     """One LM step at the handle's current estimate, in numpy long double, from the oracle's raw r, Jp, Jl of every sighting, the Huber weight and the LM rule
     alone.  Returns a dict: S, b (variable poses in upload order), their scales A_S, A_b, n_terms, cost, gradient_max_norm, gradient_norm, step_pose [P,6],
     step_point [L,3], step_norm, point_var, pivots_ok.  want_step=False: the reduced system and the scalars of the linearisation only (at a large radius the reduced
-    system is too ill-conditioned for a step that is better than fp64: the refinement stalls at cond(S) 2^-64, and the step is checked at the solve's own radius)."""
+    system is too ill-conditioned for a step that is better than fp64: the refinement stalls at cond(S) 2^-64, and the step is checked at the solve's own radius).
+    side (tests/object_cases.py, SideTerms): the factors of the other families -- the reduced system then runs over (variable poses, variable objects), both in
+    upload order, the damping of a row comes from the whole diagonal of J^T J, and object_var, step_object are returned too.  lin0: (r, Jp, Jl) of the sightings
+    from somewhere else than the oracle handle."""
     assert np.finfo(LD).eps <= 2.0 ** -63, "numpy long double is no wider than double here: the reference needs the x87 format or better"
-    r64, Jp64, Jl64 = oracle_handle.debug_linearize(0)
+    r64, Jp64, Jl64 = oracle_handle.debug_linearize(0) if lin0 is None else lin0
     r, Jp, Jl = r64.astype(LD), Jp64.astype(LD), Jl64.astype(LD)
     n = len(r)
     P, L = len(prob["poses"]), len(prob["points"])
@@ -523,9 +527,12 @@ def reference(prob, oracle_handle, radius, mask=None, want_step=True):
     both = bool(over[act].any()) and bool((~over[act]).any())
     live = act & ~(cp & cl)
     var_pose = (prob["pose_const"] == 0) & (np.bincount(pose[live], minlength=P) > 0)
+    if side is not None:
+        var_pose |= (prob["pose_const"] == 0) & side.pose_used
     var_point = (prob["point_const"] == 0) & (np.bincount(point[live], minlength=L) > 0)
     frame = np.where(var_pose, np.cumsum(var_pose) - 1, -1)
     nF = int(var_pose.sum())
+    ex = side.assemble(var_pose, frame) if side is not None else None
     # pose side: every active sighting of a variable pose (a constant point's too)
     Hpp, App, gp, Agp = np.zeros((nF, 6, 6), LD), np.zeros((nF, 6, 6), LD), np.zeros((nF, 6), LD), np.zeros((nF, 6), LD)
     mp = act & var_pose[pose]
@@ -549,7 +556,7 @@ def reference(prob, oracle_handle, radius, mask=None, want_step=True):
     Hinv, piv = _inv3(Hd)
     pivots_ok = bool((piv[var_point] > 0).all())
     i6 = np.arange(6)
-    lam_p = _lm_lambda(Hpp[:, i6, i6], radius)
+    lam_p = _lm_lambda(Hpp[:, i6, i6] if ex is None else Hpp[:, i6, i6] + np.diagonal(ex["H"])[:6 * nF].reshape(nF, 6), radius)
     S4 = np.zeros((nF, nF, 6, 6), LD); A4 = np.zeros((nF, nF, 6, 6), LD); T4 = np.zeros((nF, nF), np.int64)
     fi = np.arange(nF)
     S4[fi, fi] = Hpp; S4[fi[:, None], fi[:, None], i6[None, :], i6[None, :]] += lam_p
@@ -577,8 +584,26 @@ def reference(prob, oracle_handle, radius, mask=None, want_step=True):
     S = S4.transpose(0, 2, 1, 3).reshape(m, m); A_S = A4.transpose(0, 2, 1, 3).reshape(m, m)
     bv, A_b = b.reshape(m), Ab.reshape(m)
     g_all = np.concatenate([gp.ravel(), gl[var_point].ravel()])
-    out = dict(S=S, b=bv, A_S=A_S, A_b=A_b, n_terms=int(max(T4.max(), Tb.max())), cost=cost, gradient_max_norm=np.abs(g_all).max(), gradient_norm=np.sqrt((g_all * g_all).sum()),
+    n_terms = int(max(T4.max(), Tb.max()))
+    if ex is not None:
+        # the other families: their J^T J and J^T r over (variable poses, variable objects), the objects' damping from their own diagonal
+        mp, m = m, ex["H"].shape[0]
+        io = np.arange(mp, m)
+        lam_o = _lm_lambda(np.diagonal(ex["H"])[mp:], radius)
+        Sf, Af = ex["H"].copy(), ex["A"].copy()
+        Sf[:mp, :mp] += S; Af[:mp, :mp] += A_S
+        Sf[io, io] += lam_o; Af[io, io] += lam_o
+        bf, Abf = ex["g"].copy(), ex["Ag"].copy()
+        bf[:mp] += bv; Abf[:mp] += A_b
+        Tf, Tbf = ex["T"].copy(), ex["Tg"].copy()
+        Tf[:mp, :mp] += np.kron(T4, np.ones((6, 6), np.int64)); Tf[io, io] += 1
+        Tbf[:mp] += np.repeat(Tb, 6)
+        g_all = np.concatenate([gp.ravel() + ex["g"][:mp], ex["g"][mp:], gl[var_point].ravel()])
+        S, A_S, bv, A_b, n_terms, cost = Sf, Af, bf, Abf, int(max(Tf.max(), Tbf.max())), cost + ex["cost"]
+    out = dict(S=S, b=bv, A_S=A_S, A_b=A_b, n_terms=n_terms, cost=cost, gradient_max_norm=np.abs(g_all).max(), gradient_norm=np.sqrt((g_all * g_all).sum()),
                point_var=var_point, pose_var=var_pose, pivots_ok=pivots_ok, both_huber_branches=both)
+    if ex is not None:
+        out.update(object_var=ex["object_var"], side_branches=ex["branches"], n_pose_rows=6 * nF)
     if not want_step:
         return out
     # the step: S y = b in fp64 with iterative refinement on long double residuals; poses move by -y, points by -Hinv (g_l - sum Hpl^T y)
@@ -592,7 +617,7 @@ def reference(prob, oracle_handle, radius, mask=None, want_step=True):
             break
     else:
         raise AssertionError("the refinement of the reference step did not converge")
-    yf = y.reshape(nF, 6)
+    yf = y[:6 * nF].reshape(nF, 6)
     t = gl.copy()
     np.subtract.at(t, point[order], np.einsum("nab,na->nb", Hpl[order], yf[frame[pose[order]]]))
     step_point = -np.einsum("lab,lb->la", Hinv, t)
@@ -600,6 +625,10 @@ def reference(prob, oracle_handle, radius, mask=None, want_step=True):
     step_pose = np.zeros((P, 6), LD)
     step_pose[var_pose] = -yf
     out.update(step_pose=step_pose, step_point=step_point, step_norm=np.sqrt((step_pose ** 2).sum() + (step_point ** 2).sum()))
+    if ex is not None:                                                # objects move by minus their part of y
+        step_object = np.zeros((len(ex["object_var"]), ex["od"]), LD)
+        step_object[ex["object_var"]] = -y[6 * nF:].reshape(-1, ex["od"])
+        out.update(step_object=step_object, step_norm=np.sqrt((step_pose ** 2).sum() + (step_point ** 2).sum() + (step_object ** 2).sum()))
     return out
 
 

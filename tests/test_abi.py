@@ -83,6 +83,43 @@ def test_invalid_arguments(lib):
     assert lib.obvi_ba_object_covariances(None, C.c_int64(0), None, None, None) == -1
 
 
+def _relpose_between_a_pose_and_itself_is_refused(ba):
+    """set_relpose with pose_idx_a[i] == pose_idx_b[i]: OBVI_ERR_INVALID_ARGUMENT, nothing stored, the factors set before stay"""
+    import numpy as np
+    import synth
+    prob = synth.make_problem(P=8, L=60, O=0, seed=5)
+    synth.upload(ba, prob)
+    cost0, _, sq0 = ba.evaluate(True)
+    n = len(prob["rl_a"])
+    assert n == 7 and ba.num_factors(obvi_ba.FACTOR_REL_POSE) == n
+    f = ba._fn("ba_num_factors")
+    a, b = prob["rl_a"].copy(), prob["rl_b"].copy()
+    for at in (0, 3, n - 1):                      # first, middle and last factor of the call
+        bad_b = b.copy(); bad_b[at] = a[at]
+        with pytest.raises(obvi_ba.ObviError, match="status -1"):
+            ba.set_relpose(a, bad_b, prob["rl_t"], prob["rl_aa"], prob["rl_cov"], prob["rl_huber"])
+        assert f(ba._h, C.c_int32(obvi_ba.FACTOR_REL_POSE)) == n
+    with pytest.raises(obvi_ba.ObviError, match="status -1"):   # a call of one such factor alone
+        ba.set_relpose(a[:1], a[:1], prob["rl_t"][:1], prob["rl_aa"][:1], prob["rl_cov"][:1], prob["rl_huber"])
+    assert f(ba._h, C.c_int32(obvi_ba.FACTOR_REL_POSE)) == n
+    cost1, _, sq1 = ba.evaluate(True)
+    assert cost1 == cost0 and np.array_equal(sq1, sq0) and sq1[-n:].min() > 0
+    ba.set_relpose(b, a, prob["rl_t"], prob["rl_aa"], prob["rl_cov"], prob["rl_huber"])   # the reverse order is a valid factor
+    assert f(ba._h, C.c_int32(obvi_ba.FACTOR_REL_POSE)) == n
+
+
+def test_oracle_refuses_a_relpose_factor_between_a_pose_and_itself():
+    _relpose_between_a_pose_and_itself_is_refused(helpers.oracle_ba())
+
+
+@pytest.mark.gpu
+def test_product_refuses_a_relpose_factor_between_a_pose_and_itself():
+    g = helpers.product_ba()
+    _relpose_between_a_pose_and_itself_is_refused(g)
+    with pytest.raises(obvi_ba.ObviError, match="a pose and itself"):
+        g.set_relpose([2], [2], [[0.1, 0, 0]], [[0, 0, 0.01]], [[1 if i % 7 == 0 else 0 for i in range(36)]], 1.0)
+
+
 def test_generator_shapes():
     import numpy as np
     import synth
