@@ -321,6 +321,21 @@ int obvi_ba_debug_select(obvi_ba_handle* h, int64_t n, const double* sq, const u
  * collective runs, even with shared objects and an all-reduce hook set. */
 int obvi_ba_debug_reduced_system(obvi_ba_handle* h, double radius, double* lhs, double* rhs, int32_t m_cap,
                                  int32_t* m_out);
+/* one reduced system together with what the LM step's tile Cholesky makes of it: the assembly of obvi_ba_debug_reduced_system, a copy of its
+ * lhs / rhs taken before the factorisation overwrites them, then the step's own factorisation and substitutions on those very tiles, and the y that
+ * the back-substitution pass reads.  Sign convention:  lhs * y = rhs  (rhs is the reduced gradient; the step the LM loop applies is -y, Jacobi-scaled).
+ * lhs [m][m], rhs [m], y [m] in canonical order (variable poses by index, then variable objects); grid_row[i] (may be NULL) = row of the tile grid,
+ * i.e. position in the elimination order, of canonical row i: the grid has 64 * [4] rows, those that no grid_row names are padding (identity).
+ * lhs_in == rhs_in == NULL: the handle's own system; lhs, rhs and y belong to ONE assembly (atomics make two assemblies differ in the last bits).
+ * lhs_in [m][m] symmetric and rhs_in [m] given (canonical order): they take the place of the assembled values in the tile grid and right-hand side --
+ * padding rows keep their identity diagonal, a non-zero entry outside the structural tile mask is refused with OBVI_ERR_INVALID_ARGUMENT -- while the
+ * elimination order, levels, job lists, slices and chains stay those of the uploaded problem and the handle's knobs; lhs / rhs return the given values.
+ * Returns OBVI_ERR_NUMERICAL (lhs, rhs, y still written) if the step's scalar block reports a non-positive pivot or a non-finite entry -- what
+ * obvi_ba_solve rejects a step on --, OBVI_OK otherwise.  A wait time-out of the fused level kernel is handled as in a solve: the step is re-run on the
+ * two-launch schedule and counted in obvi_ba_get_problem_stats [16].  The handle is left as obvi_ba_debug_reduced_system leaves it.  It is the rank's
+ * own system: a handle with shared objects and an all-reduce hook set is refused with OBVI_ERR_INVALID_ARGUMENT (the step would run its collectives). */
+int obvi_ba_debug_reduced_solve(obvi_ba_handle* h, double radius, const double* lhs_in, const double* rhs_in,
+                                double* lhs, double* rhs, double* y, int32_t* grid_row, int32_t m_cap, int32_t* m_out);
 /* structure of the reduced program after the last evaluate/solve, as doubles:
  * [0] variable poses [1] variable objects [2] eliminated points [3] reduced rows m [4] tiles per dim
  * [5] Schur 6x6 blocks [6] Schur observation pairs [7] non-zero tiles after fill [8] trsm tile jobs

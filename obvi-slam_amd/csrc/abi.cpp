@@ -340,6 +340,83 @@ int obvi_ba_debug_reduced_system(obvi_ba_handle* h, double radius, double* lhs, 
   OBVI_API_END(h)
 }
 
+int obvi_ba_debug_reduced_solve(obvi_ba_handle* h, double radius, const double* lhs_in, const double* rhs_in, double* lhs, double* rhs, double* y,
+                                int32_t* grid_row, int32_t m_cap, int32_t* m_out) {
+  if (!h || !lhs || !rhs || !y || (lhs_in == nullptr) != (rhs_in == nullptr)) return OBVI_ERR_INVALID_ARGUMENT;
+  if (!check_ready(h)) return fail(h, OBVI_ERR_NOT_READY, "debug_reduced_solve: cameras not set");
+  OBVI_API_BEGIN
+  OBVI_HIP(hipSetDevice(h->device));
+  { const int vrc = validate_indices(h); if (vrc != OBVI_OK) return vrc; }
+  if (exchanging(h)) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "debug_reduced_solve: the handle exchanges shared objects; the entry solves a rank's own system only");
+  if (h->mask_dirty) h->dirty = true;   // (as obvi_ba_debug_reduced_system)
+  prepare(h);
+  if (m_out) *m_out = (int32_t)h->m_canon;
+  if (h->m_canon > m_cap) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "debug_reduced_solve: buffer too small");
+  const int64_t mc = h->m_canon, nt = h->nt;
+  if (mc == 0 || h->m == 0) return OBVI_OK;
+  hipStream_t s = h->stream;
+  constexpr int64_t TT = (int64_t)kTile * kTile;
+  std::vector<double> tiles((size_t)(nt * nt * TT)), hr((size_t)nt * kTile), hy((size_t)nt * kTile);
+  std::vector<int32_t> tl((size_t)2 * h->ntiles);
+  h->d_tiles.download(tl.data(), tl.size(), s);
+  sync(h);
+  std::vector<uint8_t> mk((size_t)nt * nt, 0);   // tiles outside the structural mask are never written and never read
+  for (int t = 0; t < h->ntiles; ++t) mk[(size_t)tl[2 * t] * nt + tl[2 * t + 1]] = 1;
+  const bool given = lhs_in != nullptr;
+  if (given) {
+    for (int64_t ci = 0; ci < mc; ++ci)
+      for (int64_t cj = 0; cj < mc; ++cj) {
+        const double v = lhs_in[ci * mc + cj], w = lhs_in[cj * mc + ci];
+        if (!(v == w) && !(v != v && w != w)) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "debug_reduced_solve: the given system is not symmetric");
+        const int64_t i = h->h_canon_row[ci], j = h->h_canon_row[cj];
+        if (v != 0.0 && !mk[(size_t)(std::max(i, j) / kTile) * nt + std::min(i, j) / kTile])
+          return fail(h, OBVI_ERR_INVALID_ARGUMENT, "debug_reduced_solve: a non-zero entry of the given system lies outside the structural tile mask");
+      }
+  }
+  // between the step's assembly and its factorisation: the system as the factorisation is about to see it -- or the caller's, put in its place
+  const std::function<void()> between = [&] {
+    h->d_S.download(tiles.data(), tiles.size(), s); h->d_rhs.download(hr.data(), hr.size(), s);
+    sync(h);
+    if (!given) return;
+    for (int64_t ci = 0; ci < mc; ++ci) {   // real rows only: the padding rows keep the identity the step's clear gave them
+      const int64_t i = h->h_canon_row[ci];
+      hr[i] = rhs_in[ci];
+      for (int64_t cj = 0; cj < mc; ++cj) {
+        const int64_t j = h->h_canon_row[cj];
+        const int64_t r = std::max(i, j), c = std::min(i, j);
+        const size_t tix = (size_t)(r / kTile) * nt + (c / kTile);
+        if (!mk[tix]) continue;
+        const double v = lhs_in[ci * mc + cj];
+        tiles[tix * TT + (r % kTile) * kTile + (c % kTile)] = v;
+        if (r / kTile == c / kTile) tiles[tix * TT + (c % kTile) * kTile + (r % kTile)] = v;   // diagonal tiles are kept symmetric
+      }
+    }
+    OBVI_HIP(hipMemcpyAsync(h->d_S.get(), tiles.data(), tiles.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    OBVI_HIP(hipMemcpyAsync(h->d_rhs.get(), hr.data(), hr.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    sync(h);
+  };
+  // the LM step itself, as at a first iteration, with the factor kept in the tiles (nothing is cleared behind it: the next step clears)
+  { QuietStep quiet(h); submit_step(h, radius, /*first_iter=*/true, /*solve=*/true, /*keep_factor=*/true, &between); }
+  h->d_y.download(hy.data(), hy.size(), s);
+  sync(h);
+  bool finite = true;
+  for (int64_t ci = 0; ci < mc; ++ci) {
+    const int64_t i = h->h_canon_row[ci];
+    rhs[ci] = hr[i]; y[ci] = hy[i]; finite = finite && std::isfinite(hy[i]);
+    if (grid_row) grid_row[ci] = (int32_t)i;
+    for (int64_t cj = 0; cj < mc; ++cj) {
+      const int64_t j = h->h_canon_row[cj];
+      const int64_t r = std::max(i, j), c = std::min(i, j);
+      const size_t tix = (size_t)(r / kTile) * nt + (c / kTile);
+      lhs[ci * mc + cj] = mk[tix] ? tiles[tix * TT + (r % kTile) * kTile + (c % kTile)] : 0.0;
+    }
+  }
+  if (h->h_scal[SC_CHOL_FAIL] != 0.0 || h->h_scal[SC_NONFINITE] != 0.0 || !finite)
+    return fail(h, OBVI_ERR_NUMERICAL, "debug_reduced_solve: the step reports a non-positive pivot or a non-finite entry");
+  return OBVI_OK;
+  OBVI_API_END(h)
+}
+
 int obvi_ba_object_covariances(obvi_ba_handle* h, int64_t n_pairs, const uint32_t* obj_a, const uint32_t* obj_b, double* cov49) {
   if (!h || n_pairs < 0 || (n_pairs > 0 && (!obj_a || !obj_b || !cov49))) return OBVI_ERR_INVALID_ARGUMENT;
   if (!check_ready(h)) return fail(h, OBVI_ERR_NOT_READY, "object_covariances: cameras not set");

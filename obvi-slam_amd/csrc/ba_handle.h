@@ -705,7 +705,9 @@ int object_cov_forward(obvi_ba_handle* h, int64_t n_pairs, const char* what, int
 // ... and the od x od blocks of the pairs (obj_a[i], obj_b[i]) from that Yt into d_cov_out, pair after pair; a pair with an object that is no variable: zeros
 void object_cov_pair_blocks(obvi_ba_handle* h, int64_t n_pairs, const uint32_t* obj_a, const uint32_t* obj_b, int64_t ldt, CovTables& keep);
 // ---- lm.cpp
-void submit_step(obvi_ba_handle* h, double radius, bool first_iter, bool solve, bool keep_factor = false);
+// `between`: runs on the host between the assembly and the factorisation, with both streams joined (obvi_ba_debug_reduced_solve copies the system out, or
+// puts a given one in, there); it runs again if the step is re-submitted after a wait time-out
+void submit_step(obvi_ba_handle* h, double radius, bool first_iter, bool solve, bool keep_factor = false, const std::function<void()>* between = nullptr);
 void assemble_step(obvi_ba_handle* h, double radius, bool first_iter, bool schur, bool exchange);
 int prove_tail_order(obvi_ba_handle* h, const char* what);   // first collective of a covariance pass on a handle that exchanges
 inline bool exchanging(const obvi_ba_handle* h) { return h->allreduce != nullptr && !h->h_shared_ov.empty(); }

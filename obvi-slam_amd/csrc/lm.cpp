@@ -208,14 +208,15 @@ static bool publish_and_wait(obvi_ba_handle* h, bool keep_factor, double t_submi
 
 // One LM step on the device: linearise at the current point, assemble and solve the damped reduced
 // system, form the candidate, evaluate it.  `solve` false: linearisation only (gradient norms).
-void submit_step(obvi_ba_handle* h, double radius, bool first_iter, bool solve, bool keep_factor) {
+void submit_step(obvi_ba_handle* h, double radius, bool first_iter, bool solve, bool keep_factor, const std::function<void()>* between) {
   ApiTimer api_timer_("  LM step (submit + wait)");
   const double t_submit0 = api_times() ? wall_s() : 0.0;
   const bool exchange = h->allreduce != nullptr && !h->h_shared_ov.empty();
   assemble_step(h, radius, first_iter, solve, exchange);
+  if (between) (*between)();
   factor_step(h, solve, exchange);
   trial_point_step(h, solve, exchange);
-  if (!publish_and_wait(h, keep_factor, t_submit0)) submit_step(h, radius, first_iter, solve, keep_factor);
+  if (!publish_and_wait(h, keep_factor, t_submit0)) submit_step(h, radius, first_iter, solve, keep_factor, between);
 }
 
 // A collective covariance pass (cov.cpp, obvi_ba_object_covariances) on a handle that exchanges: the proof obvi_ba_solve runs first, as a collective of its

@@ -702,6 +702,27 @@ class BundleAdjuster:
         mm = m.value
         return lhs.ravel()[:mm * mm].reshape(mm, mm).copy(), rhs[:mm].copy()
 
+    def debug_reduced_solve(self, radius, lhs_in=None, rhs_in=None, m_cap=4096):
+        """(status, lhs, rhs, y, grid_row) of obvi_ba_debug_reduced_solve: lhs * y = rhs, canonical order.  status is OBVI_OK (0) or OBVI_ERR_NUMERICAL (-6: the
+        step's scalar block reports a non-positive pivot or a non-finite entry); any other status raises.  lhs_in / rhs_in: a given system in place of the assembly."""
+        if (lhs_in is None) != (rhs_in is None):
+            raise ObviError("debug_reduced_solve: give both lhs_in and rhs_in, or neither")
+        if lhs_in is not None:
+            rin = _f64(rhs_in, (-1,))
+            lin = _f64(lhs_in, (len(rin), len(rin)))
+            m_cap = len(rin)                      # (a handle whose system has more rows refuses; fewer is caught below)
+        lhs, rhs, y, row = np.zeros((m_cap, m_cap)), np.zeros(m_cap), np.zeros(m_cap), np.full(m_cap, -1, dtype=np.int32)
+        m = C.c_int32(0)
+        rc = self._fn("ba_debug_reduced_solve")(self._h, C.c_double(radius), _ptr(lin, C.c_double) if lhs_in is not None else None,
+                                                _ptr(rin, C.c_double) if lhs_in is not None else None, _ptr(lhs, C.c_double), _ptr(rhs, C.c_double),
+                                                _ptr(y, C.c_double), _ptr(row, C.c_int32), C.c_int32(m_cap), C.byref(m))
+        if rc != -6:
+            self._check(rc, "debug_reduced_solve")
+        mm = m.value
+        if lhs_in is not None and mm != len(rin):
+            raise ObviError("debug_reduced_solve: the given system has %d rows, the handle's reduced system %d" % (len(rin), mm))
+        return rc, lhs.ravel()[:mm * mm].reshape(mm, mm).copy(), rhs[:mm].copy(), y[:mm].copy(), row[:mm].copy()
+
     def problem_stats(self):
         buf = (C.c_double * 22)()
         n = self._fn("ba_get_problem_stats")(self._h, buf, C.c_int32(22))

@@ -1080,6 +1080,45 @@ int oracle_ba_debug_reduced_system(oracle_handle* h, double radius, double* lhs,
   return OBVI_OK;
 }
 
+// Mirror of obvi_ba_debug_reduced_solve: the system of oracle_ba_debug_reduced_system (or the given one) as doubles, and the y of  lhs y = rhs  by a dense
+// Cholesky in long double in canonical order -- the oracle has no tile grid: grid_row is the identity.  OBVI_ERR_NUMERICAL on a pivot that is not positive
+// (a NaN included), with lhs and rhs written.
+int oracle_ba_debug_reduced_solve(oracle_handle* h, double radius, const double* lhs_in, const double* rhs_in, double* lhs, double* rhs, double* y,
+                                  int32_t* grid_row, int32_t m_cap, int32_t* m_out) {
+  if (!h || !lhs || !rhs || !y || (lhs_in == nullptr) != (rhs_in == nullptr)) return OBVI_ERR_INVALID_ARGUMENT;
+  int32_t m32 = 0;
+  const int rc = oracle_ba_debug_reduced_system(h, radius, lhs, rhs, m_cap, &m32);
+  if (m_out) *m_out = m32;
+  if (rc != OBVI_OK) return rc;
+  const int64_t m = m32;
+  if (lhs_in) {
+    for (int64_t i = 0; i < m; ++i) for (int64_t j = 0; j < i; ++j) {
+      const double v = lhs_in[i * m + j], w = lhs_in[j * m + i];
+      if (!(v == w) && !(v != v && w != w)) return OBVI_ERR_INVALID_ARGUMENT;
+    }
+    std::copy(lhs_in, lhs_in + m * m, lhs); std::copy(rhs_in, rhs_in + m, rhs);
+  }
+  for (int64_t i = 0; i < m; ++i) { y[i] = 0.0; if (grid_row) grid_row[i] = (int32_t)i; }
+  std::vector<long double> L((size_t)(m * m), 0.0L), z((size_t)m);
+  for (int64_t j = 0; j < m; ++j) {   // column by column
+    long double p = lhs[j * m + j];
+    for (int64_t k = 0; k < j; ++k) p -= L[j * m + k] * L[j * m + k];
+    if (!(p > 0.0L)) return OBVI_ERR_NUMERICAL;
+    const long double d = std::sqrt(p);
+    L[j * m + j] = d;
+    for (int64_t i = j + 1; i < m; ++i) {
+      long double v = lhs[i * m + j];
+      for (int64_t k = 0; k < j; ++k) v -= L[i * m + k] * L[j * m + k];
+      L[i * m + j] = v / d;
+    }
+  }
+  for (int64_t i = 0; i < m; ++i) { long double v = rhs[i]; for (int64_t k = 0; k < i; ++k) v -= L[i * m + k] * z[k]; z[i] = v / L[i * m + i]; }
+  for (int64_t i = m - 1; i >= 0; --i) { long double v = z[i]; for (int64_t k = i + 1; k < m; ++k) v -= L[k * m + i] * z[k]; z[i] = v / L[i * m + i]; }
+  bool finite = true;
+  for (int64_t i = 0; i < m; ++i) { y[i] = (double)z[i]; finite = finite && std::isfinite(y[i]); }
+  return finite ? OBVI_OK : OBVI_ERR_NUMERICAL;
+}
+
 // ceres::Covariance::Compute + GetCovarianceBlock for pairs of object blocks, as the long-term-map extraction asks for them
 // (long_term_object_map_extraction.cpp:419-433, long_term_object_map_extraction.h:318-340, 499-513): blocks of (J^T J)^-1 over
 // the variable parameter blocks at the current point, J robustified (Covariance::Options::apply_loss_function defaults to

@@ -23,9 +23,9 @@ def test_every_function_of_the_covariance_header_is_exported():
 
 def test_the_covariance_entries_are_not_part_of_the_mirrored_header():
     """tests/test_abi.py::test_oracle_mirrors_the_abi asks the oracle for a twin of every obvi_ba_* name in obvi_ba.h: the new entries have
-    their own header and prefix, and obvi_ba.h declares exactly the 43 names it declared before (digest of the sorted list)."""
+    their own header and prefix, and obvi_ba.h declares exactly the 43 names it declared before them plus obvi_ba_debug_reduced_solve, which the oracle does mirror (digest of the sorted list)."""
     names = entry.abi_symbols()
-    assert len(names) == 43 and hashlib.sha256(" ".join(names).encode()).hexdigest()[:16] == "7f090ea1b576ed75"
+    assert len(names) == 44 and hashlib.sha256(" ".join(names).encode()).hexdigest()[:16] == "2837b0377bdf0305"
     assert "obvi_cov_" not in open(os.path.join(helpers.ROOT, "include", "obvi_ba.h")).read()
 
 
