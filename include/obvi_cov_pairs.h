@@ -42,6 +42,18 @@ extern "C" {
 int obvi_cov_compute_pairs(obvi_ba_handle* h, int64_t n, const uint8_t* kind_a, const uint32_t* idx_a, const uint8_t* kind_b,
                            const uint32_t* idx_b);
 
+/* Debug / verification: obvi_cov_compute_pairs on the same pairs (n = 0: obvi_cov_compute), exposing the system the pass inverts.
+ *   lhs [m][m] (row-major, canonical order: variable poses by index, then objects -- the order of obvi_ba_debug_reduced_solve): a copy of the tiles
+ *       taken between the pass's assembly and its factorisation: undamped, parameter-prior diagonals included; tiles outside the structural
+ *       mask read as zero.  grid_row [m] (may be null): the row of the tile grid of every canonical index.
+ *   lhs_in (may be null): values put in place of the assembled tiles, which lhs then shows.  Checked as obvi_ba_debug_reduced_solve checks its
+ *       own: symmetric, no non-zero entry outside the structural tile mask, else OBVI_ERR_INVALID_ARGUMENT before any device work of the pass;
+ *       a non-positive pivot or a NaN gives OBVI_ERR_NUMERICAL, as the pass answers rank deficiency (lhs is written all the same).
+ * m_cap: rows the buffers hold; *m_out: m.  On success the handle is in the pass's finished state: every getter serves blocks of that one
+ * factorisation.  Refused on a handle that exchanges shared objects (OBVI_ERR_INVALID_ARGUMENT). */
+int obvi_cov_debug_compute_pairs(obvi_ba_handle* h, int64_t n, const uint8_t* kind_a, const uint32_t* idx_a, const uint8_t* kind_b,
+                                 const uint32_t* idx_b, const double* lhs_in, double* lhs, int32_t* grid_row, int32_t m_cap, int32_t* m_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -275,7 +275,9 @@ void pairs_after_inversion(obvi_ba_handle* h, const PairPlan& pp, const std::vec
 }
 
 // obvi_cov_compute (n = 0) and obvi_cov_compute_pairs
-int cov_pass(obvi_ba_handle* h, const char* what, int64_t n, const uint8_t* ka, const uint32_t* ia, const uint8_t* kb, const uint32_t* ib) {
+// `between`: handed to the step (submit_step): runs between the assembly and the factorisation (obvi_cov_debug_compute_pairs)
+int cov_pass(obvi_ba_handle* h, const char* what, int64_t n, const uint8_t* ka, const uint32_t* ia, const uint8_t* kb, const uint32_t* ib,
+             const std::function<void()>* between = nullptr) {
   const std::string name(what);
   if (!check_ready(h)) return fail(h, OBVI_ERR_NOT_READY, name + ": cameras not set");
   OBVI_HIP(hipSetDevice(h->device));
@@ -298,7 +300,7 @@ int cov_pass(obvi_ba_handle* h, const char* what, int64_t n, const uint8_t* ka, 
     // the undamped system at the current point, factorised: one LM step's linearisation and factorisation with the trust-region radius at infinity
     // (obvi_ba_object_covariances takes the same route); its point pass leaves the Z and C^-1 records the feature blocks are formed from
     upload_parameter_prior_diagonals(h);
-    { QuietStep quiet(h, /*use_extra=*/!h->h_pp_kind.empty()); submit_step(h, 1e300, true, true, /*keep_factor=*/true); }
+    { QuietStep quiet(h, /*use_extra=*/!h->h_pp_kind.empty()); submit_step(h, 1e300, true, true, /*keep_factor=*/true, between); }
     if (h->h_scal[SC_CHOL_FAIL] != 0.0 || h->h_scal[SC_NONFINITE] != 0.0 || !std::isfinite(h->h_scal[SC_STEPSQ]))
       return fail(h, OBVI_ERR_NUMERICAL, name + ": the normal equations are rank deficient at the current estimate");
   }
@@ -341,6 +343,82 @@ int obvi_cov_compute_pairs(obvi_ba_handle* h, int64_t n, const uint8_t* kind_a, 
     }
   OBVI_API_BEGIN
   return cov_pass(h, "cov_compute_pairs", n, kind_a, idx_a, kind_b, idx_b);
+  OBVI_API_END(h)
+}
+
+// cov_pass with the `between` hook of the step, as obvi_ba_debug_reduced_solve (abi.cpp) takes it: the same checks of a given system, the same copy
+int obvi_cov_debug_compute_pairs(obvi_ba_handle* h, int64_t n, const uint8_t* kind_a, const uint32_t* idx_a, const uint8_t* kind_b, const uint32_t* idx_b, const double* lhs_in,
+                                 double* lhs, int32_t* grid_row, int32_t m_cap, int32_t* m_out) {
+  if (!h || !lhs || n < 0 || (n > 0 && (!kind_a || !idx_a || !kind_b || !idx_b))) return OBVI_ERR_INVALID_ARGUMENT;
+  for (int64_t i = 0; i < n; ++i)
+    for (int side = 0; side < 2; ++side) {
+      const int kind = side ? kind_b[i] : kind_a[i]; const uint32_t idx = side ? idx_b[i] : idx_a[i];
+      if (kind > OBVI_COV_OBJECT) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "cov_debug_compute_pairs: unknown block kind");
+      if ((int64_t)idx >= block_count(h, kind)) return fail(h, OBVI_ERR_OUT_OF_RANGE, "cov_debug_compute_pairs: index out of range");
+    }
+  if (!check_ready(h)) return fail(h, OBVI_ERR_NOT_READY, "cov_debug_compute_pairs: cameras not set");
+  OBVI_API_BEGIN
+  OBVI_HIP(hipSetDevice(h->device));
+  { const int vrc = validate_indices(h); if (vrc != OBVI_OK) return vrc; }
+  if (exchanging(h)) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "cov_debug_compute_pairs: the handle exchanges shared objects; the entry inverts a rank's own system only");
+  if (h->mask_dirty) h->dirty = true;   // (as obvi_ba_debug_reduced_system)
+  prepare(h);
+  if (m_out) *m_out = (int32_t)h->m_canon;
+  if (h->m_canon > m_cap) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "cov_debug_compute_pairs: buffer too small");
+  const int64_t mc = h->m_canon, nt = h->nt;
+  if (mc == 0 || h->m == 0 || h->num_params == 0) return cov_pass(h, "cov_debug_compute_pairs", n, kind_a, idx_a, kind_b, idx_b);
+  hipStream_t s = h->stream;
+  constexpr int64_t TT = (int64_t)kTile * kTile;
+  std::vector<double> tiles((size_t)(nt * nt * TT));
+  std::vector<int32_t> tl((size_t)2 * h->ntiles);
+  h->d_tiles.download(tl.data(), tl.size(), s);
+  sync(h);
+  std::vector<uint8_t> mk((size_t)nt * nt, 0);   // tiles outside the structural mask are never written and never read
+  for (int t = 0; t < h->ntiles; ++t) mk[(size_t)tl[2 * t] * nt + tl[2 * t + 1]] = 1;
+  const bool given = lhs_in != nullptr;
+  if (given) {
+    for (int64_t ci = 0; ci < mc; ++ci)
+      for (int64_t cj = 0; cj < mc; ++cj) {
+        const double v = lhs_in[ci * mc + cj], w = lhs_in[cj * mc + ci];
+        if (!(v == w) && !(v != v && w != w)) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "cov_debug_compute_pairs: the given system is not symmetric");
+        const int64_t i = h->h_canon_row[ci], j = h->h_canon_row[cj];
+        if (v != 0.0 && !mk[(size_t)(std::max(i, j) / kTile) * nt + std::min(i, j) / kTile])
+          return fail(h, OBVI_ERR_INVALID_ARGUMENT, "cov_debug_compute_pairs: a non-zero entry of the given system lies outside the structural tile mask");
+      }
+  }
+  // between the step's assembly and its factorisation: the system as the factorisation is about to see it -- or the caller's, put in its place
+  const std::function<void()> between = [&] {
+    h->d_S.download(tiles.data(), tiles.size(), s);
+    sync(h);
+    if (!given) return;
+    for (int64_t ci = 0; ci < mc; ++ci) {   // real rows only: the padding rows keep the identity the step's clear gave them
+      const int64_t i = h->h_canon_row[ci];
+      for (int64_t cj = 0; cj < mc; ++cj) {
+        const int64_t j = h->h_canon_row[cj];
+        const int64_t r = std::max(i, j), c = std::min(i, j);
+        const size_t tix = (size_t)(r / kTile) * nt + (c / kTile);
+        if (!mk[tix]) continue;
+        const double v = lhs_in[ci * mc + cj];
+        tiles[tix * TT + (r % kTile) * kTile + (c % kTile)] = v;
+        if (r / kTile == c / kTile) tiles[tix * TT + (c % kTile) * kTile + (r % kTile)] = v;   // diagonal tiles are kept symmetric
+      }
+    }
+    OBVI_HIP(hipMemcpyAsync(h->d_S.get(), tiles.data(), tiles.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    sync(h);
+  };
+  const int rc = cov_pass(h, "cov_debug_compute_pairs", n, kind_a, idx_a, kind_b, idx_b, &between);
+  if (rc != OBVI_OK && rc != OBVI_ERR_NUMERICAL) return rc;
+  for (int64_t ci = 0; ci < mc; ++ci) {
+    const int64_t i = h->h_canon_row[ci];
+    if (grid_row) grid_row[ci] = (int32_t)i;
+    for (int64_t cj = 0; cj < mc; ++cj) {
+      const int64_t j = h->h_canon_row[cj];
+      const int64_t r = std::max(i, j), c = std::min(i, j);
+      const size_t tix = (size_t)(r / kTile) * nt + (c / kTile);
+      lhs[ci * mc + cj] = mk[tix] ? tiles[tix * TT + (r % kTile) * kTile + (c % kTile)] : 0.0;
+    }
+  }
+  return rc;
   OBVI_API_END(h)
 }
 

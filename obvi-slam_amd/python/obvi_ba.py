@@ -505,6 +505,27 @@ class BundleAdjuster:
         self._check(self._cov_fn("cov_compute_pairs")(self._h, C.c_int64(len(ia)), _ptr(ka, C.c_uint8), _ptr(ia, C.c_uint32), _ptr(kb, C.c_uint8), _ptr(ib, C.c_uint32)),
                     "cov_compute_pairs")
 
+    def covariance_debug_compute_pairs(self, kind_a=(), idx_a=(), kind_b=(), idx_b=(), lhs_in=None, m_cap=4096):
+        """covariance_compute_pairs on these pairs (none: covariance_compute), returning (S, grid_row): the system the pass inverts, canonical order, taken
+        between its assembly and its factorisation, and the row of the tile grid of every canonical index.  lhs_in: given values in place of the assembly.
+        A non-positive pivot or a NaN raises with status -6, an asymmetric system or an entry outside the structural tile mask with status -1."""
+        ka, ia, kb, ib = self._cov_pairs(kind_a, idx_a, kind_b, idx_b)
+        if lhs_in is not None:
+            lin = _f64(lhs_in)
+            if lin.ndim != 2 or lin.shape[0] != lin.shape[1]:
+                raise ObviError("cov_debug_compute_pairs: lhs_in is not square")
+            m_cap = len(lin)                      # (a handle whose system has more rows refuses; fewer is caught below)
+        lhs, row = np.zeros((m_cap, m_cap)), np.full(m_cap, -1, dtype=np.int32)
+        m = C.c_int32(0)
+        rc = self._cov_fn("cov_debug_compute_pairs")(self._h, C.c_int64(len(ia)), _ptr(ka, C.c_uint8), _ptr(ia, C.c_uint32), _ptr(kb, C.c_uint8), _ptr(ib, C.c_uint32),
+                                                     _ptr(lin, C.c_double) if lhs_in is not None else None, _ptr(lhs, C.c_double), _ptr(row, C.c_int32),
+                                                     C.c_int32(m_cap), C.byref(m))
+        if lhs_in is not None and rc in (0, -6) and m.value != len(lin):
+            raise ObviError("cov_debug_compute_pairs: the given system has %d rows, the handle's reduced system %d" % (len(lin), m.value))
+        self._check(rc, "cov_debug_compute_pairs")
+        mm = m.value
+        return lhs.ravel()[:mm * mm].reshape(mm, mm).copy(), row[:mm].copy()
+
     def _cov_own(self, name, idx, dim):
         i = np.ascontiguousarray(idx, dtype=np.uint32)
         out = np.zeros((len(i), dim, dim))

@@ -283,14 +283,16 @@ def fault_applies(sys_, fault):
     return True
 
 
-def emulate(S, b, grid_row, fault=None):
-    """y of S y = b (canonical order) by the tile algorithm; fault: one of FAULTS, planted once"""
+FACTOR_FAULTS = ("drop_update", "pad_zero", "inv_entry")
+
+
+def factor_tiles(S, grid_row, fault=None):
+    """(A, inv, M): the padded grid with the factor tiles L_ik (i >= k; L_kk with a zero upper part) where the mask M holds, the explicit inverses L_kk^-1, and
+    the fill-closed tile mask -- the part of the tile algorithm the solve and the covariance pass (tests/cov_cases.py) share; fault: one of FACTOR_FAULTS"""
     perm, rows, nt = grid(grid_row)
     n = nt * TILE
     A = np.eye(n)
     A[np.ix_(rows, rows)] = np.asarray(S, np.float64)[np.ix_(perm, perm)]
-    z = np.zeros(n)
-    z[rows] = np.asarray(b, np.float64)[perm]
     todo = fault
     if todo == "pad_zero":
         pad = np.setdiff1d(np.arange(n), rows)
@@ -298,7 +300,6 @@ def emulate(S, b, grid_row, fault=None):
         todo = None
     M = tile_mask(S, grid_row)
     T = lambda i, j: (slice(i * TILE, (i + 1) * TILE), slice(j * TILE, (j + 1) * TILE))  # noqa: E731
-    V = lambda i: slice(i * TILE, (i + 1) * TILE)  # noqa: E731
     inv = [None] * nt
     with np.errstate(all="ignore"):
         for k in range(nt):
@@ -309,15 +310,9 @@ def emulate(S, b, grid_row, fault=None):
                 inv[k][r, r] *= 1.0 + 1e-9
                 todo = None
             A[T(k, k)] = Lkk
-            z[V(k)] = inv[k] @ z[V(k)]
             col = [i for i in range(k + 1, nt) if M[i, k]]
             for i in col:
                 A[T(i, k)] = A[T(i, k)] @ inv[k].T
-            for i in col:
-                if todo == "skip_rhs":
-                    todo = None
-                    continue
-                z[V(i)] -= A[T(i, k)] @ z[V(k)]
             for i in col:
                 for j in col:
                     if j > i:
@@ -326,6 +321,30 @@ def emulate(S, b, grid_row, fault=None):
                         todo = None
                         continue
                     A[T(i, j)] -= A[T(i, k)] @ A[T(j, k)].T
+    assert todo is None, "the fault %r found no place in this system" % (fault,)
+    return A, inv, M
+
+
+def emulate(S, b, grid_row, fault=None):
+    """y of S y = b (canonical order) by the tile algorithm; fault: one of FAULTS, planted once"""
+    perm, rows, nt = grid(grid_row)
+    n = nt * TILE
+    A, inv, M = factor_tiles(S, grid_row, fault if fault in FACTOR_FAULTS else None)
+    todo = None if fault in FACTOR_FAULTS else fault
+    z = np.zeros(n)
+    z[rows] = np.asarray(b, np.float64)[perm]
+    T = lambda i, j: (slice(i * TILE, (i + 1) * TILE), slice(j * TILE, (j + 1) * TILE))  # noqa: E731
+    V = lambda i: slice(i * TILE, (i + 1) * TILE)  # noqa: E731
+    with np.errstate(all="ignore"):
+        for k in range(nt):                                   # (tile row i takes its terms in the order of k, as when this ran inside the factorisation)
+            z[V(k)] = inv[k] @ z[V(k)]
+            for i in range(k + 1, nt):
+                if not M[i, k]:
+                    continue
+                if todo == "skip_rhs":
+                    todo = None
+                    continue
+                z[V(i)] -= A[T(i, k)] @ z[V(k)]
         yg = np.zeros(n)
         for k in range(nt - 1, -1, -1):
             t = z[V(k)].copy()
