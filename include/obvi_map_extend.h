@@ -31,7 +31,8 @@
  * window with nothing new is the conditioning entries' case); k_old < 0; k_old > 0 with a null map or map_idx; a map on another device or of another block size
  * than the handle's; a map object twice; (k_old + k_new) od > OBVI_MAP_GROUP_MAX_ROWS; a result above the size obvi_map_create accepts (a covariance of 1 GiB);
  * for the handle form also null index lists, a session object twice across both lists, a constant session object, a handle that exchanges shared objects
- * (decided from what was set -- an all-reduce hook and at least one shared object -- not from the plan: no collective is entered).  OBVI_ERR_OUT_OF_RANGE:
+ * (decided from what was set -- an all-reduce hook and at least one shared object -- not from the plan: no collective is entered; with obvi_map_allow_exchange
+ * on -- obvi_map_shared.h -- the handle form runs on such a handle instead: the posterior is the joint one and the call is collective).  OBVI_ERR_OUT_OF_RANGE:
  * map_idx >= n, an object index >= O.  OBVI_ERR_NUMERICAL: a non-finite entry of post_mean / post_cov.  The handle form also returns OBVI_ERR_NOT_READY while
  * the handle has reprojection or bounding-box factors and no cameras, the status of the problem's own validation, and -- once the plan is known, before
  * anything is allocated for the new map -- OBVI_ERR_INVALID_ARGUMENT for a session object that no active factor touches.

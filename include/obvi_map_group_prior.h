@@ -34,8 +34,9 @@
  * (d still holds its offset); all members constant: the cost is part of the fixed cost; a member that only a group prior touches is a variable.
  * The members of active groups are eliminated last, group after group in the caller's order.
  *
- * NOT COLLECTIVE: a handle that exchanges shared objects (obvi_ba_set_shared_objects and an exchange hook) refuses a problem that holds group
- * priors with OBVI_ERR_INVALID_ARGUMENT before any collective is issued.  Not built either: a conditional form for groups.
+ * NOT COLLECTIVE BY DEFAULT: a handle that exchanges shared objects (obvi_ba_set_shared_objects and an exchange hook) refuses a problem that holds group
+ * priors with OBVI_ERR_INVALID_ARGUMENT before any collective is issued -- unless the caller switched the collective form on for that handle
+ * (obvi_map_allow_exchange, obvi_map_shared.h, which states its calling rules: exactly one member uploads a given prior).  Not built: a conditional form for groups.
  */
 #ifndef OBVI_MAP_GROUP_PRIOR_H_
 #define OBVI_MAP_GROUP_PRIOR_H_

@@ -28,8 +28,9 @@
  * residuals (2od per factor) and block norms after the relative-pose factors; obvi_ba_num_residuals counts them.  Constness follows types 4
  * and 5: a constant a leaves b's diagonal block and gradient (d still holds a's offset); both constant: the cost is part of the fixed cost.
  *
- * NOT COLLECTIVE: a handle that exchanges shared objects (obvi_ba_set_shared_objects and an exchange hook) refuses a problem that holds pair
- * priors with OBVI_ERR_INVALID_ARGUMENT before any collective is issued.
+ * NOT COLLECTIVE BY DEFAULT: a handle that exchanges shared objects (obvi_ba_set_shared_objects and an exchange hook) refuses a problem that holds pair
+ * priors with OBVI_ERR_INVALID_ARGUMENT before any collective is issued -- unless the caller switched the collective form on for that handle
+ * (obvi_map_allow_exchange, obvi_map_shared.h, which states its calling rules: exactly one member uploads a given prior).
  */
 #ifndef OBVI_MAP_PRIOR_H_
 #define OBVI_MAP_PRIOR_H_

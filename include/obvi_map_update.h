@@ -32,6 +32,7 @@
  * bounding-box factors and no cameras, and the status of the problem's own validation.  It refuses a session object that no active factor touches (it is
  * no variable of the solve and has no covariance) with OBVI_ERR_INVALID_ARGUMENT once the plan is known, before anything is allocated for the new map.
  * "Exchanges shared objects" is decided from what was set -- an all-reduce hook and at least one shared object -- not from the plan: no collective is entered.
+ * (With obvi_map_allow_exchange on -- obvi_map_shared.h -- the handle form runs on such a handle instead: the posterior is the joint one and the call is collective.)
  * Refused from what the device reports (OBVI_ERR_NUMERICAL, nothing left allocated): Cs_AA fails the pivot or condition tests of
  * obvi_map_set_group_priors_from_map (the same status record, the same thresholds); a non-finite entry in the result; for the handle form rank-deficient
  * normal equations, as obvi_ba_object_covariances reports them.

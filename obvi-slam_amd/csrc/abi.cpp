@@ -3,6 +3,7 @@
 // One handle == one GPU == one HIP stream pair.  There is no CPU compute path in this library: without a HIP device obvi_ba_create fails with
 // OBVI_ERR_NO_DEVICE.
 #include "ba_handle.h"
+#include "../../include/obvi_map_shared.h"
 
 namespace obvi {
 hipStream_t handle_stream(obvi_ba_handle* h) { return h->stream; }
@@ -211,7 +212,7 @@ int obvi_ba_reset(obvi_ba_handle* h) {
   if (rc) return rc;
   OBVI_API_BEGIN
   h->h_is_shared.clear(); h->h_shared_ov.clear(); h->rank = 0; h->world = 1; h->tail_t0 = -1; h->tail_level0 = -1;
-  h->allreduce = nullptr; h->allreduce_user = nullptr;
+  h->allreduce = nullptr; h->allreduce_user = nullptr; h->map_exchange = false;
   h->have_snapshot = false; h->use_extra = false; h->pc_valid = false; h->lin_valid = false; h->tiles_cleared = false;
   h->iterations.clear();
   h->profiling = 0; h->ck_used = 0;
@@ -637,6 +638,13 @@ int obvi_ba_set_shared_objects(obvi_ba_handle* h, const uint8_t* is_shared, int3
 int obvi_ba_set_allreduce(obvi_ba_handle* h, obvi_allreduce_fn fn, void* user) {
   if (!h) return OBVI_ERR_INVALID_ARGUMENT;
   h->allreduce = fn; h->allreduce_user = user;
+  return OBVI_OK;
+}
+
+int obvi_map_allow_exchange(obvi_ba_handle* h, int32_t on) {
+  if (!h || (on != 0 && on != 1)) return OBVI_ERR_INVALID_ARGUMENT;
+  // read by validate_indices and check_session_objects alone: no device call, and the plan does not depend on it
+  h->map_exchange = on != 0;
   return OBVI_OK;
 }
 

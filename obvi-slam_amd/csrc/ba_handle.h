@@ -279,6 +279,7 @@ struct obvi_ba_handle {
   obvi_allreduce_fn allreduce = nullptr;
   void* allreduce_user = nullptr;
   std::vector<uint8_t> h_is_shared;      // per object index (caller order)
+  bool map_exchange = false;             // obvi_map_allow_exchange: map pair / group priors and the map's handle forms run on a handle that exchanges (include/obvi_map_shared.h)
   int32_t rank = 0, world = 1;
   double tail_order_hash = 0.0;          // 40-bit hash (as double) of the shared objects' indices in tail order (plan.cpp)
   std::vector<int32_t> h_shared_ov;      // reduced object indices of the shared objects in the order of the tail (the same on every rank: plan.cpp)
@@ -612,10 +613,10 @@ inline int validate_indices(obvi_ba_handle* h) {
     if (f.n > 0 && (f.max_pose >= h->P || f.max_point >= h->L || f.max_obj >= h->O || f.max_cam >= ncam)) return bad(f.name);
   if (h->n_rp > 0 && (int64_t)h->h_point_ptr.size() != h->L + 1) return bad("reprojection factors (point count changed)");
   // map pair priors couple two object blocks on one handle; across handles that exchange shared objects they are not built (include/obvi_map_prior.h):
-  // refused here, before the plan and before any collective
-  if (h->n_mp > 0 && h->allreduce != nullptr && std::any_of(h->h_is_shared.begin(), h->h_is_shared.end(), [](uint8_t v) { return v != 0; }))
+  // refused here, before the plan and before any collective -- unless the caller switched the collective form on (obvi_map_allow_exchange, include/obvi_map_shared.h)
+  if (h->n_mp > 0 && !h->map_exchange && h->allreduce != nullptr && std::any_of(h->h_is_shared.begin(), h->h_is_shared.end(), [](uint8_t v) { return v != 0; }))
     return fail(h, OBVI_ERR_INVALID_ARGUMENT, "map pair priors on a handle that exchanges shared objects: the collective form is not built");
-  if (h->n_mg > 0 && h->allreduce != nullptr && std::any_of(h->h_is_shared.begin(), h->h_is_shared.end(), [](uint8_t v) { return v != 0; }))
+  if (h->n_mg > 0 && !h->map_exchange && h->allreduce != nullptr && std::any_of(h->h_is_shared.begin(), h->h_is_shared.end(), [](uint8_t v) { return v != 0; }))
     return fail(h, OBVI_ERR_INVALID_ARGUMENT, "map group priors on a handle that exchanges shared objects: the collective form is not built");
   if (h->n_mg > 0 && h->n_mp > 0) {   // a pair prior inside a group: the pair's block would have two writers, its information would count twice
     std::vector<int32_t> group_of((size_t)h->O, -1);

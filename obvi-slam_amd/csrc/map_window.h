@@ -42,8 +42,9 @@ inline int check_session_objects(obvi_ba_handle* h, int64_t k, const uint32_t* o
   for (int64_t i = 0; i < k; ++i) if ((int64_t)obj_idx[i] >= h->O) return fail(h, OBVI_ERR_OUT_OF_RANGE, what + ": object index out of range");
   if (twice(obj_idx, k)) return fail(h, OBVI_ERR_INVALID_ARGUMENT, what + ": a session object twice");
   for (int64_t i = 0; i < k; ++i) if (h->h_object_const[obj_idx[i]]) return fail(h, OBVI_ERR_INVALID_ARGUMENT, what + ": a constant object has no posterior");
-  // the flags, not the plan's list: a handle that has not planned yet exchanges as soon as it does (validate_indices refuses group priors by the same test)
-  if (h->allreduce != nullptr && std::any_of(h->h_is_shared.begin(), h->h_is_shared.end(), [](uint8_t v) { return v != 0; })) return fail(h, OBVI_ERR_INVALID_ARGUMENT, what + ": the handle exchanges shared objects");
+  // the flags, not the plan's list: a handle that has not planned yet exchanges as soon as it does (validate_indices refuses group priors by the same test);
+  // with obvi_map_allow_exchange on, the posterior is the joint one and the pass is collective (include/obvi_map_shared.h)
+  if (!h->map_exchange && h->allreduce != nullptr && std::any_of(h->h_is_shared.begin(), h->h_is_shared.end(), [](uint8_t v) { return v != 0; })) return fail(h, OBVI_ERR_INVALID_ARGUMENT, what + ": the handle exchanges shared objects");
   return OBVI_OK;
 }
 

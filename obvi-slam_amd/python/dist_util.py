@@ -329,6 +329,41 @@ def joint_long_term_map(handles, shared_ids, cross_pairs=None, timeout_s=600.0):
     return dict(ids=ids, mean=h0.get_objects()[ids], cov=h0.object_covariance_blocks(ids), cross=cross)
 
 
+def resident_map_prior(handles, map, obj_idx, map_idx, huber=1.0, uploader=0):
+    """The first arrow of the loop for a CONCURRENT job whose map lives on the device (include/obvi_map_shared.h): every member of this rank
+    (`handles`) switches the collective form of the map entries on, and ONE member of the whole job -- `uploader`, an index into `handles`; None on the ranks
+    that do not hold it -- cuts the job's group prior from `map`: the session objects obj_idx are the map objects map_idx.  Exactly one member uploads a prior:
+    cut by two it would count twice."""
+    for h in handles:
+        h.map_allow_exchange(True)
+    if uploader is not None:
+        handles[uploader].set_map_group_priors_from_map(map, [list(obj_idx)], [list(map_idx)], huber)
+
+
+def joint_resident_map(handles, map, obj_idx, map_idx, new_obj=(), folding=(0,), timeout_s=600.0):
+    """The resident-map form of joint_long_term_map: the last arrow of the loop.  After the joint solve every member of the job enters ONE collective pass (the
+    four collectives of obvi_ba_object_covariances); the members `folding` (indices into `handles`; the other ranks may pass none) fold the JOINT posterior
+    of the session objects obj_idx -- the map objects map_idx -- back into `map` on the device, with the session objects new_obj appended where given
+    (Map.condition_on / Map.extend_on; map None: a first map is born from new_obj), and every other member joins through object_covariances([]), whose
+    sequence is the same.  Nothing of the posterior crosses to the host.  Returns {member: the new obvi_ba.Map}; `map` is not written."""
+    import numpy as np
+    import obvi_ba
+    fresh = np.ascontiguousarray(new_obj, dtype=np.uint32)
+
+    def fold(h):
+        if map is None:
+            return obvi_ba.Map.from_handle(h, fresh)
+        return map.extend_on(h, obj_idx, map_idx, fresh) if len(fresh) else map.condition_on(h, obj_idx, map_idx)
+    res = run_members([(lambda h=h: fold(h)) if m in folding else (lambda h=h: h.object_covariances([])) for m, h in enumerate(handles)], timeout_s)
+    for r in res:
+        if isinstance(r, Exception):
+            for x in res:
+                if hasattr(x, "close"):
+                    x.close()
+            raise r
+    return {m: res[m] for m in folding}
+
+
 class HostGroup:
     """The group for libraries whose exchange buffers live in HOST memory (the CPU oracle; tests/test_distributed_gloo.py): k handles of this
     process, one thread each; per collective the last one to arrive sums / maximises the k buffers, runs ONE inter-rank all-reduce

@@ -691,6 +691,15 @@ class BundleAdjuster:
         m = None if is_shared is None else np.ascontiguousarray(is_shared, dtype=np.uint8)
         self._check(self._fn("ba_set_shared_objects")(self._h, _ptr(m, C.c_uint8), C.c_int32(rank), C.c_int32(world)), "set_shared_objects")
 
+    def map_allow_exchange(self, on=True):
+        """Joint map priors and Map.condition_on / extend_on / from_handle on a handle that exchanges shared objects (include/obvi_map_shared.h): off by default."""
+        try:
+            f = getattr(self._lib, self._pre + "map_allow_exchange")
+        except AttributeError:
+            raise ObviError("%smap_allow_exchange: this library has no collective map entries (include/obvi_map_shared.h is served by libobvi_ba.so only)" % self._pre)
+        f.restype = C.c_int
+        self._check(f(self._h, C.c_int32(int(on))), "map_allow_exchange")
+
     def measure_peaks(self):
         """HBM triad / copy / read bandwidth (GB/s) and the fp64 MFMA rates (TFLOP/s) of this device (obvi_ba_measure_peaks)."""
         class Peaks(C.Structure):

@@ -7,7 +7,10 @@ on the device, one read-back).  Each entry is called once before it is timed (it
 map, against the round trip through the host that gives the same map without them.
 --extend: a map that grows -- obvi_map_extend_on_handle and obvi_map_extend at 70 and 210 window rows of which 14 and 42 belong to objects
 the map lacks, against the round trip that grows the map without them: obvi_map_get, object_covariances of all pairs, numpy, obvi_map_create.
-usage (GPU box, repo root): python scripts/map_bench.py [--update | --extend]"""
+--shared K: K concurrent sessions of 500 frames / 50 000 features over 50 shared objects behind one group: ms per joint LM step without and
+with the whole-map group prior on member 0, and the wall time of the collective obvi_map_condition_on_handle (every member folds all 50 objects back) against
+the same call on ONE handle that holds the joint problem.
+usage (GPU box, repo root): python scripts/map_bench.py [--update | --extend | --shared K]"""
 import os
 import sys
 import time
@@ -202,5 +205,68 @@ def extend():
     mp.close()
 
 
+def shared(n_sessions):
+    """the map entries on handles that exchange shared objects."""
+    import dist_util
+    n_obj, steps = 50, 10
+    ids = np.arange(n_obj, dtype=np.uint32)
+    sessions = synth.make_sessions(n_sessions, P=500, L=50000, O=n_obj, seed0=1000, object_seed=77, const_poses=1, min_obj_obs=10, object_classes=("bench",))
+    rng = np.random.default_rng(1)
+    mean, cov = sessions[0]["objects"] - rng.normal(scale=0.02, size=(n_obj, OD)), spd(rng, n_obj * OD)
+    prm = obvi_ba.SolverParams(max_num_iterations=steps, allow_non_monotonic_steps=True, function_tolerance=0.0, gradient_tolerance=0.0, parameter_tolerance=0.0,
+                               initial_trust_region_radius=100.0, max_trust_region_radius=1e4)
+    mp = obvi_ba.Map.create(mean, cov, object_block_size=OD)
+
+    def job(prior):
+        group = dist_util.RcclGroup(n_sessions)
+        group.set_timeout(120.0)
+        handles = []
+        for m, q in enumerate(sessions):
+            ba = obvi_ba.BundleAdjuster(object_block_size=OD)
+            synth.upload(ba, q)
+            group.attach(m, ba, np.ones(n_obj, np.uint8))
+            handles.append(ba)
+        dist_util.resident_map_prior(handles, mp, ids, ids, huber=1e6, uploader=0 if prior else None)
+        ms = []
+        for _ in range(1 + 3):                                     # (the first solve plans and allocates: not timed)
+            for h, q in zip(handles, sessions):
+                h.update_state(poses=q["poses"], points=q["points"], objects=q["objects"])
+            t0 = time.perf_counter()
+            out = dist_util.run_members([lambda h=h: h.solve(prm) for h in handles])
+            dt = time.perf_counter() - t0
+            for o in out:
+                if isinstance(o, Exception):
+                    raise o
+            ms.append(1e3 * dt / max(1, out[0].num_iterations - 1))
+        return group, handles, ms[1:], out[0]
+    for prior in (False, True):
+        group, handles, ms, s = job(prior)
+        print("%d sessions x 500 frames over %d shared objects, %s: %.3f ms per joint LM step (median of 3 solves of %d steps: %s), final cost %.6e"
+              % (n_sessions, n_obj, "whole-map group prior on member 0" if prior else "no map prior", float(np.median(ms)), s.num_iterations - 1, " ".join("%.3f" % x for x in ms), s.final_cost))
+        if prior:
+            def fold_all():
+                for m in dist_util.joint_resident_map(handles, mp, ids, ids, folding=tuple(range(n_sessions))).values():
+                    m.close()
+            coll, _ = timed(fold_all)
+            print("collective condition_on_handle, every one of %d members folds %d rows back: %s" % (n_sessions, n_obj * OD, coll))
+        for h in handles:
+            h.close()
+        group.close()
+    one = obvi_ba.BundleAdjuster(object_block_size=OD)
+    synth.upload(one, synth.join_problems(sessions))
+    one.set_map_group_priors_from_map(mp, [list(ids)], [list(ids)], 1e6)
+    one.solve(prm)
+
+    def fold_one():
+        mp.condition_on(one, ids, ids).close()
+    alone, _ = timed(fold_one)
+    print("condition_on_handle on ONE handle that holds the joint problem: %s" % alone)
+    one.close()
+    mp.close()
+
+
 if __name__ == "__main__":
+    if "--shared" in sys.argv[1:]:
+        shared(int(sys.argv[sys.argv.index("--shared") + 1]))
+        sys.exit(0)
     extend() if "--extend" in sys.argv[1:] else update() if "--update" in sys.argv[1:] else main()

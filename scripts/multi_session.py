@@ -6,8 +6,12 @@ s-1 (ellipsoid estimates + marginal covariances as IndependentObjectMapFactor pr
 extracting the new map on the device.  Prints per-session times and the map's error against the synthetic truth.
 usage: python scripts/multi_session.py [sessions=16] [objects=200]
        python scripts/multi_session.py --concurrent [sessions=4] [objects=50]
+       python scripts/multi_session.py --concurrent --resident-map [sessions=4] [objects=50]
 --concurrent: the sessions run at the same time instead, one handle each behind one group, as ONE joint solve over the shared map, and the job ends
-with the map of the joint solve (the collective obvi_cov_compute through dist_util.joint_long_term_map): estimates and joint covariances of the shared objects."""
+with the map of the joint solve (the collective obvi_cov_compute through dist_util.joint_long_term_map): estimates and joint covariances of the shared objects.
+--resident-map (with --concurrent): TWO concurrent jobs chained through a map that never leaves the device: the first job's joint posterior is
+born as an obvi_ba.Map, member 0 of the second job cuts its group prior over all objects from that map, and the second job's joint posterior is folded back
+into it -- dist_util.resident_map_prior / joint_resident_map.  Only the report at the end reads a map back."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "obvi-slam_amd", "python")]
@@ -15,7 +19,8 @@ import numpy as np
 import obvi_ba, synth
 
 concurrent = "--concurrent" in sys.argv
-args = [a for a in sys.argv[1:] if a != "--concurrent"]
+resident = "--resident-map" in sys.argv
+args = [a for a in sys.argv[1:] if a not in ("--concurrent", "--resident-map")]
 n_sessions = int(args[0]) if len(args) > 0 else (4 if concurrent else 16)
 n_objects = int(args[1]) if len(args) > 1 else (50 if concurrent else 200)
 prm = obvi_ba.SolverParams(max_num_iterations=50, allow_non_monotonic_steps=True, function_tolerance=1e-4, gradient_tolerance=1e-10,
@@ -52,8 +57,47 @@ def concurrent_sessions():
     group.close()
 
 
+def resident_map_chain():
+    import dist_util
+    ids = np.arange(n_objects, dtype=np.uint32)
+    mp = None
+    for job in range(2):
+        sessions = synth.make_sessions(n_sessions, P=500, L=50000, O=n_objects, seed0=1000 + 100 * job, object_seed=77, const_poses=1, min_obj_obs=10, object_classes=("bench",))
+        group = dist_util.RcclGroup(n_sessions)
+        group.set_timeout(120.0)
+        handles = []
+        for m, q in enumerate(sessions):
+            ba = obvi_ba.BundleAdjuster(device_id=0)
+            synth.upload(ba, q)
+            group.attach(m, ba, np.ones(n_objects, np.uint8))
+            handles.append(ba)
+        t0 = time.time()
+        dist_util.resident_map_prior(handles, mp, ids, ids, huber=1e6, uploader=0 if mp is not None else None)   # job 0: the switch alone, there is no map yet
+        t1 = time.time()
+        out = dist_util.run_members([lambda h=h: h.solve(prm) for h in handles])
+        for o in out:
+            if isinstance(o, Exception):
+                raise o
+        t2 = time.time()
+        new = dist_util.joint_resident_map(handles, mp, ids, ids, new_obj=ids if mp is None else ())[0]
+        t3 = time.time()
+        if mp is not None:
+            mp.close()
+        mp = new
+        mean, cov = mp.get()                                      # (the report alone: the chain itself never reads the map back)
+        err = np.linalg.norm(mean[:, :3] - sessions[0]["gt_objects"][:, :3], axis=1)
+        sd = np.sqrt(np.diag(cov).reshape(-1, 7)[:, :3]).mean(axis=1)
+        print("job %d: %d concurrent sessions over %d objects%s: prior cut %.2f ms | joint solve %.1f ms (%d iterations, final cost %.6e) | posterior folded into the map %.2f ms (%d collectives in all) | centre error median %.3f m, sigma median %.3f m"
+              % (job, n_sessions, n_objects, "" if job == 0 else ", prior from the resident map", (t1 - t0) * 1e3, (t2 - t1) * 1e3, out[0].num_iterations, out[0].final_cost, (t3 - t2) * 1e3, group.stats()[0],
+                 np.median(err), np.median(sd)), flush=True)
+        for ba in handles:
+            ba.close()
+        group.close()
+    mp.close()
+
+
 if concurrent:
-    concurrent_sessions()
+    resident_map_chain() if resident else concurrent_sessions()
     sys.exit(0)
 ltm = None   # (object ids, means, covariances)
 g = obvi_ba.BundleAdjuster(device_id=0)
