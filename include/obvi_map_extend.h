@@ -44,7 +44,8 @@
  * obvi_map_select builds a new map of the objects map_idx[0..k) of `map`, in that order: a subset is their marginal, k = n a permutation.  Means and
  * covariance entries are copied exactly as the device holds them; nothing is symmetrised.  One gather on the handle's stream, one wait.  Refused: null
  * pointers, k < 1, a map on another device or of another block size, a map object twice (OBVI_ERR_INVALID_ARGUMENT); map_idx >= n (OBVI_ERR_OUT_OF_RANGE).
- * There is no row limit: k may be any 1 .. n.  This is what a session-end merge of duplicate objects, or a bound on the map's size, needs.
+ * There is no row limit: k may be any 1 .. n.  This is what a bound on the map's size needs.  (Dropping a duplicate this way throws its estimate away and moves
+ * nothing else; fusing duplicates is conditioning over the whole map, an entry of its own.)
  *
  * No sum depends on the order in which workgroups run: the same call twice gives bit-identical maps, on default and deterministic handles alike.
  */

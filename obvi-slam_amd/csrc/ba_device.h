@@ -216,6 +216,8 @@ void launch_map_cut(hipStream_t s, const MapCutDev& m, int nt_max, const double*
 // the condition test reads).
 void launch_map_factor(hipStream_t s, const MapCutDev& m, int nt_max, const double* map_mean, const double* map_cov, int64_t ldc);
 void launch_map_condition_estimate(hipStream_t s, const MapCutDev& m, int nt_max, const double* x0);
+// ... and the factor without its gather: Cholesky and W of an A (lower tiles, identity padding) that another launch filled on the stream
+void launch_map_factorize(hipStream_t s, const MapCutDev& m, int nt_max);
 
 // A map conditioned on the posterior of some of its objects (include/obvi_map_update.h; map_kernels.hip): C' = Cs - Z Y^T, mu' = mu + Y v with Y = Cs[:, A] W^T,
 // Z = Y (I - W Ps W^T), v = W (m - mu_A), W = L^-1 of Cs_AA = L L^T -- the factor of a one-group cut of the window's objects A, which ran before on the stream and
@@ -246,6 +248,23 @@ void launch_map_update(hipStream_t s, const MapUpdateDev& u);
 void launch_map_extend(hipStream_t s, const MapUpdateDev& u);
 // out[i][j] = cov[rows(i)][rows(j)], out_mean[i] = mean[rows(i)] for the k objects idx of a map of ldc rows: a copy, nothing is symmetrised
 void launch_map_select(hipStream_t s, const uint32_t* idx, int32_t k, int32_t od, const double* mean, const double* cov, int64_t ldc, double* out_mean, double* out_cov);
+// Duplicate objects of a map merged (include/obvi_map_merge.h; map_kernels.hip): pair r says x[drop_r] - x[keep_r] = d_r (+ noise R_r).  With H the Q = q od
+// constraint rows (+I at drop, -I at keep), G = Cs H^T, T = H G + R = L L^T, W = L^-1, Y = G W^T:  C' = Cs - Y Y^T, mu' = mu - Y W (H mu - d), on the NK rows
+// of the objects `kept` (those not dropped, in their old order).  T is built in a one-group cut of Q rows (cut.A, cut.Csym; cut.mean gets H mu - d; the cut's
+// map_idx is the drop list), factored and tested as any cut; G and Y are [nK][nQ] tiles of kept rows only, Wn [nQ][nQ]: W as tiles.
+struct MapMergeDev {
+  int32_t od, N, Q, NK, nQ, nK;                              // map rows, constraint rows, kept rows; the latter two in tiles of 64
+  MapCutDev cut;                                             // the one-group cut that holds T and its factor
+  const uint32_t* keep; const uint32_t* kept;                // [Q / od] the pairs' survivors; [NK / od] the objects of the new map
+  const double* offset; const double* noise;                 // [Q] d (never NULL: zeros); [Q / od][od][od] as given (not symmetrised), NULL: exact
+  const double* map_mean; const double* map_cov;             // the old map: [N], [N][N]
+  double* Wn; double* G; double* Y; double* v;               // tiles; v [64 nQ] = W (H mu - d)
+  double* out_mean; double* out_cov;                         // the new map: [NK], [NK][NK]
+  double* status;                                            // the cut's record; MS_NONFINITE as in MapUpdateDev
+};
+// T and H mu - d into the cut, its factor and condition estimate (x0: the map's start vector), G, Wn, Y, the hot launch C', v, mu'.  The cut's W and the padding
+// of its Lambda, and status, must have been zeroed on the stream.
+void launch_map_merge(hipStream_t s, const MapMergeDev& g, const double* x0);
 // the posterior of the handle form: the k x k blocks of launch_cov_pairs (pair a k + b: objects a, b) -> dense P, and the objects' current values -> pm
 void launch_map_posterior_layout(hipStream_t s, const double* blocks, const double* objects, const uint32_t* obj_idx, int32_t k, int32_t od, double* P, double* pm);
 

@@ -194,6 +194,8 @@ struct obvi_ba_handle {
   DevBuf<double> d_mc_A, d_mc_Li, d_mc_Wt, d_mc_Csym, d_mc_x, d_mc_partial, d_mc_status;
   // obvi_map_condition* / obvi_map_extend* (map_update.cpp, map_extend.cpp): the posterior as uploaded or laid out (covariance, then mean), the window's session objects, the tile operands of MapUpdateDev
   DevBuf<double> d_mu_post, d_mu_tiles; DevBuf<uint32_t> d_mu_obj;
+  // obvi_map_merge (map_merge.cpp): the pairs' survivors and the new map's objects, the offsets followed by the noise blocks, the tile operands of MapMergeDev
+  DevBuf<uint32_t> d_mm_keep, d_mm_kept; DevBuf<double> d_mm_in, d_mm_tiles;
   DevBuf<double> d_bb_blk;                                    // per-factor blocks of the bounding-box factors (k_bbox_gather)
   DevBuf<double> d_sm_blk; DevBuf<uint32_t> d_smt_ptr, d_smt_idx;   // deterministic mode: the same for the priors and relative-pose factors (k_small_gather)
   int32_t bb_pairs_unique = 1;

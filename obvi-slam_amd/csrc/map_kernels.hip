@@ -8,7 +8,9 @@
 // and Csym, the sub-block again as N rows of ld doubles (the layout of Lambda), for the power steps on C.
 // Second half of the file: a map conditioned on the posterior of a window's objects (include/obvi_map_update.h, MapUpdateDev): tile products on the factor of a
 // one-group cut, under the same rules.  Third part: the map grown by the window's new objects, born from a posterior, or gathered down to some of its objects
-// (include/obvi_map_extend.h): the same launches into a larger map, the cross block, and the scatter of the window's whole block.
+// (include/obvi_map_extend.h): the same launches into a larger map, the cross block, and the scatter of the window's whole block.  Fourth part: duplicate
+// objects of the map merged (include/obvi_map_merge.h): the innovation covariance of the pairs built in a one-group cut and factored as any cut, the gain tiles
+// of the surviving rows alone, and the downdate written straight into the smaller map.
 #include "chol_tile.h"
 
 namespace obvi {
@@ -611,6 +613,204 @@ __global__ void __launch_bounds__(kThreads) k_map_select(const uint32_t* __restr
   if (blockIdx.x == 0 && tid < T && rows[tid] >= 0) out_mean[T * blockIdx.y + tid] = mean[rows[tid]];
 }
 
+// ==== duplicate objects of the map merged (include/obvi_map_merge.h; MapMergeDev, ba_device.h) ===========================================================
+// Under the rules above.  Constraint row w belongs to pair w / od: its two map rows are the drop object's (the cut's map_idx) and the keep object's; -1: padding.
+__device__ __forceinline__ void merge_rows(const MapMergeDev& g, int w, int32_t& b, int32_t& k) {
+  b = k = -1;
+  if (w < g.Q) { const int p = w / g.od, c = w % g.od; b = (int32_t)g.cut.map_idx[p] * g.od + c; k = (int32_t)g.keep[p] * g.od + c; }
+}
+// map row of row w of the new map
+__device__ __forceinline__ int32_t merge_kept_row(const MapMergeDev& g, int w) { return w < g.NK ? (int32_t)g.kept[w / g.od] * g.od + w % g.od : -1; }
+
+// (ti, tj <= ti): T_ij = Cs[b_i, b_j] - Cs[b_i, k_j] - Cs[k_i, b_j] + Cs[k_i, k_j] + Rs, in that order, every Cs entry formed as k_map_gather forms it (the two
+// blocks of the map read along their rows, met in LDS).  Into the cut's A (lower tiles, identity padding) and both triangles of Csym; a diagonal tile is taken
+// from its lower triangle, so T is symmetric bit for bit.  Tile column 0 also writes its rows of H mu - d into the cut's mean.
+__global__ void __launch_bounds__(kThreads) k_mm_innovation(MapMergeDev g) {
+  __shared__ double P[T * LDM];
+  __shared__ double Qs[T * LDM];
+  __shared__ int32_t ri[2][T], rj[2][T];   // [0]: drop rows, [1]: keep rows, of tile rows ti and tj
+  const int ti = blockIdx.x, tj = blockIdx.y, tid = threadIdx.x;
+  if (tj > ti) return;
+  const MapCutGroup G = g.cut.groups[0];
+  if (tid < 2 * T) {
+    int32_t b, k;
+    merge_rows(g, T * (tid < T ? ti : tj) + (tid & (T - 1)), b, k);
+    (tid < T ? ri : rj)[0][tid & (T - 1)] = b;
+    (tid < T ? ri : rj)[1][tid & (T - 1)] = k;
+  }
+  __syncthreads();
+  const int64_t ldc = g.N;
+  double t[T * T / kThreads];
+#pragma unroll
+  for (int x = 0; x < T * T / kThreads; ++x) t[x] = 0.0;
+#pragma unroll 1
+  for (int term = 0; term < 4; ++term) {   // (drop, drop) - (drop, keep) - (keep, drop) + (keep, keep)
+    const int32_t* ai = ri[term >> 1];
+    const int32_t* aj = rj[term & 1];
+    const double sgn = (term == 1 || term == 2) ? -1.0 : 1.0;
+    for (int e = tid; e < T * T; e += kThreads) {
+      const int r = e >> 6, c = e & 63;
+      P[r * LDM + c] = (ai[r] >= 0 && aj[c] >= 0) ? g.map_cov[(int64_t)ai[r] * ldc + aj[c]] : 0.0;    // C[row i_r][col j_c]
+      Qs[r * LDM + c] = (aj[r] >= 0 && ai[c] >= 0) ? g.map_cov[(int64_t)aj[r] * ldc + ai[c]] : 0.0;   // C[row j_r][col i_c]
+    }
+    __syncthreads();
+#pragma unroll
+    for (int x = 0; x < T * T / kThreads; ++x) {
+      const int e = tid + kThreads * x, r = e >> 6, c = e & 63;
+      t[x] += sgn * (0.5 * (P[r * LDM + c] + Qs[c * LDM + r]));
+    }
+    __syncthreads();
+  }
+  const int od = g.od;
+#pragma unroll
+  for (int x = 0; x < T * T / kThreads; ++x) {
+    const int e = tid + kThreads * x, r = e >> 6, c = e & 63, gi = T * ti + r, gj = T * tj + c;
+    const bool in = gi < G.N && gj < G.N;
+    double v = t[x];
+    if (in && g.noise != nullptr && gi / od == gj / od) {
+      const double* R = g.noise + (int64_t)(gi / od) * od * od;
+      v += 0.5 * (R[(gi % od) * od + gj % od] + R[(gj % od) * od + gi % od]);
+    }
+    P[r * LDM + c] = in ? v : (gi == gj ? 1.0 : 0.0);
+  }
+  __syncthreads();
+  double* tile = tile_ptr(g.cut.A, G.nt, ti, tj);
+  double* Cs = g.cut.Csym;
+  for (int e = tid; e < T * T; e += kThreads) {
+    const int r = e >> 6, c = e & 63, gi = T * ti + r, gj = T * tj + c;
+    const double v = (ti == tj && c > r) ? P[c * LDM + r] : P[r * LDM + c];
+    tile[e] = v;
+    if (gi < G.N && gj < G.N) Cs[(int64_t)gi * G.ld + gj] = v;
+  }
+  if (ti != tj) {   // the upper triangle of Csym, written along its rows
+    for (int e = tid; e < T * T; e += kThreads) {
+      const int r = e >> 6, c = e & 63, gj = T * tj + r, gi = T * ti + c;
+      if (gi < G.N && gj < G.N) Cs[(int64_t)gj * G.ld + gi] = P[c * LDM + r];
+    }
+  }
+  if (tj == 0 && tid < T && ri[0][tid] >= 0) g.cut.mean[T * ti + tid] = (g.map_mean[ri[0][tid]] - g.map_mean[ri[1][tid]]) - g.offset[T * ti + tid];
+}
+
+// (ti, tj): G_ij = Cs[kept rows of tile row i][drop columns of tile column j] - Cs[the same rows][keep columns], zero in the padding; rows in the new map's
+// order, so a dropped row is never formed
+__global__ void __launch_bounds__(kThreads) k_mm_gather(MapMergeDev g) {
+  __shared__ double P[T * LDM];
+  __shared__ double Qs[T * LDM];
+  __shared__ int32_t rows[T], cols[2][T];
+  const int ti = blockIdx.x, tj = blockIdx.y, tid = threadIdx.x;
+  if (tid < T) {
+    rows[tid] = merge_kept_row(g, T * ti + tid);
+    merge_rows(g, T * tj + tid, cols[0][tid], cols[1][tid]);
+  }
+  __syncthreads();
+  const int64_t ldc = g.N;
+  double t[T * T / kThreads];
+#pragma unroll
+  for (int x = 0; x < T * T / kThreads; ++x) t[x] = 0.0;
+#pragma unroll 1
+  for (int term = 0; term < 2; ++term) {
+    const int32_t* cc = cols[term];
+    const double sgn = term ? -1.0 : 1.0;
+    for (int e = tid; e < T * T; e += kThreads) {
+      const int a = e >> 6, b = e & 63;
+      P[a * LDM + b] = (rows[a] >= 0 && cc[b] >= 0) ? g.map_cov[(int64_t)rows[a] * ldc + cc[b]] : 0.0;    // C[kept row a][col b]
+      Qs[a * LDM + b] = (cc[a] >= 0 && rows[b] >= 0) ? g.map_cov[(int64_t)cc[a] * ldc + rows[b]] : 0.0;   // C[row of col a][kept col b]
+    }
+    __syncthreads();
+#pragma unroll
+    for (int x = 0; x < T * T / kThreads; ++x) {
+      const int e = tid + kThreads * x, r = e >> 6, c = e & 63;
+      t[x] += sgn * (0.5 * (P[r * LDM + c] + Qs[c * LDM + r]));
+    }
+    __syncthreads();
+  }
+  double* gt = tile_ptr(g.G, g.nQ, ti, tj);
+#pragma unroll
+  for (int x = 0; x < T * T / kThreads; ++x) gt[tid + kThreads * x] = t[x];
+}
+
+// The hot launch.  (ti, tj <= ti): C'_ij = Cs[kept_i, kept_j] - sum_k Y_ik Y_jk^T, k ascending; the old map's two blocks are read through the kept rows, each
+// along its rows; written along the rows of both triangles, a diagonal tile from its lower triangle -- k_mu_cov with Z = Y and a row table.
+__global__ void __launch_bounds__(kThreads) k_mm_cov(MapMergeDev g) {
+  __shared__ double A[T * LDM];
+  __shared__ double B[T * LDM];
+  __shared__ int32_t rows_i[T], rows_j[T];
+  const int ti = blockIdx.x, tj = blockIdx.y, tid = threadIdx.x;
+  if (tj > ti) return;
+  if (tid < 2 * T) (tid < T ? rows_i : rows_j)[tid & (T - 1)] = merge_kept_row(g, T * (tid < T ? ti : tj) + (tid & (T - 1)));
+  f64x4 acc[4] = {};
+  for (int k = 0; k < g.nQ; ++k) {
+    __syncthreads();
+    if (ti != tj) stage_tiles(A, tile_ptr(g.Y, g.nQ, ti, k), B, tile_ptr(g.Y, g.nQ, tj, k));
+    else stage_tile(A, tile_ptr(g.Y, g.nQ, ti, k));
+    __syncthreads();
+    tile_abt_mfma(A, ti != tj ? B : A, acc);
+  }
+  __syncthreads();
+  const int NK = g.NK;
+  const int64_t ldc = g.N, ldo = NK;
+  for (int e = tid; e < T * T; e += kThreads) {   // the old map's two blocks, each along its rows
+    const int a = e >> 6, b = e & 63;
+    A[a * LDM + b] = (rows_i[a] >= 0 && rows_j[b] >= 0) ? g.map_cov[(int64_t)rows_i[a] * ldc + rows_j[b]] : 0.0;
+    B[a * LDM + b] = (rows_j[a] >= 0 && rows_i[b] >= 0) ? g.map_cov[(int64_t)rows_j[a] * ldc + rows_i[b]] : 0.0;
+  }
+  __syncthreads();
+  const int lane = tid & 63, wv = tid >> 6;
+  double v[4][4];
+#pragma unroll
+  for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = 16 * rt + (lane >> 4) + 4 * r, col = 16 * wv + (lane & 15);
+      v[rt][r] = 0.5 * (A[row * LDM + col] + B[col * LDM + row]) - acc[rt][r];
+    }
+  __syncthreads();
+#pragma unroll
+  for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) A[(16 * rt + (lane >> 4) + 4 * r) * LDM + 16 * wv + (lane & 15)] = v[rt][r];
+  __syncthreads();
+  bool bad = false;
+  for (int e = tid; e < T * T; e += kThreads) {
+    const int r = e >> 6, c = e & 63;
+    const int gi = T * ti + r, gj = T * tj + c;
+    if (gi < NK && gj < NK) {
+      const double x = (ti == tj && c > r) ? A[c * LDM + r] : A[r * LDM + c];
+      g.out_cov[(int64_t)gi * ldo + gj] = x;
+      bad = bad || !isfinite(x);
+    }
+    const int hj = T * tj + r, hi = T * ti + c;
+    if (ti != tj && hi < NK && hj < NK) g.out_cov[(int64_t)hj * ldo + hi] = A[c * LDM + r];
+  }
+  if (bad) g.status[MS_NONFINITE] = 1.0;
+}
+
+// v = W (H mu - d): workgroup b its 64 rows, four threads per row, the dot product split by column mod 4 (k_mu_v's sum)
+__global__ void __launch_bounds__(kThreads) k_mm_v(MapMergeDev g) {
+  const int row = T * blockIdx.x + (threadIdx.x >> 2), part = threadIdx.x & 3;
+  double s = 0.0;
+  if (row < g.Q) for (int c = part; c <= row; c += 4) s += g.cut.W[(int64_t)row * g.Q + c] * g.cut.mean[c];
+  s += __shfl_xor(s, 1, 64);
+  s += __shfl_xor(s, 2, 64);
+  if (part == 0) g.v[row] = s;
+}
+// mu'[kept] = mu[kept] - Y v: workgroup b its 64 rows of the new map
+__global__ void __launch_bounds__(kThreads) k_mm_mean(MapMergeDev g) {
+  const int r = threadIdx.x >> 2, part = threadIdx.x & 3, row = T * blockIdx.x + r;
+  double s = 0.0;
+  for (int k = 0; k < g.nQ; ++k) {
+    const double* y = tile_ptr(g.Y, g.nQ, blockIdx.x, k) + r * T;
+    for (int c = part; c < T; c += 4) s += y[c] * g.v[T * k + c];
+  }
+  s += __shfl_xor(s, 1, 64);
+  s += __shfl_xor(s, 2, 64);
+  if (part == 0 && row < g.NK) {
+    const double x = g.map_mean[merge_kept_row(g, row)] - s;
+    g.out_mean[row] = x;
+    if (!isfinite(x)) g.status[MS_NONFINITE] = 1.0;
+  }
+}
+
 }  // namespace
 
 void launch_map_update(hipStream_t s, const MapUpdateDev& u) {
@@ -664,6 +864,12 @@ void launch_map_factor(hipStream_t s, const MapCutDev& m, int nt_max, const doub
   if (m.n <= 0) return;
   const unsigned gz = (unsigned)std::min<int64_t>(m.n, 65535);
   hipLaunchKernelGGL(k_map_gather, dim3(nt_max, nt_max, gz), dim3(kThreads), 0, s, m, map_mean, map_cov, ldc);
+  launch_map_factorize(s, m, nt_max);
+}
+
+void launch_map_factorize(hipStream_t s, const MapCutDev& m, int nt_max) {
+  if (m.n <= 0) return;
+  const unsigned gz = (unsigned)std::min<int64_t>(m.n, 65535);
   for (int k = 0; k < nt_max; ++k) {
     hipLaunchKernelGGL(k_map_potrf, dim3(gz), dim3(kThreads), 0, s, m, k);
     if (k + 1 == nt_max) break;
@@ -680,6 +886,21 @@ void launch_map_condition_estimate(hipStream_t s, const MapCutDev& m, int nt_max
   const int nb = (std::min(nt_max * T, kMapGroupMaxRows) + kPowRows - 1) / kPowRows;
   for (int step = 0; step < kMapPowerSteps; ++step) hipLaunchKernelGGL(k_map_power, dim3(nb, gz, 2), dim3(kThreads), 0, s, m, x0, step);
   hipLaunchKernelGGL(k_map_power_finish, dim3((unsigned)((m.n + 63) / 64)), dim3(64), 0, s, m);
+}
+
+void launch_map_merge(hipStream_t s, const MapMergeDev& g, const double* x0) {
+  const int nQ = g.nQ, nK = g.nK;
+  hipLaunchKernelGGL(k_mm_innovation, dim3(nQ, nQ), dim3(kThreads), 0, s, g);
+  launch_map_factorize(s, g.cut, nQ);
+  launch_map_condition_estimate(s, g.cut, nQ, x0);
+  MapUpdateDev u{};   // k_mu_operands' first plane reads nA, Wt and Wn alone
+  u.nA = nQ; u.Wt = g.cut.Wt; u.Wn = g.Wn;
+  hipLaunchKernelGGL(k_mu_operands, dim3(nQ, nQ, 1), dim3(kThreads), 0, s, u);                                   // Wn = W as tiles
+  hipLaunchKernelGGL(k_mm_gather, dim3(nK, nQ), dim3(kThreads), 0, s, g);
+  hipLaunchKernelGGL(k_mu_gemm, dim3(nK, nQ), dim3(kThreads), 0, s, MuGemm{g.G, g.Wn, g.Y, nQ, nQ, 1, 0});       // Y = G W^T
+  hipLaunchKernelGGL(k_mm_cov, dim3(nK, nK), dim3(kThreads), 0, s, g);
+  hipLaunchKernelGGL(k_mm_v, dim3(nQ), dim3(kThreads), 0, s, g);
+  hipLaunchKernelGGL(k_mm_mean, dim3(nK), dim3(kThreads), 0, s, g);
 }
 
 }  // namespace obvi

@@ -1,0 +1,70 @@
+// map_merge.cpp -- include/obvi_map_merge.h: duplicate objects of a device-resident map fused into one (map_kernels.hip).  The host checks every index and
+// every pair, sets up a one-group cut of the constraint rows (map_window.h: the set-up map_update.cpp and map_extend.cpp use; the cut's object list is the drop
+// list), launches into a freshly allocated, smaller map, reads the cut's status record back and hands the new map out only when nothing was refused.
+#include "map_window.h"
+#include "../../include/obvi_map_merge.h"
+
+extern "C" {
+
+int obvi_map_merge(obvi_ba_handle* h, const obvi_map* map, int64_t q, const uint32_t* drop_idx, const uint32_t* keep_idx, const double* offset, const double* noise,
+                   uint32_t* new_index, obvi_map** out) {
+  if (out) *out = nullptr;
+  if (!h || !map || !out || q < 1 || !drop_idx || !keep_idx) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "map_merge: bad arguments");
+  const int od = h->od;
+  if (q > OBVI_MAP_GROUP_MAX_ROWS / od) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "map_merge: pairs of more than OBVI_MAP_GROUP_MAX_ROWS rows");
+  // device, block size, the range of the drop list and an object dropped twice: the checks of every window
+  { const int rc = check_window(h, map, q, drop_idx, q * od, "map_merge"); if (rc != OBVI_OK) return rc; }
+  const int64_t n = map->n;
+  for (int64_t r = 0; r < q; ++r) if ((int64_t)keep_idx[r] >= n) return fail(h, OBVI_ERR_OUT_OF_RANGE, "map_merge: map index out of range");
+  std::vector<uint8_t> dropped((size_t)n, 0);
+  for (int64_t r = 0; r < q; ++r) dropped[drop_idx[r]] = 1;
+  for (int64_t r = 0; r < q; ++r) {
+    if (keep_idx[r] == drop_idx[r]) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "map_merge: an object merged into itself");
+    if (dropped[keep_idx[r]]) return fail(h, OBVI_ERR_INVALID_ARGUMENT, "map_merge: an object that is dropped in one pair and kept in another (resolve chains to one survivor per group)");
+  }
+  const int64_t Q = q * od, nn = (int64_t)od * od;
+  if (offset) for (int64_t i = 0; i < Q; ++i) if (!std::isfinite(offset[i])) return fail(h, OBVI_ERR_NUMERICAL, "map_merge: an offset that is not finite");
+  if (noise) for (int64_t i = 0; i < q * nn; ++i) if (!std::isfinite(noise[i])) return fail(h, OBVI_ERR_NUMERICAL, "map_merge: a noise entry that is not finite");
+  OBVI_API_BEGIN
+  OBVI_HIP(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  // the new map's objects, and where every old one went; all host tables are alive until the wait
+  std::vector<uint32_t> kept, where((size_t)n);
+  kept.reserve((size_t)(n - q));
+  for (int64_t o = 0; o < n; ++o) if (!dropped[o]) { where[o] = (uint32_t)kept.size(); kept.push_back((uint32_t)o); }
+  for (int64_t r = 0; r < q; ++r) where[drop_idx[r]] = where[keep_idx[r]];
+  std::vector<double> in((size_t)(Q + (noise ? q * nn : 0)), 0.0);
+  if (offset) std::copy(offset, offset + Q, in.begin());
+  if (noise) std::copy(noise, noise + q * nn, in.begin() + Q);
+  const int64_t N = n * od, NK = (n - q) * od, nQ = map_group_slabs(Q), nK = map_group_slabs(NK), tile = (int64_t)kTile * kTile;
+  const MapCutDev m = window_cut(h, q, drop_idx);
+  h->d_mm_keep.upload(keep_idx, (size_t)q, s); h->d_mm_kept.upload(kept, s); h->d_mm_in.upload(in, s);
+  h->d_mm_tiles.resize((size_t)((nQ * nQ + 2 * nK * nQ) * tile + kTile * nQ));
+  // the new map
+  std::unique_ptr<obvi_map, MapDeleter> fresh(new obvi_map());
+  fresh->device = map->device; fresh->od = od; fresh->n = n - q;
+  OBVI_HIP(hipMalloc(reinterpret_cast<void**>(&fresh->d_mean), sizeof(double) * NK));
+  OBVI_HIP(hipMalloc(reinterpret_cast<void**>(&fresh->d_cov), sizeof(double) * NK * NK));
+  OBVI_HIP(hipMalloc(reinterpret_cast<void**>(&fresh->d_x0), sizeof(double) * kMapGroupMaxRows));
+  OBVI_HIP(hipMemcpyAsync(fresh->d_x0, map->d_x0, sizeof(double) * kMapGroupMaxRows, hipMemcpyDeviceToDevice, s));
+  MapMergeDev g{};
+  g.od = od; g.N = (int32_t)N; g.Q = (int32_t)Q; g.NK = (int32_t)NK; g.nQ = (int32_t)nQ; g.nK = (int32_t)nK;
+  g.cut = m; g.keep = h->d_mm_keep.get(); g.kept = h->d_mm_kept.get();
+  g.offset = h->d_mm_in.get(); g.noise = noise ? h->d_mm_in.get() + Q : nullptr;
+  g.map_mean = map->d_mean; g.map_cov = map->d_cov;
+  g.Wn = h->d_mm_tiles.get(); g.G = g.Wn + nQ * nQ * tile; g.Y = g.G + nK * nQ * tile; g.v = g.Y + nK * nQ * tile;
+  g.out_mean = fresh->d_mean; g.out_cov = fresh->d_cov; g.status = m.status;
+  launch_map_merge(s, g, map->d_x0);
+  OBVI_HIP(hipGetLastError());
+  double st[kMapStatusDoubles];
+  h->d_mc_status.download(st, (size_t)kMapStatusDoubles, s);
+  sync(h);   // the call's one wait: either map may go away from here on, and any stream may read the new one
+  if (!window_cut_spd(st)) return fail(h, OBVI_ERR_NUMERICAL, "map_merge: the covariance of the pairs' differences is not SPD, or numerically singular (a pair that is already merged?)");
+  if (st[MS_NONFINITE] != 0.0) return fail(h, OBVI_ERR_NUMERICAL, "map_merge: a non-finite entry in the new map");
+  if (new_index) std::copy(where.begin(), where.end(), new_index);
+  *out = fresh.release();
+  return OBVI_OK;
+  OBVI_API_END(h)
+}
+
+}  // extern "C"

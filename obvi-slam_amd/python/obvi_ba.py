@@ -235,6 +235,26 @@ class Map:
         """A first Map, born from the current estimates and joint covariance of `ba`'s objects obj_idx."""
         return cls._unborn(ba).extend_on(ba, [], [], obj_idx)
 
+    # ---- a map that shrinks (include/obvi_map_merge.h) ----
+    def merge(self, ba, drop_idx, keep_idx, offset=None, noise=None):
+        """(Map, new_index [n]): a new Map of n - q objects in which each object drop_idx[r] is fused into keep_idx[r], x_drop - x_keep = offset[r] ([q][od];
+        None: zeros) up to the covariance noise[r] ([q][od][od]; None: exactly); new_index[o] is the new number of old object o."""
+        drop, keep = np.ascontiguousarray(drop_idx, dtype=np.uint32).ravel(), np.ascontiguousarray(keep_idx, dtype=np.uint32).ravel()
+        if len(drop) != len(keep):
+            raise ObviError("map_merge: drop_idx and keep_idx differ in length")
+        try:
+            f = getattr(self._lib, self._pre + "map_merge")
+        except AttributeError:
+            raise ObviError("%smap_merge: this library cannot merge objects of a map (include/obvi_map_merge.h is served by libobvi_ba.so only)" % self._pre)
+        f.restype = C.c_int
+        d = None if offset is None else _f64(offset, (len(drop), self.od))
+        r = None if noise is None else _f64(noise, (len(drop), self.od, self.od))
+        where = np.zeros(self.n_objects, np.uint32)
+        new = C.c_void_p()
+        rc = f(ba._h, self._m, C.c_int64(len(drop)), _ptr(drop, C.c_uint32), _ptr(keep, C.c_uint32), _ptr(d, C.c_double), _ptr(r, C.c_double),
+               _ptr(where, C.c_uint32), C.byref(new))
+        return self._conditioned(ba, rc, new, "map_merge"), where
+
     def close(self):
         if self._m:
             f = getattr(self._lib, self._pre + "map_destroy")

@@ -10,7 +10,9 @@ the map lacks, against the round trip that grows the map without them: obvi_map_
 --shared K: K concurrent sessions of 500 frames / 50 000 features over 50 shared objects behind one group: ms per joint LM step without and
 with the whole-map group prior on member 0, and the wall time of the collective obvi_map_condition_on_handle (every member folds all 50 objects back) against
 the same call on ONE handle that holds the joint problem.
-usage (GPU box, repo root): python scripts/map_bench.py [--update | --extend | --shared K]"""
+--merge: a map that shrinks -- obvi_map_merge of 1, 10 and 30 pairs of the 200-object map (noise on every pair), wait included, against the
+round trip that merges without it: obvi_map_get, the same formula in numpy, obvi_map_create.
+usage (GPU box, repo root): python scripts/map_bench.py [--update | --extend | --merge | --shared K]"""
 import os
 import sys
 import time
@@ -205,6 +207,63 @@ def extend():
     mp.close()
 
 
+def numpy_merge(mean, cov, drop, keep, offset, noise):
+    """The formulas of include/obvi_map_merge.h on the host."""
+    n, q = len(mean), len(drop)
+    Cs = 0.5 * (cov + cov.T)
+    rows = lambda o: np.concatenate([np.arange(OD * x, OD * x + OD) for x in o])   # noqa: E731
+    rb, rk = rows(drop), rows(keep)
+    G = Cs[:, rb] - Cs[:, rk]                                                       # Cs H^T
+    Tm = G[rb] - G[rk]
+    for r in range(q):
+        Tm[OD * r:OD * r + OD, OD * r:OD * r + OD] += 0.5 * (noise[r] + noise[r].T)
+    resid = mean.ravel()[rb] - mean.ravel()[rk] - offset.ravel()
+    K = np.linalg.solve(0.5 * (Tm + Tm.T), G.T).T
+    kept = rows(np.setdiff1d(np.arange(n), drop))
+    mu = (mean.ravel() - K @ resid)[kept]
+    Cn = (Cs - K @ G.T)[np.ix_(kept, kept)]
+    return mu.reshape(-1, OD), 0.5 * (Cn + Cn.T)
+
+
+def merge():
+    """duplicate objects of the map merged.  The device entry against the round trip a session needs without it."""
+    rng = np.random.default_rng(1)
+    mean, cov = rng.normal(size=(N_MAP, OD)), spd(rng, N_MAP * OD)
+    mp = obvi_ba.Map.create(mean, cov, object_block_size=OD)
+    ba = obvi_ba.BundleAdjuster(object_block_size=OD)
+    ba.set_cameras(synth.K_DEFAULT[None], synth.EXT_DEFAULT[None])
+    ba.set_poses(np.zeros((1, 6)), np.ones(1, np.uint8))
+    ba.set_points(np.zeros((0, 3)), np.zeros(0, np.uint8))
+    ba.set_objects(np.zeros((1, OD)), np.zeros(1, np.uint8))
+    for q in (1, 10, 30):
+        perm = rng.permutation(N_MAP)
+        drop, keep = perm[:q], perm[q:2 * q]
+        offset = 0.1 * rng.normal(size=(q, OD))
+        A = rng.normal(size=(q, OD, OD))
+        noise = 1e-3 * (A @ A.transpose(0, 2, 1) + OD * np.eye(OD))
+        last = {}
+
+        def round_trip():
+            old_mean, old_cov = mp.get()
+            mu, Cn = numpy_merge(old_mean, old_cov, drop, keep, offset, noise)
+            with obvi_ba.Map.create(mu, Cn, object_block_size=OD) as new:
+                last["host"] = (mu, Cn, new.n_objects)
+
+        def device():
+            new, _ = mp.merge(ba, drop, keep, offset, noise)
+            with new:
+                last["n"] = new.n_objects
+        base, b = timed(round_trip)
+        dev, d = timed(device)
+        new, _ = mp.merge(ba, drop, keep, offset, noise)
+        with new:
+            mu, Cn = new.get()
+        print("%3d pairs (%4d rows), %d -> %d map rows: round trip %s   obvi_map_merge %s  (x %.1f)   |C' - numpy's| / |C'| %.1e"
+              % (q, q * OD, N_MAP * OD, (N_MAP - q) * OD, base, dev, b / d, np.abs(Cn - last["host"][1]).max() / np.abs(Cn).max()))
+    ba.close()
+    mp.close()
+
+
 def shared(n_sessions):
     """the map entries on handles that exchange shared objects."""
     import dist_util
@@ -269,4 +328,4 @@ if __name__ == "__main__":
     if "--shared" in sys.argv[1:]:
         shared(int(sys.argv[sys.argv.index("--shared") + 1]))
         sys.exit(0)
-    extend() if "--extend" in sys.argv[1:] else update() if "--update" in sys.argv[1:] else main()
+    merge() if "--merge" in sys.argv[1:] else extend() if "--extend" in sys.argv[1:] else update() if "--update" in sys.argv[1:] else main()
