@@ -41,6 +41,7 @@ Knobs read_knobs() {
   set_i64("OBVI_SMALL_LANES_BELOW", k.small_lanes_below);
   set_flag("OBVI_SIDE_PACKED", k.side_packed);
   if (const char* v = std::getenv("OBVI_BACKSUB_LANES")) { const int n = std::atoi(v); if (n == 1 || n == 2 || n == 4 || n == 8 || n == 16 || n == 32) k.backsub_lanes = n; }
+  set_flag("OBVI_POINT_FLAT", k.point_flat);
   set_int("OBVI_DET_MIN_STRIDE", k.det_min_stride); k.det_min_stride = std::max(1, k.det_min_stride);
   set_flag("OBVI_POSE_LIN_REUSE", k.pose_lin_reuse);
   set_flag("OBVI_FUSED_POTRF", k.fused_potrf);

@@ -299,7 +299,7 @@ void launch_reproj_gather(hipStream_t s, int64_t n, const uint32_t* perm, const 
 void launch_pose_cache(hipStream_t s, int64_t P, const double* poses, PoseCache* out, int analytic /* obvi_ba_options.reprojection_variant == OBVI_REPROJECTION_ANALYTIC */);
 void launch_point_pass(hipStream_t s, const BlocksDev& b, const ReprojDev& rp, const DevCam* cams, const PoseCache* pc, const double* points,
                        const ReducedDev& rd, const PointDev& pt, double radius, int first_iter, double* scal, const uint32_t* wave_obs, int64_t n_waves,
-                       const uint32_t* long_points, int64_t n_long);
+                       const uint32_t* long_points, int64_t n_long, bool flat /* Knobs::point_flat: k_point_pass requests its loads in front of the `live` branch and of the scan */);
 // lin: NULL, or (unsliced pose pass only) 27 doubles per pose that take the sums instead of Hdiag / g; launch_pose_lin_add adds such a set
 void launch_pose_pass(hipStream_t s, const BlocksDev& b, const ReprojPoseDev& rq, const DevCam* cams, const PoseCache* pc,
                       const double* points, const ReducedDev& rd, double* lin = nullptr);

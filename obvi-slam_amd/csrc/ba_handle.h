@@ -71,6 +71,7 @@ struct Knobs {
   int64_t small_lanes_below = 4096;     // OBVI_SMALL_LANES_BELOW: bounding-box factors below which the small factors take 16 lanes each
   bool side_packed = true;              // OBVI_SIDE_PACKED: big problems and deterministic handles, the bounding boxes in 256-thread workgroups of their own (0: in the other small factors' 64-thread launch)
   int backsub_lanes = 0;                // OBVI_BACKSUB_LANES: lanes per feature of the back-substitution, 1, 2, 4, 8, 16 or 32 (0: by sightings per feature)
+  bool point_flat = true;               // OBVI_POINT_FLAT: k_point_pass requests an observation's fields, the pose cache and the point's scale as early as their addresses are known (0: inside the `live` branch and behind the scan)
   int det_min_stride = 4096;            // OBVI_DET_MIN_STRIDE: deterministic mode, first size of the partial-sum slots (at least 1)
   bool pose_lin_reuse = true;           // OBVI_POSE_LIN_REUSE: the trial cost stages the pose side of the next linearisation (0: a pose pass in every step)
   // obvi_ba_create

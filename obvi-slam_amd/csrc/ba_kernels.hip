@@ -274,7 +274,17 @@ __global__ void __launch_bounds__(kBlock) k_point_pass_long(BlocksDev b, ReprojD
 // (the one-thread-per-point form evaluated them twice).  Per point: H_ll = sum rho' Jl^T Jl, g_l = sum rho' Jl^T r
 // by a segmented scan over the run's lanes (shuffles); every lane forms the
 // 3x3 Cholesky of H_ll + lambda and its own Z = rho' Jp^T Jl C^-T.
+// FLAT (Knobs::point_flat): what a lane reads is requested as early as its address is known -- with the piece: the observation's own
+// fields (point, pose, pixel, camera index, sigma, flag); with what those index (the point's flags, track and position, the pose's id):
+// the 21 pose-cache gathers; in front of the segmented scan: the point's Jacobi scale.  Before, pixel / camera index / sigma / pose cache
+// were requested inside `if (live)`, behind the loads that `live` itself waits for, and the scale behind the scan: two more dependent
+// round trips per wavefront and a third at the end.  The camera stays in the branch (hoisted as well, the kernel needs more than its 128
+// registers); its index is known by then and the few cameras are cache-resident.  A lane without an observation reads the piece's first
+// one; `live` only decides whether the values are evaluated.  Same arithmetic, same order, same results bit for bit.
 // ---------------------------------------------------------------------------------------
+// a value that must be in its register here: keeps a load that only the `live` branch uses from being moved back behind the branch
+__device__ __forceinline__ void held(double v) { asm volatile("" :: "v"(v)); }
+template <bool FLAT>
 __global__ void __launch_bounds__(kBlock, kPointImageDoubles <= 1264 ? 4 : 3) k_point_pass(BlocksDev b, ReprojDev rp, const DevCam* __restrict__ cams,
                                                       const PoseCache* __restrict__ pc, const double* __restrict__ points,
                                                       ReducedDev rd, PointDev pt, double radius, int first_iter, double* scal,
@@ -291,29 +301,55 @@ __global__ void __launch_bounds__(kBlock, kPointImageDoubles <= 1264 ? 4 : 3) k_
     const bool have = (uint32_t)lane < n;
     const uint32_t a = a0 + (have ? (uint32_t)lane : 0u);
     const uint32_t l = rp.point[a], p = rp.pose[a];
+    // FLAT: the observation's own fields go out with its two indices ...
+    double2 px_f = {0.0, 0.0};
+    double sigma_f = 0.0;
+    uint32_t cam_f = 0;
+    uint8_t act_f = 0;
+    if (FLAT) { px_f = rp.pixel[a]; cam_f = rp.cam[a]; sigma_f = rp.sigma[a]; act_f = rp.active[a]; }
     const uint32_t beg = rp.point_ptr[l], end = rp.point_ptr[l + 1];
     const bool lvar = b.point_var[l] != 0;
     const int32_t vid = b.pose_vid[p];
-    const bool live = have && rp.active[a] && (vid >= 0 || lvar);   // else: inactive, or an all-constant residual block (fixed cost)
     const double X[3] = {points[3 * (int64_t)l], points[3 * (int64_t)l + 1], points[3 * (int64_t)l + 2]};
+    // ... and the pose cache beside the loads that `live` waits for
+    PoseCache cache_f;
+    if (FLAT) {
+      const double* soa = reinterpret_cast<const double*>(pc + b.P + 1) + p;
+      double* f = reinterpret_cast<double*>(&cache_f);
+#pragma unroll
+      for (int k = 0; k < 21; ++k) f[k] = soa[k * b.P];
+#pragma unroll
+      for (int k = 0; k < 21; ++k) held(f[k]);
+      held(px_f.x); held(px_f.y); held(sigma_f);
+    }
+    const bool live = have && (FLAT ? act_f : rp.active[a]) && (vid >= 0 || lvar);   // else: inactive, or an all-constant residual block (fixed cost)
     double r[2] = {0.0, 0.0}, Jp[12], Jl[6], w = 0.0;
 #pragma unroll
     for (int i = 0; i < 12; ++i) Jp[i] = 0.0;
 #pragma unroll
     for (int i = 0; i < 6; ++i) Jl[i] = 0.0;
     if (live) {
-      const double2 px = rp.pixel[a];
-      PoseCache cache;   // from the field-major copy (k_pose_cache)
-      {
-        const double* soa = reinterpret_cast<const double*>(pc + b.P + 1) + p;
-        double* f = reinterpret_cast<double*>(&cache);
+      if (FLAT) {
+        reproj_eval<true>(cache_f, cams[cam_f], X, px_f.x, px_f.y, sigma_f, r, Jp, Jl);
+      } else {
+        const double2 px = rp.pixel[a];
+        PoseCache cache;   // from the field-major copy (k_pose_cache)
+        {
+          const double* soa = reinterpret_cast<const double*>(pc + b.P + 1) + p;
+          double* f = reinterpret_cast<double*>(&cache);
 #pragma unroll
-        for (int k = 0; k < 21; ++k) f[k] = soa[k * b.P];
+          for (int k = 0; k < 21; ++k) f[k] = soa[k * b.P];
+        }
+        reproj_eval<true>(cache, cams[rp.cam[a]], X, px.x, px.y, rp.sigma[a], r, Jp, Jl);
       }
-      reproj_eval<true>(cache, cams[rp.cam[a]], X, px.x, px.y, rp.sigma[a], r, Jp, Jl);
       double rho0;
       huber_eval(r[0] * r[0] + r[1] * r[1], rp.huber, &rho0, &w);
       cost = 0.5 * rho0;
+    }
+    double sc_f[3] = {0.0, 0.0, 0.0};   // FLAT: the Jacobi scale of the point, requested in front of the scan that it is used behind
+    if (FLAT && !first_iter) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) sc_f[k] = pt.scale[3 * (int64_t)l + k];
     }
     const bool sum = live && lvar;
     // per point: sums over its run of lanes (segmented inclusive scan, then everybody reads the run's last lane)
@@ -336,6 +372,7 @@ __global__ void __launch_bounds__(kBlock, kPointImageDoubles <= 1264 ? 4 : 3) k_
 #pragma unroll
       for (int q = 0; q < 9; ++q) { const double up = __shfl_up(t[q], d, 64); t[q] += take ? up : 0.0; }
     }
+    if (FLAT) { held(sc_f[0]); held(sc_f[1]); held(sc_f[2]); }
     const int last = have ? min(first + len - 1, 63) : lane;
 #pragma unroll
     for (int q = 0; q < 9; ++q) t[q] = __shfl(t[q], last, 64);
@@ -344,6 +381,7 @@ __global__ void __launch_bounds__(kBlock, kPointImageDoubles <= 1264 ? 4 : 3) k_
       const double h00 = t[0], h10 = t[1], h11 = t[2], h20 = t[3], h21 = t[4], h22 = t[5], g0 = t[6], g1 = t[7], g2 = t[8];
       double s0, s1, s2;
       if (first_iter) { s0 = 1.0 / (1.0 + sqrt(h00)); s1 = 1.0 / (1.0 + sqrt(h11)); s2 = 1.0 / (1.0 + sqrt(h22)); }
+      else if (FLAT) { s0 = sc_f[0]; s1 = sc_f[1]; s2 = sc_f[2]; }
       else { s0 = pt.scale[3 * (int64_t)l]; s1 = pt.scale[3 * (int64_t)l + 1]; s2 = pt.scale[3 * (int64_t)l + 2]; }
       double lam0 = lm_lambda(h00, s0, radius), lam1 = lm_lambda(h11, s1, radius), lam2 = lm_lambda(h22, s2, radius);
       if (pt.extra) { lam0 += pt.extra[3 * (int64_t)l]; lam1 += pt.extra[3 * (int64_t)l + 1]; lam2 += pt.extra[3 * (int64_t)l + 2]; }
@@ -2102,10 +2140,11 @@ void launch_pose_cache(hipStream_t s, int64_t P, const double* poses, PoseCache*
 }
 void launch_point_pass(hipStream_t s, const BlocksDev& b, const ReprojDev& rp, const DevCam* cams, const PoseCache* pc, const double* points,
                        const ReducedDev& rd, const PointDev& pt, double radius, int first_iter, double* scal, const uint32_t* wave_obs, int64_t n_waves,
-                       const uint32_t* long_points, int64_t n_long) {
+                       const uint32_t* long_points, int64_t n_long, bool flat) {
   const uint32_t sums = OBVI_SC(SC_COST) | OBVI_SC(SC_GSQ) | OBVI_SC(SC_XSQ);
   launch_reducing(s, b, scal, point_pass_grid(n_waves), sums, [&](dim3 g) {
-    hipLaunchKernelGGL(k_point_pass, g, dim3(kBlock), 0, s, b, rp, cams, pc, points, rd, pt, radius, first_iter, scal, wave_obs, n_waves); });
+    if (flat) hipLaunchKernelGGL(k_point_pass<true>, g, dim3(kBlock), 0, s, b, rp, cams, pc, points, rd, pt, radius, first_iter, scal, wave_obs, n_waves);
+    else hipLaunchKernelGGL(k_point_pass<false>, g, dim3(kBlock), 0, s, b, rp, cams, pc, points, rd, pt, radius, first_iter, scal, wave_obs, n_waves); });
   launch_reducing(s, b, scal, point_pass_long_grid(n_long), sums, [&](dim3 g) {
     hipLaunchKernelGGL(k_point_pass_long, g, dim3(kBlock), 0, s, b, rp, cams, pc, points, rd, pt, radius, first_iter, scal, long_points, n_long); });
 }
