@@ -265,6 +265,23 @@ struct MapMergeDev {
 // T and H mu - d into the cut, its factor and condition estimate (x0: the map's start vector), G, Wn, Y, the hot launch C', v, mu'.  The cut's W and the padding
 // of its Lambda, and status, must have been zeroed on the stream.
 void launch_map_merge(hipStream_t s, const MapMergeDev& g, const double* x0);
+// Duplicate objects of a map proposed (include/obvi_map_match.h; map_kernels.hip): every pair a < b of the n objects that passes the label and centre-distance
+// tests gets s = d^T T^-1 d on the rows of `mask`, d = mu_b - mu_a (row 3 wrapped by `period`), T = Cs_bb - Cs_ba - Cs_ab + Cs_aa.  stat [n][n], upper
+// triangle: s, or kMatchNotTested / kMatchSingular.  The pairs with s <= gate leave in (a, b) order, cut at `capacity`.
+constexpr double kMatchNotTested = -1.0, kMatchSingular = -2.0;
+struct MapMatchDev {
+  int32_t od, n; uint32_t mask; int32_t use_dist;            // mask: never 0 (all rows: every bit below od); use_dist 0: no centre test
+  double gate, dist2, period;                                // dist2 = D D; period 0: no wrap
+  int64_t capacity;
+  const double* map_mean; const double* map_cov;             // the map: [n od], [n od][n od]
+  const int32_t* label;                                      // [n] or NULL
+  double* diag; double* mean;                                // [n][od][od] the symmetrised diagonal blocks, [n][od] the means beside them
+  double* stat;                                              // [n][n]
+  int64_t* row_cnt; int64_t* row_off; int64_t* totals;       // [n][3] found, tested, singular of row a; [n] found in the rows before a; [3] the sums
+  uint32_t* out_a; uint32_t* out_b; double* out_stat; double* out_yaw;   // [min(capacity, n (n - 1) / 2)] each (never read when capacity is 0)
+};
+// five launches: diagonal blocks, pairs, row counts, the scan of the rows (one workgroup), the scatter.  n >= 1.
+void launch_map_match(hipStream_t s, const MapMatchDev& m);
 // the posterior of the handle form: the k x k blocks of launch_cov_pairs (pair a k + b: objects a, b) -> dense P, and the objects' current values -> pm
 void launch_map_posterior_layout(hipStream_t s, const double* blocks, const double* objects, const uint32_t* obj_idx, int32_t k, int32_t od, double* P, double* pm);
 

@@ -10,7 +10,9 @@
 // one-group cut, under the same rules.  Third part: the map grown by the window's new objects, born from a posterior, or gathered down to some of its objects
 // (include/obvi_map_extend.h): the same launches into a larger map, the cross block, and the scatter of the window's whole block.  Fourth part: duplicate
 // objects of the map merged (include/obvi_map_merge.h): the innovation covariance of the pairs built in a one-group cut and factored as any cut, the gain tiles
-// of the surviving rows alone, and the downdate written straight into the smaller map.
+// of the surviving rows alone, and the downdate written straight into the smaller map.  Fifth part: duplicate objects of the map proposed
+// (include/obvi_map_match.h): every pair's difference in units of its own covariance, one lane per pair, and the pairs within the gate compacted in (a, b) order
+// by counts and a scan.
 #include "chol_tile.h"
 
 namespace obvi {
@@ -811,7 +813,182 @@ __global__ void __launch_bounds__(kThreads) k_mm_mean(MapMergeDev g) {
   }
 }
 
+// ==== duplicate objects of the map proposed (include/obvi_map_match.h; MapMatchDev, ba_device.h) ==========================================================
+// Under the rules above.  Every count is a sum of integers and every output position comes from the scan of the rows' counts: nothing depends on the order in
+// which workgroups run.
+
+// object o: its diagonal block, symmetrised as k_map_gather forms every entry, compacted to [o][od][od]
+__global__ void __launch_bounds__(64) k_mt_diag(MapMatchDev m) {
+  const int o = blockIdx.x, od = m.od, tid = threadIdx.x;
+  const int64_t ldc = (int64_t)m.n * od;
+  const double* C = m.map_cov + ((int64_t)o * od) * ldc + (int64_t)o * od;
+  for (int e = tid; e < od * od; e += 64) {
+    const int r = e / od, c = e % od;
+    m.diag[(int64_t)o * od * od + e] = 0.5 * (C[r * ldc + c] + C[c * ldc + r]);
+  }
+}
+
+// the wrap of a yaw difference: period * rint(dy / period), each operation rounded on its own
+__device__ __forceinline__ double match_wrap(double dy, double period) { return period > 0.0 ? __dmul_rn(period, rint(dy / period)) : 0.0; }
+
+// Workgroup (bi, bj >= bi): the pairs (a, b), a < b, of B = 64 / OD objects a of block bi and B objects b of block bj; B OD = 63 rows for both block sizes, so
+// the two orientations of the cross block -- C[rows a][columns b] and C[rows b][columns a], both read along their rows -- are the two staged tiles of
+// k_map_gather.  One lane per pair: label and distance tests first, then T (lower triangle, in registers; rows outside the mask replaced by the identity),
+// its Cholesky with the pivot extremes of k_map_potrf over the rows of the mask, and s = |L^-1 d|^2 by forward substitution beside it.
+template <int OD>
+__global__ void __launch_bounds__(kThreads) k_mt_pairs(MapMatchDev m) {
+  constexpr int B = T / OD, R = B * OD;
+  __shared__ double P[T * LDM];   // C[rows of block bi][columns of block bj]
+  __shared__ double Q[T * LDM];   // C[rows of block bj][columns of block bi]
+  __shared__ double Da[B * OD * OD], Db[B * OD * OD], ma[R], mb[R];
+  const int bi = blockIdx.x, bj = blockIdx.y, tid = threadIdx.x;
+  if (bj < bi) return;
+  const int n = m.n;
+  const int na = min(B, n - bi * B), nb = min(B, n - bj * B), ra = na * OD, rb = nb * OD;
+  const int64_t ldc = (int64_t)n * OD, row_a = (int64_t)bi * R, row_b = (int64_t)bj * R;
+  for (int e = tid; e < T * T; e += kThreads) {
+    const int r = e >> 6, c = e & 63;
+    P[r * LDM + c] = (r < ra && c < rb) ? m.map_cov[(row_a + r) * ldc + row_b + c] : 0.0;
+    Q[r * LDM + c] = (r < rb && c < ra) ? m.map_cov[(row_b + r) * ldc + row_a + c] : 0.0;
+  }
+  for (int e = tid; e < B * OD * OD; e += kThreads) {
+    Da[e] = e < ra * OD ? m.diag[row_a * OD + e] : 0.0;
+    Db[e] = e < rb * OD ? m.diag[row_b * OD + e] : 0.0;
+  }
+  if (tid < R) {
+    ma[tid] = tid < ra ? m.map_mean[row_a + tid] : 0.0;
+    mb[tid] = tid < rb ? m.map_mean[row_b + tid] : 0.0;
+  }
+  __syncthreads();
+  const int al = tid / B, bl = tid % B, a = bi * B + al, b = bj * B + bl;
+  if (al >= na || bl >= nb || a >= b) return;
+  bool test = true;
+  if (m.label != nullptr) { const int32_t la = m.label[a], lb = m.label[b]; test = la >= 0 && la == lb; }
+  if (test && m.use_dist) {
+    const double dx = mb[bl * OD] - ma[al * OD], dy = mb[bl * OD + 1] - ma[al * OD + 1], dz = mb[bl * OD + 2] - ma[al * OD + 2];
+    test = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz)) <= m.dist2;
+  }
+  double code = kMatchNotTested;
+  if (test) {
+    double t[OD * (OD + 1) / 2], d[OD], y[OD];
+#pragma unroll
+    for (int r = 0; r < OD; ++r) d[r] = mb[bl * OD + r] - ma[al * OD + r];
+    if (OD == 7) d[3] = __dsub_rn(d[3], match_wrap(d[3], m.period));
+#pragma unroll
+    for (int r = 0; r < OD; ++r) {
+      const bool inr = (m.mask >> r) & 1u;
+      d[r] = inr ? d[r] : 0.0;
+#pragma unroll
+      for (int c = 0; c <= r; ++c) {
+        const bool in = inr && ((m.mask >> c) & 1u);
+        const double bb = Db[(bl * OD + r) * OD + c], aa = Da[(al * OD + r) * OD + c];
+        const double ba = 0.5 * (Q[(bl * OD + r) * LDM + al * OD + c] + P[(al * OD + c) * LDM + bl * OD + r]);
+        const double ab = 0.5 * (P[(al * OD + r) * LDM + bl * OD + c] + Q[(bl * OD + c) * LDM + al * OD + r]);
+        t[r * (r + 1) / 2 + c] = in ? ((bb - ba) - ab) + aa : (r == c ? 1.0 : 0.0);
+      }
+    }
+    double s = 0.0, pmin = INFINITY, pmax = 0.0;
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < OD; ++j) {   // left-looking: column j of L, then row j of the forward substitution
+#pragma unroll
+      for (int k = 0; k < j; ++k) {
+        const double ljk = t[j * (j + 1) / 2 + k];
+#pragma unroll
+        for (int i = j; i < OD; ++i) t[i * (i + 1) / 2 + j] -= t[i * (i + 1) / 2 + k] * ljk;
+      }
+      const double p = t[j * (j + 1) / 2 + j];
+      const bool ok = p > 0.0 && isfinite(p);
+      const double dj = sqrt(ok ? p : 1.0);
+      if ((m.mask >> j) & 1u) { bad = bad || !ok; pmin = fmin(pmin, dj); pmax = fmax(pmax, dj); }
+      double acc = d[j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) acc -= t[j * (j + 1) / 2 + k] * y[k];
+      y[j] = acc / dj;
+      s += y[j] * y[j];
+#pragma unroll
+      for (int i = j + 1; i < OD; ++i) t[i * (i + 1) / 2 + j] /= dj;
+    }
+    code = (bad || !(pmin * pmin > 1e-13 * pmax * pmax)) ? kMatchSingular : s;
+  }
+  m.stat[(int64_t)a * n + b] = code;
+}
+
+__device__ __forceinline__ bool match_found(double v, double gate) { return v >= 0.0 && v <= gate; }
+
+// row a: its found, tested and singular pairs
+__global__ void __launch_bounds__(kThreads) k_mt_count(MapMatchDev m) {
+  __shared__ int32_t part[3][kThreads / 64];
+  const int a = blockIdx.x, tid = threadIdx.x, n = m.n;
+  int32_t c[3] = {0, 0, 0};
+  for (int b = a + 1 + tid; b < n; b += kThreads) {
+    const double v = m.stat[(int64_t)a * n + b];
+    c[0] += match_found(v, m.gate) ? 1 : 0; c[1] += v != kMatchNotTested ? 1 : 0; c[2] += v == kMatchSingular ? 1 : 0;
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int x = 32; x >= 1; x >>= 1) c[i] += __shfl_xor(c[i], x, 64);
+    if ((tid & 63) == 0) part[i][tid >> 6] = c[i];
+  }
+  __syncthreads();
+  if (tid < 3) { int64_t sum = 0; for (int w = 0; w < kThreads / 64; ++w) sum += part[tid][w]; m.row_cnt[3 * (int64_t)a + tid] = sum; }
+}
+
+// one workgroup: row_off[a] = found pairs of the rows before a, and the three totals
+__global__ void __launch_bounds__(kThreads) k_mt_scan(MapMatchDev m) {
+  __shared__ int64_t part[3][kThreads];
+  const int tid = threadIdx.x, n = m.n, per = (n + kThreads - 1) / kThreads, lo = min(n, tid * per), hi = min(n, lo + per);
+  int64_t c[3] = {0, 0, 0};
+  for (int a = lo; a < hi; ++a) for (int i = 0; i < 3; ++i) c[i] += m.row_cnt[3 * (int64_t)a + i];
+  for (int i = 0; i < 3; ++i) part[i][tid] = c[i];
+  __syncthreads();
+  if (tid < 3) {
+    int64_t run = 0;
+    for (int x = 0; x < kThreads; ++x) { const int64_t v = part[tid][x]; part[tid][x] = run; run += v; }
+    m.totals[tid] = run;
+  }
+  __syncthreads();
+  int64_t off = part[0][tid];
+  for (int a = lo; a < hi; ++a) { m.row_off[a] = off; off += m.row_cnt[3 * (int64_t)a]; }
+}
+
+// row a: its found pairs to their places behind row_off[a], in the order of b, up to `capacity`
+__global__ void __launch_bounds__(kThreads) k_mt_scatter(MapMatchDev m) {
+  __shared__ int32_t wcnt[kThreads / 64];
+  const int a = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = m.n, od = m.od;
+  if (m.row_cnt[3 * (int64_t)a] == 0) return;
+  int64_t base = m.row_off[a];
+  for (int b0 = a + 1; b0 < n && base < m.capacity; b0 += kThreads) {
+    const int b = b0 + tid;
+    const double v = b < n ? m.stat[(int64_t)a * n + b] : kMatchNotTested;
+    const bool hit = match_found(v, m.gate);
+    const uint64_t votes = __ballot(hit);
+    __syncthreads();
+    if (lane == 0) wcnt[wv] = __popcll(votes);
+    __syncthreads();
+    int before = __popcll(votes & ((1ull << lane) - 1ull)), all = 0;
+    for (int w = 0; w < kThreads / 64; ++w) { before += w < wv ? wcnt[w] : 0; all += wcnt[w]; }
+    const int64_t pos = base + before;
+    if (hit && pos < m.capacity) {
+      m.out_a[pos] = (uint32_t)a; m.out_b[pos] = (uint32_t)b; m.out_stat[pos] = v;
+      m.out_yaw[pos] = od == 7 ? match_wrap(m.map_mean[(int64_t)b * od + 3] - m.map_mean[(int64_t)a * od + 3], m.period) : 0.0;
+    }
+    base += all;
+  }
+}
+
 }  // namespace
+
+void launch_map_match(hipStream_t s, const MapMatchDev& m) {
+  const int B = T / m.od, nb = (m.n + B - 1) / B;
+  hipLaunchKernelGGL(k_mt_diag, dim3(m.n), dim3(64), 0, s, m);
+  if (m.od == 7) hipLaunchKernelGGL(k_mt_pairs<7>, dim3(nb, nb), dim3(kThreads), 0, s, m);
+  else hipLaunchKernelGGL(k_mt_pairs<9>, dim3(nb, nb), dim3(kThreads), 0, s, m);
+  hipLaunchKernelGGL(k_mt_count, dim3(m.n), dim3(kThreads), 0, s, m);
+  hipLaunchKernelGGL(k_mt_scan, dim3(1), dim3(kThreads), 0, s, m);
+  if (m.capacity > 0) hipLaunchKernelGGL(k_mt_scatter, dim3(m.n), dim3(kThreads), 0, s, m);
+}
 
 void launch_map_update(hipStream_t s, const MapUpdateDev& u) {
   const int nA = u.nA, nN = u.nN;

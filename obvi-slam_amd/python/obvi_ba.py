@@ -255,6 +255,39 @@ class Map:
                _ptr(where, C.c_uint32), C.byref(new))
         return self._conditioned(ba, rc, new, "map_merge"), where
 
+    # ---- which objects are duplicates (include/obvi_map_match.h) ----
+    def match(self, ba, gate, labels=None, row_mask=0, max_centre_distance=float("inf"), yaw_period=0.0, capacity=None):
+        """(a, b, stat, yaw_offset, counts): the pairs a < b of this map's objects whose difference, on the rows of row_mask, is within `gate` in units of its own
+        covariance, in (a, b) order; counts = (found, tested, singular).  capacity None: a count-only call, then one of the exact size."""
+        try:
+            f = getattr(self._lib, self._pre + "map_match")
+        except AttributeError:
+            raise ObviError("%smap_match: this library cannot match objects of a map (include/obvi_map_match.h is served by libobvi_ba.so only)" % self._pre)
+        f.restype = C.c_int
+        lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.int32).ravel()
+        if lab is not None and len(lab) != self.n_objects:
+            raise ObviError("map_match: labels must name every object of the map")
+        counts = np.zeros(3, np.int64)
+
+        def call(cap, a, b, s, w):
+            ba._check(f(ba._h, self._m, _ptr(lab, C.c_int32), C.c_uint32(int(row_mask)), C.c_double(gate), C.c_double(max_centre_distance), C.c_double(yaw_period),
+                        C.c_int64(cap), _ptr(a, C.c_uint32), _ptr(b, C.c_uint32), _ptr(s, C.c_double), _ptr(w, C.c_double), _ptr(counts, C.c_int64)), "map_match")
+
+        counted = capacity is None
+        if counted:
+            call(0, None, None, None, None)
+            capacity = counts[0]
+        capacity = int(capacity)
+        if capacity < 0:
+            call(capacity, None, None, None, None)                     # refused: raises
+        a, b, s, w = np.zeros(capacity, np.uint32), np.zeros(capacity, np.uint32), np.zeros(capacity), np.zeros(capacity)
+        if capacity > 0:
+            call(capacity, a, b, s, w)
+        elif not counted:
+            call(0, None, None, None, None)
+        k = min(capacity, int(counts[0]))
+        return a[:k], b[:k], s[:k], w[:k], tuple(int(c) for c in counts)
+
     def close(self):
         if self._m:
             f = getattr(self._lib, self._pre + "map_destroy")
@@ -273,6 +306,33 @@ class Map:
             self.close()
         except Exception:
             pass
+
+
+def map_match_resolve(od, a, b, stat, max_pairs=None, library=None, prefix="obvi_"):
+    """(drop, keep, sel): candidate pairs a < b with their statistics (Map.match) resolved, greedily in ascending (stat, a, b) order, into lists Map.merge accepts
+    as they are -- no object dropped twice, no dropped object kept; sel[i] is the position of selected pair i in the input.  Host only: no handle, no device."""
+    path = library or default_library_path()
+    if not os.path.exists(path):
+        raise ObviError("%s not found: build it with __graft_entry__.build() -- there is no CPU fallback" % path)
+    try:
+        f = getattr(C.CDLL(path), prefix + "map_match_resolve")
+    except AttributeError:
+        raise ObviError("%smap_match_resolve: this library cannot match objects of a map (include/obvi_map_match.h is served by libobvi_ba.so only)" % prefix)
+    f.restype = C.c_int
+    ia, ib = np.ascontiguousarray(a, dtype=np.uint32).ravel(), np.ascontiguousarray(b, dtype=np.uint32).ravel()
+    st = _f64(stat).ravel()
+    if not len(ia) == len(ib) == len(st):
+        raise ObviError("map_match_resolve: a, b and stat differ in length")
+    if max_pairs is None:
+        max_pairs = MAP_GROUP_MAX_ROWS // (int(od) or 7)
+    room = max(1, min(int(max_pairs), len(ia)))
+    drop, keep, sel = np.zeros(room, np.uint32), np.zeros(room, np.uint32), np.zeros(room, np.uint32)
+    q = C.c_int64(0)
+    rc = f(C.c_int32(int(od)), C.c_int64(len(ia)), _ptr(ia, C.c_uint32), _ptr(ib, C.c_uint32), _ptr(st, C.c_double), C.c_int64(int(max_pairs)),
+           _ptr(drop, C.c_uint32), _ptr(keep, C.c_uint32), _ptr(sel, C.c_uint32), C.byref(q))
+    if rc != 0:
+        raise ObviError("%smap_match_resolve failed: status %d" % (prefix, rc))
+    return drop[:q.value], keep[:q.value], sel[:q.value]
 
 
 class BundleAdjuster:

@@ -12,7 +12,9 @@ with the whole-map group prior on member 0, and the wall time of the collective 
 the same call on ONE handle that holds the joint problem.
 --merge: a map that shrinks -- obvi_map_merge of 1, 10 and 30 pairs of the 200-object map (noise on every pair), wait included, against the
 round trip that merges without it: obvi_map_get, the same formula in numpy, obvi_map_create.
-usage (GPU box, repo root): python scripts/map_bench.py [--update | --extend | --merge | --shared K]"""
+--match: which objects are duplicates -- obvi_map_match over all 19 900 pairs of the 200-object map (whole block, no labels), both waits
+included, against the only route without it: obvi_map_get and the same statistic vectorised in numpy; nothing is uploaded again on either side.
+usage (GPU box, repo root): python scripts/map_bench.py [--update | --extend | --merge | --match | --shared K]"""
 import os
 import sys
 import time
@@ -264,6 +266,57 @@ def merge():
     mp.close()
 
 
+def numpy_match(mean, cov, gate):
+    """The statistic of include/obvi_map_match.h for every pair on the host, vectorised: whole block, no labels, no distance."""
+    n = len(mean)
+    a, b = np.triu_indices(n, 1)
+    blocks = (0.5 * (cov + cov.T)).reshape(n, OD, n, OD).transpose(0, 2, 1, 3)
+    Tm = blocks[b, b] - blocks[b, a] - blocks[a, b] + blocks[a, a]
+    d = mean[b] - mean[a]
+    s = np.einsum("pi,pi->p", d, np.linalg.solve(Tm, d[:, :, None])[:, :, 0])
+    hit = s <= gate
+    return a[hit], b[hit], s[hit]
+
+
+def match():
+    """duplicate objects of the map proposed.  The device entry (a count-only call, then one of the exact size) against the only route without
+    it: obvi_map_get and the same statistic in numpy; nothing is uploaded again on either side."""
+    rng = np.random.default_rng(1)
+    mean, cov = rng.normal(size=(N_MAP, OD)), spd(rng, N_MAP * OD)
+    mp = obvi_ba.Map.create(mean, cov, object_block_size=OD)
+    ba = obvi_ba.BundleAdjuster(object_block_size=OD)
+    ba.set_cameras(synth.K_DEFAULT[None], synth.EXT_DEFAULT[None])
+    ba.set_poses(np.zeros((1, 6)), np.ones(1, np.uint8))
+    ba.set_points(np.zeros((0, 3)), np.zeros(0, np.uint8))
+    ba.set_objects(np.zeros((1, OD)), np.zeros(1, np.uint8))
+    pairs = N_MAP * (N_MAP - 1) // 2
+    s_all = numpy_match(mean, cov, np.inf)[2]
+    for want in (20, pairs):
+        v = np.sort(s_all)
+        gate = 0.5 * (v[want - 1] + v[want]) if want < pairs else 2.0 * v[-1]
+        last = {}
+
+        def round_trip():
+            old_mean, old_cov = mp.get()
+            last["host"] = numpy_match(old_mean, old_cov, gate)
+
+        def device():
+            last["dev"] = mp.match(ba, gate)
+
+        def device_sized():
+            last["dev"] = mp.match(ba, gate, capacity=pairs)
+        base, b = timed(round_trip)
+        two, d2 = timed(device)
+        one, d1 = timed(device_sized)
+        ha, hb, hs = last["host"]
+        da, db, ds, _, counts = last["dev"]
+        same = np.array_equal(ha, da) and np.array_equal(hb, db)
+        print("%d objects (%d rows, %d pairs), %5d found: obvi_map_get + numpy %s   obvi_map_match, count then exact size %s  (x %.1f)   one call, capacity = all pairs %s  (x %.1f)   "
+              "same pairs: %s   |s - numpy's| / s %.1e" % (N_MAP, N_MAP * OD, pairs, counts[0], base, two, b / d2, one, b / d1, same, float((np.abs(ds - hs) / hs).max()) if same else np.nan))
+    ba.close()
+    mp.close()
+
+
 def shared(n_sessions):
     """the map entries on handles that exchange shared objects."""
     import dist_util
@@ -328,4 +381,4 @@ if __name__ == "__main__":
     if "--shared" in sys.argv[1:]:
         shared(int(sys.argv[sys.argv.index("--shared") + 1]))
         sys.exit(0)
-    merge() if "--merge" in sys.argv[1:] else extend() if "--extend" in sys.argv[1:] else update() if "--update" in sys.argv[1:] else main()
+    match() if "--match" in sys.argv[1:] else merge() if "--merge" in sys.argv[1:] else extend() if "--extend" in sys.argv[1:] else update() if "--update" in sys.argv[1:] else main()
