@@ -225,7 +225,8 @@ void launch_map_factorize(hipStream_t s, const MapCutDev& m, int nt_max);
 // [tile rows][nA] tiles of 64 x 64, tile-major (chol_tile.h), the ragged last tiles padded with zeros (Wn: with the identity, as the cut pads).
 // The same launches grow the map (include/obvi_map_extend.h): the window also held N_B rows of objects B the map lacks, the posterior is over (A, B) with the
 // leading dimension ldp = N_A + N_B, and the new map has ldo = N + N_B rows, B behind the old ones: C'[old, B] = Y V^T with V = Ps_BA W^T.  A map that is only
-// conditioned has N_B = 0, ldp = N_A, ldo = N.
+// conditioned has N_B = 0, ldp = N_A, ldo = N.  C' and mu' come from the downdate path the merge below shares (map_kernels.hip: k_map_downdate, k_map_wd,
+// k_map_mean), here on the old map's own rows.
 struct MapUpdateDev {
   int32_t od, N, NA, nN, nA;
   int32_t NB, nB, ldp, ldo;                                  // rows of B in nB tile rows; leading dimensions of P and of out_cov
@@ -240,11 +241,10 @@ struct MapUpdateDev {
   double* out_mean; double* out_cov;                         // the new map: [ldo], [ldo][ldo]
   double* status;                                            // the cut's record: MS_NONFINITE is set to 1 by whoever writes a non-finite entry of the new map
 };
-// ten launches; status[MS_NONFINITE] must have been zeroed on the stream
-void launch_map_update(hipStream_t s, const MapUpdateDev& u);
-// The map grown by B: the update's launches into the larger map, then Ps_BA staged, V, the cross block Y V^T along the rows of both of its copies, and the
-// window's whole (A, B) block and means scattered last.  N_A = 0: the old block is symmetrised and copied (out_cov's cross blocks must have been zeroed on the
-// stream); N = 0 too: the scatter alone.  No grid has a zero dimension.  status[MS_NONFINITE] must have been zeroed on the stream.
+// The map conditioned and, N_B > 0, grown by B: the operands (Wn and Ps_AA, G, Y, U, M, Z), Ps_BA staged and V, v, the downdate C' and mu' on the old map's
+// rows, the cross block Y V^T along the rows of both of its copies, and the window's whole (A, B) block and means scattered last.  N_B = 0 (the condition):
+// Ps_BA, V and the cross block are skipped -- ten launches.  N_A = 0: the old block is symmetrised and copied (out_cov's cross blocks must have been zeroed on
+// the stream); N = 0 too: the scatter alone.  No grid has a zero dimension.  status[MS_NONFINITE] must have been zeroed on the stream.
 void launch_map_extend(hipStream_t s, const MapUpdateDev& u);
 // out[i][j] = cov[rows(i)][rows(j)], out_mean[i] = mean[rows(i)] for the k objects idx of a map of ldc rows: a copy, nothing is symmetrised
 void launch_map_select(hipStream_t s, const uint32_t* idx, int32_t k, int32_t od, const double* mean, const double* cov, int64_t ldc, double* out_mean, double* out_cov);
@@ -259,11 +259,10 @@ struct MapMergeDev {
   const double* offset; const double* noise;                 // [Q] d (never NULL: zeros); [Q / od][od][od] as given (not symmetrised), NULL: exact
   const double* map_mean; const double* map_cov;             // the old map: [N], [N][N]
   double* Wn; double* G; double* Y; double* v;               // tiles; v [64 nQ] = W (H mu - d)
-  double* out_mean; double* out_cov;                         // the new map: [NK], [NK][NK]
-  double* status;                                            // the cut's record; MS_NONFINITE as in MapUpdateDev
+  double* out_mean; double* out_cov;                         // the new map: [NK], [NK][NK]; a non-finite entry sets MS_NONFINITE of the cut's record
 };
-// T and H mu - d into the cut, its factor and condition estimate (x0: the map's start vector), G, Wn, Y, the hot launch C', v, mu'.  The cut's W and the padding
-// of its Lambda, and status, must have been zeroed on the stream.
+// T and H mu - d into the cut, its factor and condition estimate (x0: the map's start vector), G, Wn, Y, then the downdate path of MapUpdateDev through the
+// row table `kept` with Z = Y: C', v, mu'.  The cut's W, the padding of its Lambda and its status record must have been zeroed on the stream.
 void launch_map_merge(hipStream_t s, const MapMergeDev& g, const double* x0);
 // Duplicate objects of a map proposed (include/obvi_map_match.h; map_kernels.hip): every pair a < b of the n objects that passes the label and centre-distance
 // tests gets s = d^T T^-1 d on the rows of `mask`, d = mu_b - mu_a (row 3 wrapped by `period`), T = Cs_bb - Cs_ba - Cs_ab + Cs_aa.  stat [n][n], upper

@@ -6,11 +6,14 @@
 //   Li : nt tiles, the inverses of the diagonal tiles of L
 //   Wt : tile (i, k), k <= i, holds (W_ik)^T -- the operand order tile_abt_mfma (C += A B^T) wants in stages 3 and 4
 // and Csym, the sub-block again as N rows of ld doubles (the layout of Lambda), for the power steps on C.
-// Second half of the file: a map conditioned on the posterior of a window's objects (include/obvi_map_update.h, MapUpdateDev): tile products on the factor of a
-// one-group cut, under the same rules.  Third part: the map grown by the window's new objects, born from a posterior, or gathered down to some of its objects
-// (include/obvi_map_extend.h): the same launches into a larger map, the cross block, and the scatter of the window's whole block.  Fourth part: duplicate
-// objects of the map merged (include/obvi_map_merge.h): the innovation covariance of the pairs built in a one-group cut and factored as any cut, the gain tiles
-// of the surviving rows alone, and the downdate written straight into the smaller map.  Fifth part: duplicate objects of the map proposed
+// Second half of the file: the entries that write a new map.  They share ONE downdate path -- k_map_downdate (C' = Cs[rows, rows] - Z Y^T on a row table),
+// k_map_wd (v = W d) and k_map_mean (mu' = mu[rows] + sign Y v) -- on the factor of a one-group cut, under the same rules, and three callers feed it: the map
+// conditioned on the posterior of a window's objects (include/obvi_map_update.h, MapUpdateDev: identity rows, Z = Y (I - W Ps W^T), sign +); the map grown by
+// the window's new objects, born from a posterior, or gathered down to some of its objects (include/obvi_map_extend.h: the condition's launches into a larger
+// map, plus the cross block; the condition IS the extension by no object, and both end in the scatter of the window's whole block); duplicate objects of the
+// map merged (include/obvi_map_merge.h: the innovation covariance of the pairs built in a one-group cut and factored as any cut, the gain tiles of the
+// surviving rows alone, then the downdate through the survivors' row table with Z = Y, sign -, straight into the smaller map).  Every read of a symmetrised
+// entry of a map or a posterior goes through stage_sym / sym_at.  Last part: duplicate objects of the map proposed
 // (include/obvi_map_match.h): every pair's difference in units of its own covariance, one lane per pair, and the pairs within the gate compacted in (a, b) order
 // by counts and a scan.
 #include "chol_tile.h"
@@ -39,8 +42,59 @@ __device__ __forceinline__ void acc_to_tile(double* tile, const f64x4 acc[4]) {
     for (int r = 0; r < 4; ++r) tile[(16 * rt + (lane >> 4) + 4 * r) * T + 16 * wv + (lane & 15)] = acc[rt][r];
 }
 
+// ---- what every part of the file shares: row tables, the symmetrised read, a tile written to both triangles ---------------------------------------
+// Row w of a list of n rows, od per object -> its row of the map, idx[w / od] od + w % od (idx NULL: w itself); -1 behind the list: padding
+__device__ __forceinline__ int32_t table_row(const uint32_t* idx, int od, int n, int w) { return w >= n ? -1 : (idx != nullptr ? (int32_t)idx[w / od] * od + w % od : w); }
+// one tile row's 64 entries of a table, by the first 64 threads; a barrier before anyone reads them
+__device__ __forceinline__ void fill_rows(int32_t* t, const uint32_t* idx, int od, int n, int tile) { if (threadIdx.x < T) t[threadIdx.x] = table_row(idx, od, n, T * tile + threadIdx.x); }
+// The symmetrised two-sided read of Cs = (C + C^T) / 2 at rows ra x columns cb (two tables of 64 rows of C in LDS): both blocks of C are read along their rows,
+// P[a][b] = C[ra[a]][cb[b]] and Q[a][b] = C[cb[a]][ra[b]], zero in the padding, and meet in LDS: behind a barrier Cs[ra[r]][cb[c]] = sym_at(P, Q, r, c).
+// Each tile travels in two phases, as tile_fetch / tile_put do it: all of a thread's loads first, then its LDS writes (one loop of load + store waits for every
+// load on its own: sixteen memory latencies per tile).
+__device__ __forceinline__ void stage_sym(double* P, double* Q, const double* C, int64_t ld, const int32_t* ra, const int32_t* cb) {
+  constexpr int X = T * T / kThreads;
+  const int b = threadIdx.x & 63, a0 = threadIdx.x >> 6;   // element x of a thread: row a0 + 4 x, column b
+  const int32_t pb = cb[b], qb = ra[b];
+  double p[X], q[X];
+#pragma unroll
+  for (int x = 0; x < X; ++x) {
+    const int32_t pa = ra[a0 + (kThreads / T) * x];
+    const double c = C[(pa >= 0 && pb >= 0) ? (int64_t)pa * ld + pb : 0];   // unconditional, or every load gets a block and a wait of its own; C[0] is there
+    p[x] = (pa >= 0 && pb >= 0) ? c : 0.0;
+  }
+#pragma unroll
+  for (int x = 0; x < X; ++x) P[(a0 + (kThreads / T) * x) * LDM + b] = p[x];
+#pragma unroll
+  for (int x = 0; x < X; ++x) {
+    const int32_t qa = cb[a0 + (kThreads / T) * x];
+    const double c = C[(qa >= 0 && qb >= 0) ? (int64_t)qa * ld + qb : 0];
+    q[x] = (qa >= 0 && qb >= 0) ? c : 0.0;
+  }
+#pragma unroll
+  for (int x = 0; x < X; ++x) Q[(a0 + (kThreads / T) * x) * LDM + b] = q[x];
+}
+__device__ __forceinline__ double sym_at(const double* P, const double* Q, int r, int c) { return 0.5 * (P[r * LDM + c] + Q[c * LDM + r]); }
+// Tile (ti, tj) of an nr x nc block, row-major in LDS, to out[T ti + r][off + T tj + c] and, transposed, to out[off + T tj + r][T ti + c]: both copies are
+// written along their rows.  lower: a diagonal tile of a symmetric block -- written once, its upper half mirrored from its lower.  Returns whether an entry
+// of the first copy is not finite.
+__device__ __forceinline__ bool tile_to_both_triangles(const double* A, double* out, int64_t ldo, int ti, int tj, int nr, int nc, int off, bool lower) {
+  bool bad = false;
+  for (int e = threadIdx.x; e < T * T; e += kThreads) {
+    const int r = e >> 6, c = e & 63;
+    const int gi = T * ti + r, gj = T * tj + c;
+    if (gi < nr && gj < nc) {
+      const double x = (lower && c > r) ? A[c * LDM + r] : A[r * LDM + c];
+      out[(int64_t)gi * ldo + off + gj] = x;
+      bad = bad || !isfinite(x);
+    }
+    const int hj = T * tj + r, hi = T * ti + c;
+    if (!lower && hi < nr && hj < nc) out[(int64_t)(off + hj) * ldo + hi] = A[c * LDM + r];
+  }
+  return bad;
+}
+
 // ---- stage 1: gather ---------------------------------------------------------------------------------------------------------------------
-// workgroup (ti, tj <= ti, group): A_ij = (C[rows i][rows j] + C[rows j][rows i]^T) / 2.  Both blocks of the map are read along their rows and meet in LDS.
+// workgroup (ti, tj <= ti, group): A_ij = (C[rows i][rows j] + C[rows j][rows i]^T) / 2, the symmetrised read above
 __global__ void __launch_bounds__(kThreads) k_map_gather(MapCutDev m, const double* __restrict__ map_mean, const double* __restrict__ map_cov, int64_t ldc) {
   __shared__ double P[T * LDM];
   __shared__ double Q[T * LDM];
@@ -52,33 +106,24 @@ __global__ void __launch_bounds__(kThreads) k_map_gather(MapCutDev m, const doub
     if (ti >= G.nt) continue;
     const int od = m.od, tid = threadIdx.x;
     __syncthreads();
-    if (tid < 2 * T) {   // map row of every row of the two tile rows; -1: padding
-      const int gi = T * (tid < T ? ti : tj) + (tid & (T - 1));
-      int32_t mr = -1;
-      if (gi < G.N) mr = (int32_t)m.map_idx[G.member0 + gi / od] * od + gi % od;
-      (tid < T ? rows_i : rows_j)[tid & (T - 1)] = mr;
-    }
+    fill_rows(rows_i, m.map_idx + G.member0, od, G.N, ti);
+    fill_rows(rows_j, m.map_idx + G.member0, od, G.N, tj);
     __syncthreads();
-    for (int e = tid; e < T * T; e += kThreads) {
-      const int r = e >> 6, c = e & 63;
-      const int32_t ai = rows_i[r], aj = rows_j[c], bj = rows_j[r], bi = rows_i[c];
-      P[r * LDM + c] = (ai >= 0 && aj >= 0) ? map_cov[(int64_t)ai * ldc + aj] : 0.0;   // C[row i_r][col j_c]
-      Q[r * LDM + c] = (bj >= 0 && bi >= 0) ? map_cov[(int64_t)bj * ldc + bi] : 0.0;   // C[row j_r][col i_c]
-    }
+    stage_sym(P, Q, map_cov, ldc, rows_i, rows_j);
     __syncthreads();
     double* tile = tile_ptr(m.A + G.tile0 * (T * T), G.nt, ti, tj);
     double* Cs = m.Csym + G.lam_off;
     for (int e = tid; e < T * T; e += kThreads) {
       const int r = e >> 6, c = e & 63, gi = T * ti + r, gj = T * tj + c;
       const bool in = gi < G.N && gj < G.N;
-      const double v = in ? 0.5 * (P[r * LDM + c] + Q[c * LDM + r]) : (gi == gj ? 1.0 : 0.0);
+      const double v = in ? sym_at(P, Q, r, c) : (gi == gj ? 1.0 : 0.0);
       tile[e] = v;
       if (in) Cs[(int64_t)gi * G.ld + gj] = v;
     }
     if (ti != tj) {   // the upper triangle of Csym, written along its rows
       for (int e = tid; e < T * T; e += kThreads) {
         const int r = e >> 6, c = e & 63, gj = T * tj + r, gi = T * ti + c;
-        if (gi < G.N && gj < G.N) Cs[(int64_t)gj * G.ld + gi] = 0.5 * (P[c * LDM + r] + Q[r * LDM + c]);
+        if (gi < G.N && gj < G.N) Cs[(int64_t)gj * G.ld + gi] = sym_at(P, Q, c, r);
       }
     }
     if (tj == 0 && tid < T && rows_i[tid] >= 0) m.mean[(int64_t)od * G.member0 + T * ti + tid] = map_mean[rows_i[tid]];
@@ -330,46 +375,40 @@ __global__ void __launch_bounds__(64) k_map_power_finish(MapCutDev m) {
   }
 }
 
-// ==== the map conditioned on a window's posterior (include/obvi_map_update.h; MapUpdateDev, ba_device.h) ==================================================
+// ==== the map conditioned on a window's posterior (include/obvi_map_update.h; MapUpdateDev, ba_device.h), and the downdate path ===========================
 // Every kernel below writes tiles or rows that no other workgroup of its launch writes, reads only what earlier launches wrote, and sums in a fixed order.
-__device__ __forceinline__ int32_t window_map_row(const MapUpdateDev& u, int w) { return w < u.NA ? (int32_t)u.map_idx[w / u.od] * u.od + w % u.od : -1; }
-
-// (ti, tj, 0): Wn_ij = (Wt_ij)^T for j <= i, zero above;  (ti, tj, 1): Ps_ij = (P + P^T) / 2, zero in the padding
-__global__ void __launch_bounds__(kThreads) k_mu_operands(MapUpdateDev u) {
+// (ti, tj, 0): Wn_ij = (Wt_ij)^T for j <= i, zero above -- the cut's W as [nt][nt] tiles;  (ti, tj, 1), the window's alone: Ps_ij = (P + P^T) / 2 of the
+// leading NA rows of the posterior, zero in the padding
+__global__ void __launch_bounds__(kThreads) k_mu_operands(const double* Wt, double* Wn, int nt, const double* P, int64_t ldp, int NA, double* Ps) {
   __shared__ double A[T * LDM];
   const int ti = blockIdx.x, tj = blockIdx.y, tid = threadIdx.x;
   if (blockIdx.z == 0) {
-    double* wn = tile_ptr(u.Wn, u.nA, ti, tj);
-    if (tj <= ti) stage_tile(A, tile_ptr(const_cast<double*>(u.Wt), u.nA, ti, tj));
+    double* wn = tile_ptr(Wn, nt, ti, tj);
+    if (tj <= ti) stage_tile(A, tile_ptr(const_cast<double*>(Wt), nt, ti, tj));
     __syncthreads();
     for (int e = tid; e < T * T; e += kThreads) wn[e] = tj <= ti ? A[(e & 63) * LDM + (e >> 6)] : 0.0;
     return;
   }
-  double* ps = tile_ptr(u.Ps, u.nA, ti, tj);
+  double* ps = tile_ptr(Ps, nt, ti, tj);
   for (int e = tid; e < T * T; e += kThreads) {
     const int gi = T * ti + (e >> 6), gj = T * tj + (e & 63);
-    ps[e] = (gi < u.NA && gj < u.NA) ? 0.5 * (u.P[(int64_t)gi * u.ldp + gj] + u.P[(int64_t)gj * u.ldp + gi]) : 0.0;
+    ps[e] = (gi < NA && gj < NA) ? 0.5 * (P[gi * ldp + gj] + P[gj * ldp + gi]) : 0.0;
   }
 }
 
-// (ti, tj): G_ij = Cs[rows of tile row i][window columns of tile column j]; the two blocks of the map are read along their rows and meet in LDS, as in k_map_gather
+// (ti, tj): G_ij = Cs[rows of tile row i][window columns of tile column j], zero in the padding
 __global__ void __launch_bounds__(kThreads) k_mu_gather(MapUpdateDev u) {
   __shared__ double P[T * LDM];
   __shared__ double Q[T * LDM];
-  __shared__ int32_t cols[T];
+  __shared__ int32_t rows[T], cols[T];
   const int ti = blockIdx.x, tj = blockIdx.y, tid = threadIdx.x;
-  if (tid < T) cols[tid] = window_map_row(u, T * tj + tid);
+  fill_rows(rows, nullptr, u.od, u.N, ti);
+  fill_rows(cols, u.map_idx, u.od, u.NA, tj);
   __syncthreads();
-  const int64_t ldc = u.N;
-  for (int e = tid; e < T * T; e += kThreads) {
-    const int a = e >> 6, b = e & 63;
-    const int gr = T * ti + a, gb = T * ti + b;
-    P[a * LDM + b] = (gr < u.N && cols[b] >= 0) ? u.map_cov[(int64_t)gr * ldc + cols[b]] : 0.0;   // C[row r_a][col A_b]
-    Q[a * LDM + b] = (cols[a] >= 0 && gb < u.N) ? u.map_cov[(int64_t)cols[a] * ldc + gb] : 0.0;   // C[row A_a][col r_b]
-  }
+  stage_sym(P, Q, u.map_cov, u.N, rows, cols);
   __syncthreads();
   double* g = tile_ptr(u.G, u.nA, ti, tj);
-  for (int e = tid; e < T * T; e += kThreads) { const int r = e >> 6, c = e & 63; g[e] = 0.5 * (P[r * LDM + c] + Q[c * LDM + r]); }
+  for (int e = tid; e < T * T; e += kThreads) g[e] = sym_at(P, Q, e >> 6, e & 63);
 }
 
 // C_ij = sum_k A_ik B_jk^T over tiles; kmode 0: k < kn, 1: k <= j, 2: k <= i (the lower triangular W as B, as A).  sym: C = I - sum, the tiles j <= i computed
@@ -401,105 +440,81 @@ __global__ void __launch_bounds__(kThreads) k_mu_gemm(MuGemm g) {
   }
 }
 
-// The hot launch.  (ti, tj <= ti): C'_ij = Cs_ij - sum_k Z_ik Y_jk^T, k ascending; written along the rows of both triangles, a diagonal tile from its lower triangle.
-__global__ void __launch_bounds__(kThreads) k_mu_cov(MapUpdateDev u) {
+// The hot launch, the downdate every entry ends in: the new map's block C'_ij = Cs[rows_i, rows_j] - sum_k Z_ik Y_jk^T for (ti, tj <= ti), k ascending.  The
+// rows of the old map behind the block's n rows are the objects `kept` (the merge: the survivors) or, kept NULL, the rows themselves (the condition and the
+// extension: the old map's block of the new one).  Z == Y (the merge): a diagonal tile stages one operand for both.  Written along the rows of both triangles,
+// a diagonal tile from its lower half: C' is symmetric bit for bit.
+struct MapDowndate {
+  const double* Z; const double* Y; int32_t nk;   // [tile rows][nk] tiles each
+  const uint32_t* kept; int32_t od, n;            // the block's rows
+  int64_t ldc, ldo;
+  const double* map_cov; double* out_cov; double* status;
+};
+__global__ void __launch_bounds__(kThreads) k_map_downdate(MapDowndate d) {
   __shared__ double A[T * LDM];
   __shared__ double B[T * LDM];
+  __shared__ int32_t rows_i[T], rows_j[T];
   const int ti = blockIdx.x, tj = blockIdx.y, tid = threadIdx.x;
   if (tj > ti) return;
+  fill_rows(rows_i, d.kept, d.od, d.n, ti);
+  fill_rows(rows_j, d.kept, d.od, d.n, tj);
+  const bool one = ti == tj && d.Z == d.Y;
   f64x4 acc[4] = {};
-  for (int k = 0; k < u.nA; ++k) {
+  for (int k = 0; k < d.nk; ++k) {
     __syncthreads();
-    stage_tiles(A, tile_ptr(u.Z, u.nA, ti, k), B, tile_ptr(u.Y, u.nA, tj, k));
+    if (!one) stage_tiles(A, tile_ptr(const_cast<double*>(d.Z), d.nk, ti, k), B, tile_ptr(const_cast<double*>(d.Y), d.nk, tj, k));
+    else stage_tile(A, tile_ptr(const_cast<double*>(d.Y), d.nk, ti, k));
     __syncthreads();
-    tile_abt_mfma(A, B, acc);
+    tile_abt_mfma(A, one ? A : B, acc);
   }
   __syncthreads();
-  const int N = u.N;
-  const int64_t ldc = N, ldo = u.ldo;
-  for (int e = tid; e < T * T; e += kThreads) {   // the old map's two blocks, each along its rows
-    const int a = e >> 6, b = e & 63;
-    const int ia = T * ti + a, jb = T * tj + b, ja = T * tj + a, ib = T * ti + b;
-    A[a * LDM + b] = (ia < N && jb < N) ? u.map_cov[(int64_t)ia * ldc + jb] : 0.0;
-    B[a * LDM + b] = (ja < N && ib < N) ? u.map_cov[(int64_t)ja * ldc + ib] : 0.0;
-  }
+  stage_sym(A, B, d.map_cov, d.ldc, rows_i, rows_j);   // the old map's two blocks, each along its rows
   __syncthreads();
   const int lane = tid & 63, wv = tid >> 6;
   double v[4][4];
 #pragma unroll
   for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = 16 * rt + (lane >> 4) + 4 * r, col = 16 * wv + (lane & 15);
-      v[rt][r] = 0.5 * (A[row * LDM + col] + B[col * LDM + row]) - acc[rt][r];
-    }
+    for (int r = 0; r < 4; ++r) v[rt][r] = sym_at(A, B, 16 * rt + (lane >> 4) + 4 * r, 16 * wv + (lane & 15)) - acc[rt][r];
   __syncthreads();
 #pragma unroll
   for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
     for (int r = 0; r < 4; ++r) A[(16 * rt + (lane >> 4) + 4 * r) * LDM + 16 * wv + (lane & 15)] = v[rt][r];
   __syncthreads();
-  bool bad = false;
-  for (int e = tid; e < T * T; e += kThreads) {
-    const int r = e >> 6, c = e & 63;
-    const int gi = T * ti + r, gj = T * tj + c;
-    if (gi < N && gj < N) {
-      const double x = (ti == tj && c > r) ? A[c * LDM + r] : A[r * LDM + c];
-      u.out_cov[(int64_t)gi * ldo + gj] = x;
-      bad = bad || !isfinite(x);
-    }
-    const int hj = T * tj + r, hi = T * ti + c;
-    if (ti != tj && hi < N && hj < N) u.out_cov[(int64_t)hj * ldo + hi] = A[c * LDM + r];
-  }
-  if (bad) u.status[MS_NONFINITE] = 1.0;
+  if (tile_to_both_triangles(A, d.out_cov, d.ldo, ti, tj, d.n, d.n, 0, ti == tj)) d.status[MS_NONFINITE] = 1.0;
 }
 
-// v = W (m - mu_A): workgroup b its 64 rows, four threads per row, the dot product split by column mod 4
-__global__ void __launch_bounds__(kThreads) k_mu_v(MapUpdateDev u) {
+// v = W d, d = a - b (b NULL: d = a), W dense and lower triangular, n x n: workgroup b its 64 rows, four threads per row, the dot product split by column mod 4
+template <bool DIFF>
+__device__ __forceinline__ double wd_part(const double* w, const double* a, const double* b, int part, int row) {
+  double s = 0.0;
+  for (int c = part; c <= row; c += 4) s += w[c] * (DIFF ? a[c] - b[c] : a[c]);
+  return s;
+}
+__global__ void __launch_bounds__(kThreads) k_map_wd(const double* W, const double* a, const double* b, int n, double* v) {
   const int row = T * blockIdx.x + (threadIdx.x >> 2), part = threadIdx.x & 3;
   double s = 0.0;
-  if (row < u.NA) for (int c = part; c <= row; c += 4) s += u.W[(int64_t)row * u.NA + c] * (u.pm[c] - u.mean_A[c]);
+  if (row < n) s = b != nullptr ? wd_part<true>(W + (int64_t)row * n, a, b, part, row) : wd_part<false>(W + (int64_t)row * n, a, nullptr, part, row);   // (one loop with the test inside it ran 4 us longer)
   s += __shfl_xor(s, 1, 64);
   s += __shfl_xor(s, 2, 64);
-  if (part == 0) u.v[row] = s;
+  if (part == 0) v[row] = s;
 }
-// mu' = mu + Y v: workgroup b its 64 map rows
-__global__ void __launch_bounds__(kThreads) k_mu_mean(MapUpdateDev u) {
+// mu'[row] = mu[its row of the old map] + sign (Y v)[row] on the rows of a downdate: workgroup b its 64 rows
+__global__ void __launch_bounds__(kThreads) k_map_mean(MapDowndate d, const double* v, double sign, const double* map_mean, double* out_mean) {
   const int r = threadIdx.x >> 2, part = threadIdx.x & 3, row = T * blockIdx.x + r;
   double s = 0.0;
-  for (int k = 0; k < u.nA; ++k) {
-    const double* y = tile_ptr(u.Y, u.nA, blockIdx.x, k) + r * T;
-    for (int c = part; c < T; c += 4) s += y[c] * u.v[T * k + c];
+  for (int k = 0; k < d.nk; ++k) {
+    const double* y = tile_ptr(const_cast<double*>(d.Y), d.nk, blockIdx.x, k) + r * T;
+    for (int c = part; c < T; c += 4) s += y[c] * v[T * k + c];
   }
   s += __shfl_xor(s, 1, 64);
   s += __shfl_xor(s, 2, 64);
-  if (part == 0 && row < u.N) {
-    const double x = u.map_mean[row] + s;
-    u.out_mean[row] = x;
-    if (!isfinite(x)) u.status[MS_NONFINITE] = 1.0;
+  if (part == 0 && row < d.n) {
+    const double x = map_mean[table_row(d.kept, d.od, d.n, row)] + sign * s;
+    out_mean[row] = x;
+    if (!isfinite(x)) d.status[MS_NONFINITE] = 1.0;
   }
-}
-// the window's own block and means: the posterior itself, bit for bit
-__global__ void __launch_bounds__(kThreads) k_mu_scatter(MapUpdateDev u) {
-  __shared__ int32_t rows[T], cols[T];
-  const int ti = blockIdx.x, tj = blockIdx.y, tid = threadIdx.x;
-  if (tid < 2 * T) (tid < T ? rows : cols)[tid & (T - 1)] = window_map_row(u, T * (tid < T ? ti : tj) + (tid & (T - 1)));
-  __syncthreads();
-  const double* ps = tile_ptr(u.Ps, u.nA, ti, tj);
-  bool bad = false;
-  for (int e = tid; e < T * T; e += kThreads) {
-    const int r = e >> 6, c = e & 63;
-    if (rows[r] < 0 || cols[c] < 0) continue;
-    const double x = ps[e];
-    u.out_cov[(int64_t)rows[r] * u.ldo + cols[c]] = x;
-    bad = bad || !isfinite(x);
-  }
-  if (tj == 0 && tid < T && rows[tid] >= 0) {
-    const double x = u.pm[T * ti + tid];
-    u.out_mean[rows[tid]] = x;
-    bad = bad || !isfinite(x);
-  }
-  if (bad) u.status[MS_NONFINITE] = 1.0;
 }
 
 // P[od a + r][od b + c] = blocks[a k + b][r][c], pm[od a + r] = objects[obj_idx[a]][r]
@@ -514,23 +529,21 @@ __global__ void __launch_bounds__(kThreads) k_mu_posterior_layout(const double* 
 
 // ==== the map grown by a window's new objects (include/obvi_map_extend.h) ===================================================================================
 // row of the new map of row w of the posterior over (A, B): A keeps its map rows, B follows the old map
-__device__ __forceinline__ int32_t window_new_row(const MapUpdateDev& u, int w) { return w < u.NA ? window_map_row(u, w) : (w < u.NA + u.NB ? u.N + (w - u.NA) : -1); }
+__device__ __forceinline__ int32_t window_new_row(const MapUpdateDev& u, int w) { return w < u.NA ? table_row(u.map_idx, u.od, u.NA, w) : (w < u.NA + u.NB ? u.N + (w - u.NA) : -1); }
 
-// (bi, aj): Pba_ij = Ps[B rows of tile row i][A columns of tile column j], zero in the padding; the two blocks of P are read along their rows and meet in LDS
+// (bi, aj): Pba_ij = Ps[B rows of tile row i][A columns of tile column j], zero in the padding
 __global__ void __launch_bounds__(kThreads) k_mx_stage(MapUpdateDev u) {
   __shared__ double P[T * LDM];
   __shared__ double Q[T * LDM];
+  __shared__ int32_t ra[T], rb[T];   // rows of the posterior: A's of tile column j, B's of tile row i
   const int ti = blockIdx.x, tj = blockIdx.y, tid = threadIdx.x;
-  const int64_t ld = u.ldp;
-  for (int e = tid; e < T * T; e += kThreads) {
-    const int a = e >> 6, b = e & 63;
-    const int bi = T * ti + a, aj = T * tj + b, ai = T * tj + a, bj = T * ti + b;
-    P[a * LDM + b] = (bi < u.NB && aj < u.NA) ? u.P[(int64_t)(u.NA + bi) * ld + aj] : 0.0;   // P[B row a][A col b]
-    Q[a * LDM + b] = (ai < u.NA && bj < u.NB) ? u.P[(int64_t)ai * ld + u.NA + bj] : 0.0;     // P[A row a][B col b]
-  }
+  fill_rows(ra, nullptr, u.od, u.NA, tj);
+  if (tid < T) rb[tid] = T * ti + tid < u.NB ? u.NA + T * ti + tid : -1;
+  __syncthreads();
+  stage_sym(P, Q, u.P, u.ldp, ra, rb);
   __syncthreads();
   double* t = tile_ptr(u.Pba, u.nA, ti, tj);
-  for (int e = tid; e < T * T; e += kThreads) { const int r = e >> 6, c = e & 63; t[e] = 0.5 * (Q[c * LDM + r] + P[r * LDM + c]); }
+  for (int e = tid; e < T * T; e += kThreads) t[e] = sym_at(P, Q, e & 63, e >> 6);   // Ps[A_c][B_r], as the scatter forms it
 }
 
 // (ti, tj): X_ij = sum_k Y_ik V_jk^T, k ascending -- rows of tile row i of the old map against the B rows of tile row j; written along the rows of both
@@ -538,7 +551,7 @@ __global__ void __launch_bounds__(kThreads) k_mx_stage(MapUpdateDev u) {
 __global__ void __launch_bounds__(kThreads) k_mx_cross(MapUpdateDev u) {
   __shared__ double A[T * LDM];
   __shared__ double B[T * LDM];
-  const int ti = blockIdx.x, tj = blockIdx.y, tid = threadIdx.x;
+  const int ti = blockIdx.x, tj = blockIdx.y;
   f64x4 acc[4] = {};
   for (int k = 0; k < u.nA; ++k) {
     __syncthreads();
@@ -549,44 +562,28 @@ __global__ void __launch_bounds__(kThreads) k_mx_cross(MapUpdateDev u) {
   __syncthreads();
   acc_to_lds(A, acc, 1.0);
   __syncthreads();
-  const int N = u.N, NB = u.NB;
-  const int64_t ldo = u.ldo;
-  bool bad = false;
-  for (int e = tid; e < T * T; e += kThreads) {
-    const int r = e >> 6, c = e & 63;
-    const int gi = T * ti + r, gj = T * tj + c;
-    if (gi < N && gj < NB) {
-      const double x = A[r * LDM + c];
-      u.out_cov[(int64_t)gi * ldo + N + gj] = x;
-      bad = bad || !isfinite(x);
-    }
-    const int hj = T * tj + r, hi = T * ti + c;
-    if (hj < NB && hi < N) u.out_cov[(int64_t)(N + hj) * ldo + hi] = A[c * LDM + r];
-  }
-  if (bad) u.status[MS_NONFINITE] = 1.0;
+  if (tile_to_both_triangles(A, u.out_cov, u.ldo, ti, tj, u.N, u.NB, u.N, false)) u.status[MS_NONFINITE] = 1.0;
 }
 
-// (ti, tj) over the tiles of the posterior: the window's whole block of the new map and its means are the posterior itself, (P + P^T) / 2 and pm bit for bit
+// (ti, tj) over the tiles of the posterior: the window's whole block of the new map and its means are the posterior itself, (P + P^T) / 2 and pm bit for bit.
+// N_B = 0: the condition's scatter.
 __global__ void __launch_bounds__(kThreads) k_mx_scatter(MapUpdateDev u) {
   __shared__ double P[T * LDM];
   __shared__ double Q[T * LDM];
-  __shared__ int32_t rows[T], cols[T];
+  __shared__ int32_t src_i[T], src_j[T], rows[T], cols[T];   // rows of the posterior, and where they go in the new map
   const int ti = blockIdx.x, tj = blockIdx.y, tid = threadIdx.x;
-  if (tid < 2 * T) (tid < T ? rows : cols)[tid & (T - 1)] = window_new_row(u, T * (tid < T ? ti : tj) + (tid & (T - 1)));
-  const int NP = u.NA + u.NB;
-  const int64_t ld = u.ldp;
-  for (int e = tid; e < T * T; e += kThreads) {
-    const int a = e >> 6, b = e & 63;
-    const int ia = T * ti + a, jb = T * tj + b, ja = T * tj + a, ib = T * ti + b;
-    P[a * LDM + b] = (ia < NP && jb < NP) ? u.P[(int64_t)ia * ld + jb] : 0.0;
-    Q[a * LDM + b] = (ja < NP && ib < NP) ? u.P[(int64_t)ja * ld + ib] : 0.0;
-  }
+  const int32_t to = tid < 2 * T ? window_new_row(u, T * (tid < T ? ti : tj) + (tid & (T - 1))) : -1;   // asked for first: map_idx arrives beside the tiles
+  fill_rows(src_i, nullptr, u.od, u.NA + u.NB, ti);
+  fill_rows(src_j, nullptr, u.od, u.NA + u.NB, tj);
+  __syncthreads();
+  stage_sym(P, Q, u.P, u.ldp, src_i, src_j);
+  if (tid < 2 * T) (tid < T ? rows : cols)[tid & (T - 1)] = to;
   __syncthreads();
   bool bad = false;
   for (int e = tid; e < T * T; e += kThreads) {
     const int r = e >> 6, c = e & 63;
     if (rows[r] < 0 || cols[c] < 0) continue;
-    const double x = 0.5 * (P[r * LDM + c] + Q[c * LDM + r]);
+    const double x = sym_at(P, Q, r, c);
     u.out_cov[(int64_t)rows[r] * u.ldo + cols[c]] = x;
     bad = bad || !isfinite(x);
   }
@@ -617,16 +614,10 @@ __global__ void __launch_bounds__(kThreads) k_map_select(const uint32_t* __restr
 
 // ==== duplicate objects of the map merged (include/obvi_map_merge.h; MapMergeDev, ba_device.h) ===========================================================
 // Under the rules above.  Constraint row w belongs to pair w / od: its two map rows are the drop object's (the cut's map_idx) and the keep object's; -1: padding.
-__device__ __forceinline__ void merge_rows(const MapMergeDev& g, int w, int32_t& b, int32_t& k) {
-  b = k = -1;
-  if (w < g.Q) { const int p = w / g.od, c = w % g.od; b = (int32_t)g.cut.map_idx[p] * g.od + c; k = (int32_t)g.keep[p] * g.od + c; }
-}
-// map row of row w of the new map
-__device__ __forceinline__ int32_t merge_kept_row(const MapMergeDev& g, int w) { return w < g.NK ? (int32_t)g.kept[w / g.od] * g.od + w % g.od : -1; }
 
-// (ti, tj <= ti): T_ij = Cs[b_i, b_j] - Cs[b_i, k_j] - Cs[k_i, b_j] + Cs[k_i, k_j] + Rs, in that order, every Cs entry formed as k_map_gather forms it (the two
-// blocks of the map read along their rows, met in LDS).  Into the cut's A (lower tiles, identity padding) and both triangles of Csym; a diagonal tile is taken
-// from its lower triangle, so T is symmetric bit for bit.  Tile column 0 also writes its rows of H mu - d into the cut's mean.
+// (ti, tj <= ti): T_ij = Cs[b_i, b_j] - Cs[b_i, k_j] - Cs[k_i, b_j] + Cs[k_i, k_j] + Rs, in that order, every Cs entry by the symmetrised read.  Into the cut's A
+// (lower tiles, identity padding) and both triangles of Csym; a diagonal tile is taken from its lower triangle, so T is symmetric bit for bit.  Tile column 0
+// also writes its rows of H mu - d into the cut's mean.
 __global__ void __launch_bounds__(kThreads) k_mm_innovation(MapMergeDev g) {
   __shared__ double P[T * LDM];
   __shared__ double Qs[T * LDM];
@@ -634,32 +625,21 @@ __global__ void __launch_bounds__(kThreads) k_mm_innovation(MapMergeDev g) {
   const int ti = blockIdx.x, tj = blockIdx.y, tid = threadIdx.x;
   if (tj > ti) return;
   const MapCutGroup G = g.cut.groups[0];
-  if (tid < 2 * T) {
-    int32_t b, k;
-    merge_rows(g, T * (tid < T ? ti : tj) + (tid & (T - 1)), b, k);
-    (tid < T ? ri : rj)[0][tid & (T - 1)] = b;
-    (tid < T ? ri : rj)[1][tid & (T - 1)] = k;
-  }
+  fill_rows(ri[0], g.cut.map_idx, g.od, g.Q, ti); fill_rows(ri[1], g.keep, g.od, g.Q, ti);
+  fill_rows(rj[0], g.cut.map_idx, g.od, g.Q, tj); fill_rows(rj[1], g.keep, g.od, g.Q, tj);
   __syncthreads();
-  const int64_t ldc = g.N;
   double t[T * T / kThreads];
 #pragma unroll
   for (int x = 0; x < T * T / kThreads; ++x) t[x] = 0.0;
 #pragma unroll 1
   for (int term = 0; term < 4; ++term) {   // (drop, drop) - (drop, keep) - (keep, drop) + (keep, keep)
-    const int32_t* ai = ri[term >> 1];
-    const int32_t* aj = rj[term & 1];
     const double sgn = (term == 1 || term == 2) ? -1.0 : 1.0;
-    for (int e = tid; e < T * T; e += kThreads) {
-      const int r = e >> 6, c = e & 63;
-      P[r * LDM + c] = (ai[r] >= 0 && aj[c] >= 0) ? g.map_cov[(int64_t)ai[r] * ldc + aj[c]] : 0.0;    // C[row i_r][col j_c]
-      Qs[r * LDM + c] = (aj[r] >= 0 && ai[c] >= 0) ? g.map_cov[(int64_t)aj[r] * ldc + ai[c]] : 0.0;   // C[row j_r][col i_c]
-    }
+    stage_sym(P, Qs, g.map_cov, g.N, ri[term >> 1], rj[term & 1]);
     __syncthreads();
 #pragma unroll
     for (int x = 0; x < T * T / kThreads; ++x) {
-      const int e = tid + kThreads * x, r = e >> 6, c = e & 63;
-      t[x] += sgn * (0.5 * (P[r * LDM + c] + Qs[c * LDM + r]));
+      const int e = tid + kThreads * x;
+      t[x] += sgn * sym_at(P, Qs, e >> 6, e & 63);
     }
     __syncthreads();
   }
@@ -700,117 +680,27 @@ __global__ void __launch_bounds__(kThreads) k_mm_gather(MapMergeDev g) {
   __shared__ double Qs[T * LDM];
   __shared__ int32_t rows[T], cols[2][T];
   const int ti = blockIdx.x, tj = blockIdx.y, tid = threadIdx.x;
-  if (tid < T) {
-    rows[tid] = merge_kept_row(g, T * ti + tid);
-    merge_rows(g, T * tj + tid, cols[0][tid], cols[1][tid]);
-  }
+  fill_rows(rows, g.kept, g.od, g.NK, ti);
+  fill_rows(cols[0], g.cut.map_idx, g.od, g.Q, tj); fill_rows(cols[1], g.keep, g.od, g.Q, tj);
   __syncthreads();
-  const int64_t ldc = g.N;
   double t[T * T / kThreads];
 #pragma unroll
   for (int x = 0; x < T * T / kThreads; ++x) t[x] = 0.0;
 #pragma unroll 1
   for (int term = 0; term < 2; ++term) {
-    const int32_t* cc = cols[term];
     const double sgn = term ? -1.0 : 1.0;
-    for (int e = tid; e < T * T; e += kThreads) {
-      const int a = e >> 6, b = e & 63;
-      P[a * LDM + b] = (rows[a] >= 0 && cc[b] >= 0) ? g.map_cov[(int64_t)rows[a] * ldc + cc[b]] : 0.0;    // C[kept row a][col b]
-      Qs[a * LDM + b] = (cc[a] >= 0 && rows[b] >= 0) ? g.map_cov[(int64_t)cc[a] * ldc + rows[b]] : 0.0;   // C[row of col a][kept col b]
-    }
+    stage_sym(P, Qs, g.map_cov, g.N, rows, cols[term]);
     __syncthreads();
 #pragma unroll
     for (int x = 0; x < T * T / kThreads; ++x) {
-      const int e = tid + kThreads * x, r = e >> 6, c = e & 63;
-      t[x] += sgn * (0.5 * (P[r * LDM + c] + Qs[c * LDM + r]));
+      const int e = tid + kThreads * x;
+      t[x] += sgn * sym_at(P, Qs, e >> 6, e & 63);
     }
     __syncthreads();
   }
   double* gt = tile_ptr(g.G, g.nQ, ti, tj);
 #pragma unroll
   for (int x = 0; x < T * T / kThreads; ++x) gt[tid + kThreads * x] = t[x];
-}
-
-// The hot launch.  (ti, tj <= ti): C'_ij = Cs[kept_i, kept_j] - sum_k Y_ik Y_jk^T, k ascending; the old map's two blocks are read through the kept rows, each
-// along its rows; written along the rows of both triangles, a diagonal tile from its lower triangle -- k_mu_cov with Z = Y and a row table.
-__global__ void __launch_bounds__(kThreads) k_mm_cov(MapMergeDev g) {
-  __shared__ double A[T * LDM];
-  __shared__ double B[T * LDM];
-  __shared__ int32_t rows_i[T], rows_j[T];
-  const int ti = blockIdx.x, tj = blockIdx.y, tid = threadIdx.x;
-  if (tj > ti) return;
-  if (tid < 2 * T) (tid < T ? rows_i : rows_j)[tid & (T - 1)] = merge_kept_row(g, T * (tid < T ? ti : tj) + (tid & (T - 1)));
-  f64x4 acc[4] = {};
-  for (int k = 0; k < g.nQ; ++k) {
-    __syncthreads();
-    if (ti != tj) stage_tiles(A, tile_ptr(g.Y, g.nQ, ti, k), B, tile_ptr(g.Y, g.nQ, tj, k));
-    else stage_tile(A, tile_ptr(g.Y, g.nQ, ti, k));
-    __syncthreads();
-    tile_abt_mfma(A, ti != tj ? B : A, acc);
-  }
-  __syncthreads();
-  const int NK = g.NK;
-  const int64_t ldc = g.N, ldo = NK;
-  for (int e = tid; e < T * T; e += kThreads) {   // the old map's two blocks, each along its rows
-    const int a = e >> 6, b = e & 63;
-    A[a * LDM + b] = (rows_i[a] >= 0 && rows_j[b] >= 0) ? g.map_cov[(int64_t)rows_i[a] * ldc + rows_j[b]] : 0.0;
-    B[a * LDM + b] = (rows_j[a] >= 0 && rows_i[b] >= 0) ? g.map_cov[(int64_t)rows_j[a] * ldc + rows_i[b]] : 0.0;
-  }
-  __syncthreads();
-  const int lane = tid & 63, wv = tid >> 6;
-  double v[4][4];
-#pragma unroll
-  for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = 16 * rt + (lane >> 4) + 4 * r, col = 16 * wv + (lane & 15);
-      v[rt][r] = 0.5 * (A[row * LDM + col] + B[col * LDM + row]) - acc[rt][r];
-    }
-  __syncthreads();
-#pragma unroll
-  for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) A[(16 * rt + (lane >> 4) + 4 * r) * LDM + 16 * wv + (lane & 15)] = v[rt][r];
-  __syncthreads();
-  bool bad = false;
-  for (int e = tid; e < T * T; e += kThreads) {
-    const int r = e >> 6, c = e & 63;
-    const int gi = T * ti + r, gj = T * tj + c;
-    if (gi < NK && gj < NK) {
-      const double x = (ti == tj && c > r) ? A[c * LDM + r] : A[r * LDM + c];
-      g.out_cov[(int64_t)gi * ldo + gj] = x;
-      bad = bad || !isfinite(x);
-    }
-    const int hj = T * tj + r, hi = T * ti + c;
-    if (ti != tj && hi < NK && hj < NK) g.out_cov[(int64_t)hj * ldo + hi] = A[c * LDM + r];
-  }
-  if (bad) g.status[MS_NONFINITE] = 1.0;
-}
-
-// v = W (H mu - d): workgroup b its 64 rows, four threads per row, the dot product split by column mod 4 (k_mu_v's sum)
-__global__ void __launch_bounds__(kThreads) k_mm_v(MapMergeDev g) {
-  const int row = T * blockIdx.x + (threadIdx.x >> 2), part = threadIdx.x & 3;
-  double s = 0.0;
-  if (row < g.Q) for (int c = part; c <= row; c += 4) s += g.cut.W[(int64_t)row * g.Q + c] * g.cut.mean[c];
-  s += __shfl_xor(s, 1, 64);
-  s += __shfl_xor(s, 2, 64);
-  if (part == 0) g.v[row] = s;
-}
-// mu'[kept] = mu[kept] - Y v: workgroup b its 64 rows of the new map
-__global__ void __launch_bounds__(kThreads) k_mm_mean(MapMergeDev g) {
-  const int r = threadIdx.x >> 2, part = threadIdx.x & 3, row = T * blockIdx.x + r;
-  double s = 0.0;
-  for (int k = 0; k < g.nQ; ++k) {
-    const double* y = tile_ptr(g.Y, g.nQ, blockIdx.x, k) + r * T;
-    for (int c = part; c < T; c += 4) s += y[c] * g.v[T * k + c];
-  }
-  s += __shfl_xor(s, 1, 64);
-  s += __shfl_xor(s, 2, 64);
-  if (part == 0 && row < g.NK) {
-    const double x = g.map_mean[merge_kept_row(g, row)] - s;
-    g.out_mean[row] = x;
-    if (!isfinite(x)) g.status[MS_NONFINITE] = 1.0;
-  }
 }
 
 // ==== duplicate objects of the map proposed (include/obvi_map_match.h; MapMatchDev, ba_device.h) ==========================================================
@@ -990,37 +880,27 @@ void launch_map_match(hipStream_t s, const MapMatchDev& m) {
   if (m.capacity > 0) hipLaunchKernelGGL(k_mt_scatter, dim3(m.n), dim3(kThreads), 0, s, m);
 }
 
-void launch_map_update(hipStream_t s, const MapUpdateDev& u) {
-  const int nA = u.nA, nN = u.nN;
-  hipLaunchKernelGGL(k_mu_operands, dim3(nA, nA, 2), dim3(kThreads), 0, s, u);
-  hipLaunchKernelGGL(k_mu_gather, dim3(nN, nA), dim3(kThreads), 0, s, u);
-  hipLaunchKernelGGL(k_mu_gemm, dim3(nN, nA), dim3(kThreads), 0, s, MuGemm{u.G, u.Wn, u.Y, nA, nA, 1, 0});    // Y = G W^T
-  hipLaunchKernelGGL(k_mu_gemm, dim3(nA, nA), dim3(kThreads), 0, s, MuGemm{u.Wn, u.Ps, u.U, nA, nA, 2, 0});   // U = W Ps (Ps = Ps^T)
-  hipLaunchKernelGGL(k_mu_gemm, dim3(nA, nA), dim3(kThreads), 0, s, MuGemm{u.U, u.Wn, u.M, nA, nA, 1, 1});    // M = I - U W^T
-  hipLaunchKernelGGL(k_mu_gemm, dim3(nN, nA), dim3(kThreads), 0, s, MuGemm{u.Y, u.M, u.Z, nA, nA, 0, 0});     // Z = Y M (M = M^T)
-  hipLaunchKernelGGL(k_mu_cov, dim3(nN, nN), dim3(kThreads), 0, s, u);
-  hipLaunchKernelGGL(k_mu_v, dim3(nA), dim3(kThreads), 0, s, u);
-  hipLaunchKernelGGL(k_mu_mean, dim3(nN), dim3(kThreads), 0, s, u);
-  hipLaunchKernelGGL(k_mu_scatter, dim3(nA, nA), dim3(kThreads), 0, s, u);
-}
 void launch_map_extend(hipStream_t s, const MapUpdateDev& u) {
   const int nA = u.nA, nN = u.nN, nB = u.nB, nP = (u.NA + u.NB + T - 1) / T;
+  const MapDowndate d{u.Z, u.Y, nA, nullptr, u.od, u.N, u.N, u.ldo, u.map_cov, u.out_cov, u.status};
   if (nA > 0) {
-    hipLaunchKernelGGL(k_mu_operands, dim3(nA, nA, 2), dim3(kThreads), 0, s, u);
+    hipLaunchKernelGGL(k_mu_operands, dim3(nA, nA, 2), dim3(kThreads), 0, s, u.Wt, u.Wn, nA, u.P, (int64_t)u.ldp, u.NA, u.Ps);
     hipLaunchKernelGGL(k_mu_gather, dim3(nN, nA), dim3(kThreads), 0, s, u);
     hipLaunchKernelGGL(k_mu_gemm, dim3(nN, nA), dim3(kThreads), 0, s, MuGemm{u.G, u.Wn, u.Y, nA, nA, 1, 0});    // Y = G W^T
-    hipLaunchKernelGGL(k_mu_gemm, dim3(nA, nA), dim3(kThreads), 0, s, MuGemm{u.Wn, u.Ps, u.U, nA, nA, 2, 0});   // U = W Ps_AA
+    hipLaunchKernelGGL(k_mu_gemm, dim3(nA, nA), dim3(kThreads), 0, s, MuGemm{u.Wn, u.Ps, u.U, nA, nA, 2, 0});   // U = W Ps_AA (Ps = Ps^T)
     hipLaunchKernelGGL(k_mu_gemm, dim3(nA, nA), dim3(kThreads), 0, s, MuGemm{u.U, u.Wn, u.M, nA, nA, 1, 1});    // M = I - U W^T
-    hipLaunchKernelGGL(k_mu_gemm, dim3(nN, nA), dim3(kThreads), 0, s, MuGemm{u.Y, u.M, u.Z, nA, nA, 0, 0});     // Z = Y M
-    hipLaunchKernelGGL(k_mx_stage, dim3(nB, nA), dim3(kThreads), 0, s, u);
-    hipLaunchKernelGGL(k_mu_gemm, dim3(nB, nA), dim3(kThreads), 0, s, MuGemm{u.Pba, u.Wn, u.V, nA, nA, 1, 0});  // V = Ps_BA W^T
-    hipLaunchKernelGGL(k_mu_v, dim3(nA), dim3(kThreads), 0, s, u);
+    hipLaunchKernelGGL(k_mu_gemm, dim3(nN, nA), dim3(kThreads), 0, s, MuGemm{u.Y, u.M, u.Z, nA, nA, 0, 0});     // Z = Y M (M = M^T)
+    if (nB > 0) {
+      hipLaunchKernelGGL(k_mx_stage, dim3(nB, nA), dim3(kThreads), 0, s, u);
+      hipLaunchKernelGGL(k_mu_gemm, dim3(nB, nA), dim3(kThreads), 0, s, MuGemm{u.Pba, u.Wn, u.V, nA, nA, 1, 0});  // V = Ps_BA W^T
+    }
+    hipLaunchKernelGGL(k_map_wd, dim3(nA), dim3(kThreads), 0, s, u.W, u.pm, u.mean_A, u.NA, u.v);                // v = W (m_A - mu_A)
   }
   if (nN > 0) {   // with no window rows in the map both sums are empty: the old block symmetrised, the old means copied
-    hipLaunchKernelGGL(k_mu_cov, dim3(nN, nN), dim3(kThreads), 0, s, u);
-    hipLaunchKernelGGL(k_mu_mean, dim3(nN), dim3(kThreads), 0, s, u);
+    hipLaunchKernelGGL(k_map_downdate, dim3(nN, nN), dim3(kThreads), 0, s, d);
+    hipLaunchKernelGGL(k_map_mean, dim3(nN), dim3(kThreads), 0, s, d, u.v, 1.0, u.map_mean, u.out_mean);
   }
-  if (nA > 0) hipLaunchKernelGGL(k_mx_cross, dim3(nN, nB), dim3(kThreads), 0, s, u);
+  if (nA > 0 && nB > 0) hipLaunchKernelGGL(k_mx_cross, dim3(nN, nB), dim3(kThreads), 0, s, u);
   hipLaunchKernelGGL(k_mx_scatter, dim3(nP, nP), dim3(kThreads), 0, s, u);   // last: the A rows of the cross block give way to Ps_AB
 }
 void launch_map_select(hipStream_t s, const uint32_t* idx, int32_t k, int32_t od, const double* mean, const double* cov, int64_t ldc, double* out_mean, double* out_cov) {
@@ -1070,14 +950,13 @@ void launch_map_merge(hipStream_t s, const MapMergeDev& g, const double* x0) {
   hipLaunchKernelGGL(k_mm_innovation, dim3(nQ, nQ), dim3(kThreads), 0, s, g);
   launch_map_factorize(s, g.cut, nQ);
   launch_map_condition_estimate(s, g.cut, nQ, x0);
-  MapUpdateDev u{};   // k_mu_operands' first plane reads nA, Wt and Wn alone
-  u.nA = nQ; u.Wt = g.cut.Wt; u.Wn = g.Wn;
-  hipLaunchKernelGGL(k_mu_operands, dim3(nQ, nQ, 1), dim3(kThreads), 0, s, u);                                   // Wn = W as tiles
+  hipLaunchKernelGGL(k_mu_operands, dim3(nQ, nQ, 1), dim3(kThreads), 0, s, g.cut.Wt, g.Wn, nQ, nullptr, (int64_t)0, 0, nullptr);   // Wn = W as tiles
   hipLaunchKernelGGL(k_mm_gather, dim3(nK, nQ), dim3(kThreads), 0, s, g);
   hipLaunchKernelGGL(k_mu_gemm, dim3(nK, nQ), dim3(kThreads), 0, s, MuGemm{g.G, g.Wn, g.Y, nQ, nQ, 1, 0});       // Y = G W^T
-  hipLaunchKernelGGL(k_mm_cov, dim3(nK, nK), dim3(kThreads), 0, s, g);
-  hipLaunchKernelGGL(k_mm_v, dim3(nQ), dim3(kThreads), 0, s, g);
-  hipLaunchKernelGGL(k_mm_mean, dim3(nK), dim3(kThreads), 0, s, g);
+  const MapDowndate d{g.Y, g.Y, nQ, g.kept, g.od, g.NK, g.N, g.NK, g.map_cov, g.out_cov, g.cut.status};
+  hipLaunchKernelGGL(k_map_downdate, dim3(nK, nK), dim3(kThreads), 0, s, d);
+  hipLaunchKernelGGL(k_map_wd, dim3(nQ), dim3(kThreads), 0, s, g.cut.W, g.cut.mean, nullptr, g.Q, g.v);          // v = W (H mu - d)
+  hipLaunchKernelGGL(k_map_mean, dim3(nK), dim3(kThreads), 0, s, d, g.v, -1.0, g.map_mean, g.out_mean);
 }
 
 }  // namespace obvi

@@ -1,5 +1,5 @@
 // map_merge.cpp -- include/obvi_map_merge.h: duplicate objects of a device-resident map fused into one (map_kernels.hip).  The host checks every index and
-// every pair, sets up a one-group cut of the constraint rows (map_window.h: the set-up map_update.cpp and map_extend.cpp use; the cut's object list is the drop
+// every pair, sets up a one-group cut of the constraint rows (map_window.h: the set-up fold_window uses; the cut's object list is the drop
 // list), launches into a freshly allocated, smaller map, reads the cut's status record back and hands the new map out only when nothing was refused.
 #include "map_window.h"
 #include "../../include/obvi_map_merge.h"
@@ -40,27 +40,18 @@ int obvi_map_merge(obvi_ba_handle* h, const obvi_map* map, int64_t q, const uint
   const MapCutDev m = window_cut(h, q, drop_idx);
   h->d_mm_keep.upload(keep_idx, (size_t)q, s); h->d_mm_kept.upload(kept, s); h->d_mm_in.upload(in, s);
   h->d_mm_tiles.resize((size_t)((nQ * nQ + 2 * nK * nQ) * tile + kTile * nQ));
-  // the new map
-  std::unique_ptr<obvi_map, MapDeleter> fresh(new obvi_map());
-  fresh->device = map->device; fresh->od = od; fresh->n = n - q;
-  OBVI_HIP(hipMalloc(reinterpret_cast<void**>(&fresh->d_mean), sizeof(double) * NK));
-  OBVI_HIP(hipMalloc(reinterpret_cast<void**>(&fresh->d_cov), sizeof(double) * NK * NK));
-  OBVI_HIP(hipMalloc(reinterpret_cast<void**>(&fresh->d_x0), sizeof(double) * kMapGroupMaxRows));
-  OBVI_HIP(hipMemcpyAsync(fresh->d_x0, map->d_x0, sizeof(double) * kMapGroupMaxRows, hipMemcpyDeviceToDevice, s));
+  std::unique_ptr<obvi_map, MapDeleter> fresh = allocate_map(map->device, od, n - q);
+  inherit_power_start(fresh.get(), map, s);
   MapMergeDev g{};
   g.od = od; g.N = (int32_t)N; g.Q = (int32_t)Q; g.NK = (int32_t)NK; g.nQ = (int32_t)nQ; g.nK = (int32_t)nK;
   g.cut = m; g.keep = h->d_mm_keep.get(); g.kept = h->d_mm_kept.get();
   g.offset = h->d_mm_in.get(); g.noise = noise ? h->d_mm_in.get() + Q : nullptr;
   g.map_mean = map->d_mean; g.map_cov = map->d_cov;
   g.Wn = h->d_mm_tiles.get(); g.G = g.Wn + nQ * nQ * tile; g.Y = g.G + nK * nQ * tile; g.v = g.Y + nK * nQ * tile;
-  g.out_mean = fresh->d_mean; g.out_cov = fresh->d_cov; g.status = m.status;
+  g.out_mean = fresh->d_mean; g.out_cov = fresh->d_cov;
   launch_map_merge(s, g, map->d_x0);
-  OBVI_HIP(hipGetLastError());
-  double st[kMapStatusDoubles];
-  h->d_mc_status.download(st, (size_t)kMapStatusDoubles, s);
-  sync(h);   // the call's one wait: either map may go away from here on, and any stream may read the new one
-  if (!window_cut_spd(st)) return fail(h, OBVI_ERR_NUMERICAL, "map_merge: the covariance of the pairs' differences is not SPD, or numerically singular (a pair that is already merged?)");
-  if (st[MS_NONFINITE] != 0.0) return fail(h, OBVI_ERR_NUMERICAL, "map_merge: a non-finite entry in the new map");
+  { const int rc = finish_window_call(h, true, "map_merge: the covariance of the pairs' differences is not SPD, or numerically singular (a pair that is already merged?)",
+                                      "map_merge: a non-finite entry in the new map"); if (rc != OBVI_OK) return rc; }
   if (new_index) std::copy(where.begin(), where.end(), new_index);
   *out = fresh.release();
   return OBVI_OK;

@@ -17,21 +17,21 @@ int obvi_map_create(int32_t device_id, int32_t object_block_size, int64_t n_obje
   for (int64_t k = 0; k < rows * rows; ++k) if (!std::isfinite(cov[k])) return OBVI_ERR_NUMERICAL;
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device_id < 0 || device_id >= count) return OBVI_ERR_NO_DEVICE;
-  obvi_map* m = new (std::nothrow) obvi_map();
-  if (!m) return OBVI_ERR_HIP;
-  m->device = device_id; m->od = od; m->n = n_objects;
-  const std::vector<double> x0 = map_power_start();
-  const bool ok = hipSetDevice(device_id) == hipSuccess
-               && hipMalloc(reinterpret_cast<void**>(&m->d_mean), sizeof(double) * rows) == hipSuccess
-               && hipMalloc(reinterpret_cast<void**>(&m->d_cov), sizeof(double) * rows * rows) == hipSuccess
-               && hipMalloc(reinterpret_cast<void**>(&m->d_x0), sizeof(double) * x0.size()) == hipSuccess
-               && hipMemcpy(m->d_mean, mean, sizeof(double) * rows, hipMemcpyHostToDevice) == hipSuccess
-               && hipMemcpy(m->d_cov, cov, sizeof(double) * rows * rows, hipMemcpyHostToDevice) == hipSuccess
-               && hipMemcpy(m->d_x0, x0.data(), sizeof(double) * x0.size(), hipMemcpyHostToDevice) == hipSuccess
-               && hipDeviceSynchronize() == hipSuccess;   // the copies have landed: any stream of any thread may read the map from here on
-  if (!ok) { obvi_map_destroy(m); return OBVI_ERR_HIP; }
-  *out = m;
-  return OBVI_OK;
+  try {
+    const std::vector<double> x0 = map_power_start();
+    OBVI_HIP(hipSetDevice(device_id));
+    std::unique_ptr<obvi_map, MapDeleter> m = allocate_map(device_id, od, n_objects);
+    OBVI_HIP(hipMemcpy(m->d_mean, mean, sizeof(double) * rows, hipMemcpyHostToDevice));
+    OBVI_HIP(hipMemcpy(m->d_cov, cov, sizeof(double) * rows * rows, hipMemcpyHostToDevice));
+    OBVI_HIP(hipMemcpy(m->d_x0, x0.data(), sizeof(double) * x0.size(), hipMemcpyHostToDevice));
+    OBVI_HIP(hipDeviceSynchronize());   // the copies have landed: any stream of any thread may read the map from here on
+    *out = m.release();
+    return OBVI_OK;
+  } catch (const HipError&) {   // no handle to keep the words: the code alone, and whatever was allocated is freed
+    return OBVI_ERR_HIP;
+  } catch (const std::bad_alloc&) {
+    return OBVI_ERR_HIP;
+  }
 }
 
 void obvi_map_destroy(obvi_map* map) {
@@ -113,11 +113,8 @@ int obvi_map_set_group_priors_from_map(obvi_ba_handle* h, const obvi_map* map, i
   std::vector<double> status((size_t)n * kMapStatusDoubles);
   h->d_mc_status.download(status.data(), status.size(), s);
   sync(h);   // the call's one wait: the map may go away from here on
-  for (int64_t g = 0; g < n; ++g) {
-    const double* st = &status[(size_t)g * kMapStatusDoubles];
-    const bool spd = st[MS_BAD] == 0.0 && st[MS_PIV_MIN] * st[MS_PIV_MIN] > 1e-13 * st[MS_PIV_MAX] * st[MS_PIV_MAX] && st[MS_EV_C] * st[MS_EV_LAMBDA] <= 1e13;
-    if (!spd) return fail(h, OBVI_ERR_NUMERICAL, "map_set_group_priors_from_map: covariance not SPD, or numerically singular");
-  }
+  for (int64_t g = 0; g < n; ++g)
+    if (!window_cut_spd(&status[(size_t)g * kMapStatusDoubles])) return fail(h, OBVI_ERR_NUMERICAL, "map_set_group_priors_from_map: covariance not SPD, or numerically singular");
   // accepted: the call's buffers become the handle's
   h->d_mg_ptr.swap(h->d_mgn_ptr); h->d_mg_obj.swap(h->d_mgn_obj); h->d_mg_active.swap(h->d_mgn_active); h->d_mg_mean.swap(h->d_mgn_mean);
   h->d_mg_lam_off.swap(h->d_mgn_lam_off); h->d_mg_w_off.swap(h->d_mgn_w_off); h->d_mg_Lambda.swap(h->d_mgn_Lambda); h->d_mg_W.swap(h->d_mgn_W);

@@ -1,6 +1,7 @@
-// map_window.h -- what the entries that bring a window back into a device-resident map share (map_update.cpp: the map conditioned; map_extend.cpp: the map
-// grown or gathered): the checks of the window's map objects, the one-group cut of those objects in the handle's scratch buffers, the device view of the update,
-// the test of the cut's status record, and the start vector a map is given at birth (map_resident.cpp).
+// map_window.h -- what the entries that make a device-resident map share (map_resident.cpp: the map created; map_update.cpp: conditioned; map_extend.cpp: grown
+// or gathered; map_merge.cpp: its duplicates merged): the checks of the window's map objects, the one-group cut of those objects in the handle's scratch
+// buffers, the device view of the update, allocate_map, the end of a call on the cut's status record (finish_window_call), the posterior's way to the device
+// (upload_posterior, posterior_from_handle), fold_window -- the one routine that brings a window back into a map -- and the start vector a map is given at birth.
 #ifndef OBVI_MAP_WINDOW_H_
 #define OBVI_MAP_WINDOW_H_
 #include "ba_handle.h"
@@ -118,6 +119,72 @@ inline MapUpdateDev window_update(obvi_ba_handle* h, const obvi_map* map, int64_
 // the cut's pivot and condition tests on its status record: those of obvi_map_set_group_priors_from_map
 inline bool window_cut_spd(const double* st) {
   return st[MS_BAD] == 0.0 && st[MS_PIV_MIN] * st[MS_PIV_MIN] > 1e-13 * st[MS_PIV_MAX] * st[MS_PIV_MAX] && st[MS_EV_C] * st[MS_EV_LAMBDA] <= 1e13;
+}
+
+// A map of n objects with its three buffers allocated and nothing in them: the one place a map is made.  Throws HipError; the device is the current one.
+inline std::unique_ptr<obvi_map, MapDeleter> allocate_map(int device, int od, int64_t n) {
+  std::unique_ptr<obvi_map, MapDeleter> fresh(new obvi_map());
+  fresh->device = device; fresh->od = od; fresh->n = n;
+  const int64_t rows = n * od;
+  OBVI_HIP(hipMalloc(reinterpret_cast<void**>(&fresh->d_mean), sizeof(double) * rows));
+  OBVI_HIP(hipMalloc(reinterpret_cast<void**>(&fresh->d_cov), sizeof(double) * rows * rows));
+  OBVI_HIP(hipMalloc(reinterpret_cast<void**>(&fresh->d_x0), sizeof(double) * kMapGroupMaxRows));
+  return fresh;
+}
+// ... and the start vector of the map it comes from, on the stream
+inline void inherit_power_start(obvi_map* fresh, const obvi_map* from, hipStream_t s) {
+  OBVI_HIP(hipMemcpyAsync(fresh->d_x0, from->d_x0, sizeof(double) * kMapGroupMaxRows, hipMemcpyDeviceToDevice, s));
+}
+
+// The end of a call that launched on a window's cut: the cut's status record read back behind the call's one wait -- either map may go away from here on, and
+// any stream may read the new one -- then the cut's tests (factored: a cut was factored) and the flag of a non-finite entry, each refused in the entry's words.
+inline int finish_window_call(obvi_ba_handle* h, bool factored, const std::string& not_spd, const std::string& non_finite) {
+  OBVI_HIP(hipGetLastError());
+  double st[kMapStatusDoubles];
+  h->d_mc_status.download(st, (size_t)kMapStatusDoubles, h->stream);
+  sync(h);
+  if (factored && !window_cut_spd(st)) return fail(h, OBVI_ERR_NUMERICAL, not_spd);
+  if (st[MS_NONFINITE] != 0.0) return fail(h, OBVI_ERR_NUMERICAL, non_finite);
+  return OBVI_OK;
+}
+
+// The posterior of the host-pointer forms, NP rows: refused unless every entry is finite, then copied into d_mu_post (covariance [NP][NP], then mean [NP]) on
+// the handle's stream.
+inline int upload_posterior(obvi_ba_handle* h, int64_t NP, const double* post_mean, const double* post_cov, const std::string& what) {
+  for (int64_t i = 0; i < NP; ++i) if (!std::isfinite(post_mean[i])) return fail(h, OBVI_ERR_NUMERICAL, what + ": a posterior mean that is not finite");
+  for (int64_t i = 0; i < NP * NP; ++i) if (!std::isfinite(post_cov[i])) return fail(h, OBVI_ERR_NUMERICAL, what + ": a posterior covariance entry that is not finite");
+  OBVI_HIP(hipSetDevice(h->device));
+  h->d_mu_post.resize((size_t)(NP * NP + NP));
+  h2d_async(h->d_mu_post.get(), post_cov, sizeof(double) * (size_t)(NP * NP), h->stream);
+  h2d_async(h->d_mu_post.get() + NP * NP, post_mean, sizeof(double) * (size_t)NP, h->stream);
+  return OBVI_OK;
+}
+
+// One window brought back into a map -- the routine behind the condition and the extend entries -- with the posterior over (A, B) in d_mu_post (covariance
+// [N_A + N_B]^2, then mean) on the handle's stream: A the window's k_old objects of `map`, cut from it as one group and factored; B its k_new objects the map
+// lacks, appended.  k_new = 0 conditions the map; map NULL (k_old = 0): a first map, the posterior itself.  Launches into a freshly allocated map, reads the
+// cut's status record back and hands the new map out only when nothing was refused.  One wait.
+inline int fold_window(obvi_ba_handle* h, const obvi_map* map, int64_t k_old, const uint32_t* map_idx, int64_t k_new, const std::string& what, obvi_map** out) {
+  const int od = h->od;
+  const int64_t n = map ? map->n : 0, N = n * od, NA = k_old * od, NB = k_new * od, nA = map_group_slabs(NA);
+  hipStream_t s = h->stream;
+  const MapCutDev m = window_cut(h, k_old, map_idx);
+  std::unique_ptr<obvi_map, MapDeleter> fresh = allocate_map(h->device, od, n + k_new);
+  const std::vector<double> x0 = map ? std::vector<double>() : map_power_start();   // alive until the wait
+  if (map) inherit_power_start(fresh.get(), map, s);
+  else h2d_async(fresh->d_x0, x0.data(), sizeof(double) * x0.size(), s);
+  const MapUpdateDev u = window_update(h, map, k_old, k_new, m, fresh.get());
+  if (k_old > 0) {   // the condition test reads the largest eigenvalue of Lambda = Cs_AA^-1, so the cut runs whole: factor, then Lambda and the power steps
+    launch_map_factor(s, m, (int)nA, map->d_mean, map->d_cov, N);
+    launch_map_condition_estimate(s, m, (int)nA, map->d_x0);
+  } else if (N > 0) {
+    OBVI_HIP(hipMemsetAsync(fresh->d_cov, 0, sizeof(double) * (size_t)((N + NB) * (N + NB)), s));   // no product fills the cross blocks: they are zero
+  }
+  launch_map_extend(s, u);
+  { const int rc = finish_window_call(h, k_old > 0, what + ": the map's covariance of the window's objects is not SPD, or numerically singular",
+                                      what + ": a non-finite entry in the posterior or in the new map"); if (rc != OBVI_OK) return rc; }
+  *out = fresh.release();
+  return OBVI_OK;
 }
 
 }  // namespace obvi_lib
