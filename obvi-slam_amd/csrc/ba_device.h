@@ -281,6 +281,23 @@ struct MapMatchDev {
 };
 // five launches: diagonal blocks, pairs, row counts, the scan of the rows (one workgroup), the scatter.  n >= 1.
 void launch_map_match(hipStream_t s, const MapMatchDev& m);
+// A map moved into another frame under an uncertain transform (include/obvi_map_frame.h; map_kernels.hip): x'_o = g(T, x_o) object by object,
+// C' = Jt Cs Jt^T + G Sigma_s G^T with Jt = blockdiag(J_o), J_o = blockdiag(Jk_o, I3), and G the stacked G_o, whose last three rows are zero.  K = od - 3 rows
+// of a block move (centre and rotation), dT = 4 (od 7: tx ty tz psi) or 6 (od 9: translation, axis-angle) parameters has the transform.
+constexpr int kFrameMaxDT = 6;
+struct MapFrameDev {
+  int32_t od, n, has_sigma;                                  // has_sigma 0: the transform is exact, G and GS are never read
+  double transform[kFrameMaxDT];                             // [dT]
+  double sigma[kFrameMaxDT * kFrameMaxDT];                   // [dT][dT] Sigma_s, symmetrised by the host
+  const double* map_mean; const double* map_cov;             // the old map: [n od], [n od][n od]
+  double* J; double* G; double* GS;                          // [n][K][K] Jk_o, [n][K][dT] the moving rows of G_o, [n][K][dT] G_o Sigma_s
+  double* out_mean; double* out_cov;                         // the new map
+  double* status;                                            // MS_NONFINITE is set to 1 by whoever writes a non-finite entry of the new map; zeroed on the stream before
+};
+// two launches: the objects (means, Jk, G, GS: one lane each), then the covariance over object-aligned block pairs.  n >= 1.
+void launch_map_transform(hipStream_t s, const MapFrameDev& f);
+// out = (mean_a, mean_b), blockdiag(cov_a, cov_b), copied entry by entry: one launch.  The two maps may be the same one.
+void launch_map_join(hipStream_t s, int64_t rows_a, const double* mean_a, const double* cov_a, int64_t rows_b, const double* mean_b, const double* cov_b, double* out_mean, double* out_cov);
 // the posterior of the handle form: the k x k blocks of launch_cov_pairs (pair a k + b: objects a, b) -> dense P, and the objects' current values -> pm
 void launch_map_posterior_layout(hipStream_t s, const double* blocks, const double* objects, const uint32_t* obj_idx, int32_t k, int32_t od, double* P, double* pm);
 

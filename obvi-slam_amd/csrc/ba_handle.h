@@ -8,6 +8,7 @@
 //   map_resident.cpp, map_update.cpp, map_extend.cpp   the device-resident map (struct obvi_map): group priors cut from it, the map conditioned on a window's
 //                      posterior, and the map grown by a window's new objects or gathered (what the last two share: map_window.h)
 //   map_merge.cpp, map_match.cpp   duplicate objects of the map fused, and proposed (with the host-only resolver between the two)
+//   map_frame.cpp  the map moved into another frame under an uncertain transform; two maps joined
 #ifndef OBVI_BA_HANDLE_H_
 #define OBVI_BA_HANDLE_H_
 #include "../../include/obvi_ba.h"
@@ -200,6 +201,8 @@ struct obvi_ba_handle {
   DevBuf<uint32_t> d_mm_keep, d_mm_kept; DevBuf<double> d_mm_in, d_mm_tiles;
   // obvi_map_match (map_match.cpp): the labels, the compacted diagonal blocks, the [n][n] statistics, the rows' counts, offsets and the totals, the reported pairs (a, then b; stat, then yaw offset); empty until the first call
   DevBuf<int32_t> d_mt_label; DevBuf<double> d_mt_diag, d_mt_stat, d_mt_out; DevBuf<int64_t> d_mt_cnt; DevBuf<uint32_t> d_mt_idx;
+  // obvi_map_transform (map_frame.cpp): the objects' Jk, G and G Sigma_s of MapFrameDev, one after the other; empty until the first call
+  DevBuf<double> d_mf_jac;
   DevBuf<double> d_bb_blk;                                    // per-factor blocks of the bounding-box factors (k_bbox_gather)
   DevBuf<double> d_sm_blk; DevBuf<uint32_t> d_smt_ptr, d_smt_idx;   // deterministic mode: the same for the priors and relative-pose factors (k_small_gather)
   int32_t bb_pairs_unique = 1;

@@ -16,6 +16,8 @@
 // entry of a map or a posterior goes through stage_sym / sym_at.  Last part: duplicate objects of the map proposed
 // (include/obvi_map_match.h): every pair's difference in units of its own covariance, one lane per pair, and the pairs within the gate compacted in (a, b) order
 // by counts and a scan.
+// After it: the map moved into another frame under an uncertain transform, object-aligned block pair by block pair, and two maps joined
+// (include/obvi_map_frame.h).
 #include "chol_tile.h"
 
 namespace obvi {
@@ -868,7 +870,215 @@ __global__ void __launch_bounds__(kThreads) k_mt_scatter(MapMatchDev m) {
   }
 }
 
+// ==== the map moved into another frame under an uncertain transform; two maps joined (include/obvi_map_frame.h; MapFrameDev, ba_device.h) ==================
+// Under the rules above: no atomics, no flags between workgroups, every sum in a fixed order.
+
+// The unit quaternion (x y z w) of an axis-angle vector, smooth through zero: (aa sin(th / 2) / th, cos(th / 2)), by series in th^2 below th = 1e-3 (the next
+// terms are under 1e-22).  The estimator's own rotation (dual_forward_rotation) is a constant at and below 1e-8, which is right for a residual and wrong for
+// the derivative a covariance is pushed through.
+template <int N> __device__ __forceinline__ void frame_quat(const Dual<N>* aa, Dual<N>* q) {
+  typedef Dual<N> D;
+  const D t2 = aa[0] * aa[0] + aa[1] * aa[1] + aa[2] * aa[2];
+  D k, w;
+  if (t2.v > 1e-6) {
+    const D t = dsqrt(t2), half = t * 0.5;
+    k = dsin(half) / t; w = dcos(half);
+  } else {
+    k = D(0.5) - t2 * (1.0 / 48.0) + t2 * t2 * (1.0 / 3840.0);
+    w = D(1.0) - t2 * (1.0 / 8.0) + t2 * t2 * (1.0 / 384.0);
+  }
+  q[0] = k * aa[0]; q[1] = k * aa[1]; q[2] = k * aa[2]; q[3] = w;
+}
+// The rotation log of a unit quaternion, angle in [0, pi] -- the convention of relpose_eval_n (ba_math.h): 2 atan2(|v|, |w|) v / |v|, negated where w < 0 --
+// and smooth through the identity: below |v| = 1e-3 |w| the series of atan in (|v| / w)^2.
+template <int N> __device__ __forceinline__ void frame_quat_log(const Dual<N>* q, Dual<N>* aa) {
+  typedef Dual<N> D;
+  const D n2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2], w = dabs(q[3]);
+  D scale;
+  if (n2.v > 1e-6 * w.v * w.v) {
+    const D n = dsqrt(n2);
+    scale = datan2(n, w) * 2.0 / n;
+  } else {
+    const D x2 = n2 / (w * w);
+    scale = (D(2.0) / w) * (D(1.0) - x2 * (1.0 / 3.0) + x2 * x2 * (1.0 / 5.0) - x2 * x2 * x2 * (1.0 / 7.0));
+  }
+  if (q[3].v < 0.0) scale = -scale;
+  for (int i = 0; i < 3; ++i) aa[i] = scale * q[i];
+}
+
+// One lane per object: mu'_o, Jk_o (the K x K block of J_o that is not the identity), the K moving rows of G_o, and GS_o = G_o Sigma_s (sums over the
+// transform's parameters in their order).  A non-finite mean sets the flag of the status record.
+template <int OD>
+__global__ void __launch_bounds__(64) k_mf_jac(MapFrameDev f) {
+  constexpr int K = OD - 3, DT = OD == 7 ? 4 : 6;
+  const int o = blockIdx.x * 64 + threadIdx.x;
+  if (o >= f.n) return;
+  const double* m = f.map_mean + (int64_t)o * OD;
+  double mu[OD], J[K * K], G[K * DT];
+  for (int i = 0; i < K * K; ++i) J[i] = 0.0;
+  for (int i = 0; i < K * DT; ++i) G[i] = 0.0;
+  for (int i = 0; i < 3; ++i) { mu[OD - 3 + i] = m[OD - 3 + i]; G[i * DT + i] = 1.0; }
+  if (OD == 7) {   // p' = Rz(psi) p + t, yaw' = yaw + psi
+    const double psi = f.transform[3], c = cos(psi), s = sin(psi), x = m[0], y = m[1];
+    mu[0] = c * x - s * y + f.transform[0]; mu[1] = s * x + c * y + f.transform[1]; mu[2] = m[2] + f.transform[2]; mu[3] = m[3] + psi;
+    J[0] = c; J[1] = -s; J[K] = s; J[K + 1] = c; J[2 * K + 2] = 1.0; J[3 * K + 3] = 1.0;
+    G[3] = -s * x - c * y; G[DT + 3] = c * x - s * y; G[3 * DT + 3] = 1.0;   // Rz'(psi) p in the centre rows, the yaw row
+  } else {         // p' = R_T p + t, aa' = Log(R_T Exp(aa)); directions 0..2: the transform's axis-angle, 3..5: the object's
+    typedef Dual<6> D;
+    D a[3], aa[3], qt[4], qo[4], q[4], lg[3];
+    for (int i = 0; i < 3; ++i) { a[i] = dvar<6>(f.transform[3 + i], i); aa[i] = dvar<6>(m[3 + i], 3 + i); }
+    frame_quat(a, qt); frame_quat(aa, qo);
+    q[3] = qt[3] * qo[3] - (qt[0] * qo[0] + qt[1] * qo[1] + qt[2] * qo[2]);
+    q[0] = qt[3] * qo[0] + qo[3] * qt[0] + (qt[1] * qo[2] - qt[2] * qo[1]);
+    q[1] = qt[3] * qo[1] + qo[3] * qt[1] + (qt[2] * qo[0] - qt[0] * qo[2]);
+    q[2] = qt[3] * qo[2] + qo[3] * qt[2] + (qt[0] * qo[1] - qt[1] * qo[0]);
+    frame_quat_log(q, lg);
+    const D x = qt[0], y = qt[1], z = qt[2], w = qt[3];
+    const D R[9] = {D(1.0) - (y * y + z * z) * 2.0, (x * y - z * w) * 2.0, (x * z + y * w) * 2.0,
+                    (x * y + z * w) * 2.0, D(1.0) - (x * x + z * z) * 2.0, (y * z - x * w) * 2.0,
+                    (x * z - y * w) * 2.0, (y * z + x * w) * 2.0, D(1.0) - (x * x + y * y) * 2.0};
+    for (int i = 0; i < 3; ++i) {
+      const D p = R[3 * i] * m[0] + R[3 * i + 1] * m[1] + R[3 * i + 2] * m[2];
+      mu[i] = p.v + f.transform[i]; mu[3 + i] = lg[i].v;
+      for (int j = 0; j < 3; ++j) {
+        J[i * K + j] = R[3 * i + j].v; J[(3 + i) * K + 3 + j] = lg[i].d[3 + j];
+        G[i * DT + 3 + j] = p.d[j]; G[(3 + i) * DT + 3 + j] = lg[i].d[j];
+      }
+    }
+  }
+  bool bad = false;
+  for (int i = 0; i < OD; ++i) { f.out_mean[(int64_t)o * OD + i] = mu[i]; bad = bad || !isfinite(mu[i]); }
+  for (int i = 0; i < K * K; ++i) f.J[(int64_t)o * K * K + i] = J[i];
+  if (f.has_sigma) {
+    for (int r = 0; r < K; ++r)
+      for (int t = 0; t < DT; ++t) {
+        double acc = 0.0;
+        for (int u = 0; u < DT; ++u) acc += G[r * DT + u] * f.sigma[u * DT + t];
+        f.G[((int64_t)o * K + r) * DT + t] = G[r * DT + t];
+        f.GS[((int64_t)o * K + r) * DT + t] = acc;
+      }
+  }
+  if (bad) f.status[MS_NONFINITE] = 1.0;
+}
+
+// Workgroup (bi, bj >= bi): the block pairs (a, b) of B = 64 / OD objects a of block bi and B objects b of block bj -- the object-aligned blocking of
+// k_mt_pairs, 63 rows for both block sizes -- with both orientations of the cross block staged by stage_sym and met in P: P = Cs[rows a][columns b].  Thread
+// (r, c) forms entry (r, c) of  J_a Cs_ab J_b^T + GS_a G_b^T  with J = blockdiag(Jk, I3): the inner sum over the columns of b first, then the sum over the rows
+// of a, then the transform's term summed over its parameters in their order and added last; an entry whose row and column are both dimensions is Cs itself.
+// The result meets in Q and leaves along the rows of both triangles, a diagonal block from its lower triangle: C' is symmetric bit for bit.  C is read once,
+// C' written once.
+template <int OD>
+__global__ void __launch_bounds__(kThreads) k_mf_cov(MapFrameDev f) {
+  constexpr int B = T / OD, R = B * OD, K = OD - 3, DT = OD == 7 ? 4 : 6, X = T * T / kThreads;
+  __shared__ double P[T * LDM];
+  __shared__ double Q[T * LDM];
+  __shared__ double Ja[B * K * K], Jb[B * K * K], GSa[B * K * DT], Gb[B * K * DT];
+  __shared__ int32_t rows_a[T], rows_b[T];
+  const int bi = blockIdx.x, bj = blockIdx.y, tid = threadIdx.x;
+  if (bj < bi) return;
+  const int n = f.n;
+  const int na = min(B, n - bi * B), nb = min(B, n - bj * B), ra = na * OD, rb = nb * OD;
+  const int64_t ldc = (int64_t)n * OD, row_a = (int64_t)bi * R, row_b = (int64_t)bj * R;
+  if (tid < T) { rows_a[tid] = tid < ra ? (int32_t)row_a + tid : -1; rows_b[tid] = tid < rb ? (int32_t)row_b + tid : -1; }
+  for (int e = tid; e < B * K * K; e += kThreads) {
+    Ja[e] = e < na * K * K ? f.J[(int64_t)bi * B * K * K + e] : 0.0;
+    Jb[e] = e < nb * K * K ? f.J[(int64_t)bj * B * K * K + e] : 0.0;
+  }
+  if (f.has_sigma) {
+    for (int e = tid; e < B * K * DT; e += kThreads) {
+      GSa[e] = e < na * K * DT ? f.GS[(int64_t)bi * B * K * DT + e] : 0.0;
+      Gb[e] = e < nb * K * DT ? f.G[(int64_t)bj * B * K * DT + e] : 0.0;
+    }
+  }
+  __syncthreads();
+  stage_sym(P, Q, f.map_cov, ldc, rows_a, rows_b);
+  __syncthreads();
+#pragma unroll
+  for (int x = 0; x < X; ++x) {   // each thread symmetrises its own entries of P; Q is only read
+    const int e = tid + kThreads * x, r = e >> 6, c = e & 63;
+    P[r * LDM + c] = sym_at(P, Q, r, c);
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (int x = 0; x < X; ++x) {
+    const int e = tid + kThreads * x, r = e >> 6, c = e & 63;
+    double v = 0.0;
+    if (r < ra && c < rb) {
+      const int al = r / OD, ri = r - al * OD, bl = c / OD, ci = c - bl * OD;
+      const double* Sab = P + (al * OD) * LDM + bl * OD;   // Cs of the object pair (al, bl)
+      const double* ja = Ja + (al * K + ri) * K;
+      const double* jb = Jb + (bl * K + ci) * K;
+      if (ri >= K && ci >= K) {
+        v = P[r * LDM + c];
+      } else if (ri >= K) {
+#pragma unroll
+        for (int l = 0; l < K; ++l) v += P[r * LDM + bl * OD + l] * jb[l];
+      } else if (ci >= K) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) v += ja[k] * P[(al * OD + k) * LDM + c];
+      } else {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+          double w = 0.0;
+#pragma unroll
+          for (int l = 0; l < K; ++l) w += Sab[k * LDM + l] * jb[l];
+          v += ja[k] * w;
+        }
+        if (f.has_sigma) {
+          double g = 0.0;
+#pragma unroll
+          for (int t = 0; t < DT; ++t) g += GSa[(al * K + ri) * DT + t] * Gb[(bl * K + ci) * DT + t];
+          v += g;
+        }
+      }
+    }
+    Q[r * LDM + c] = v;
+  }
+  __syncthreads();
+  bool bad = false;
+  for (int e = tid; e < T * T; e += kThreads) {
+    const int r = e >> 6, c = e & 63;
+    if (r < ra && c < rb) {
+      const double x = (bi == bj && c > r) ? Q[c * LDM + r] : Q[r * LDM + c];
+      f.out_cov[(row_a + r) * ldc + row_b + c] = x;
+      bad = bad || !isfinite(x);
+    }
+    if (bi != bj && r < rb && c < ra) f.out_cov[(row_b + r) * ldc + row_a + c] = Q[c * LDM + r];
+  }
+  if (bad) f.status[MS_NONFINITE] = 1.0;
+}
+
+// Row blockIdx.y, 256 columns of it: the entry of blockdiag(A, B), copied as the device holds it; row 0's workgroups also copy the means
+__global__ void __launch_bounds__(kThreads) k_mf_join(int64_t na, const double* __restrict__ mean_a, const double* __restrict__ cov_a, int64_t nb, const double* __restrict__ mean_b,
+                                                      const double* __restrict__ cov_b, double* __restrict__ out_mean, double* __restrict__ out_cov) {
+  const int64_t n = na + nb, j = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (j >= n) return;
+  for (int64_t i = blockIdx.y; i < n; i += gridDim.y) {
+    double v = 0.0;
+    if (i < na && j < na) v = cov_a[i * na + j];
+    else if (i >= na && j >= na) v = cov_b[(i - na) * nb + (j - na)];
+    out_cov[i * n + j] = v;
+  }
+  if (blockIdx.y == 0) out_mean[j] = j < na ? mean_a[j] : mean_b[j - na];
+}
+
 }  // namespace
+
+void launch_map_transform(hipStream_t s, const MapFrameDev& f) {
+  const int B = T / f.od, nb = (f.n + B - 1) / B;
+  if (f.od == 7) {
+    hipLaunchKernelGGL(k_mf_jac<7>, dim3((f.n + 63) / 64), dim3(64), 0, s, f);
+    hipLaunchKernelGGL(k_mf_cov<7>, dim3(nb, nb), dim3(kThreads), 0, s, f);
+  } else {
+    hipLaunchKernelGGL(k_mf_jac<9>, dim3((f.n + 63) / 64), dim3(64), 0, s, f);
+    hipLaunchKernelGGL(k_mf_cov<9>, dim3(nb, nb), dim3(kThreads), 0, s, f);
+  }
+}
+void launch_map_join(hipStream_t s, int64_t rows_a, const double* mean_a, const double* cov_a, int64_t rows_b, const double* mean_b, const double* cov_b, double* out_mean, double* out_cov) {
+  const int64_t n = rows_a + rows_b;
+  hipLaunchKernelGGL(k_mf_join, dim3((unsigned)((n + kThreads - 1) / kThreads), (unsigned)std::min<int64_t>(n, 65535)), dim3(kThreads), 0, s, rows_a, mean_a, cov_a, rows_b, mean_b, cov_b,
+                     out_mean, out_cov);
+}
 
 void launch_map_match(hipStream_t s, const MapMatchDev& m) {
   const int B = T / m.od, nb = (m.n + B - 1) / B;

@@ -288,6 +288,31 @@ class Map:
         k = min(capacity, int(counts[0]))
         return a[:k], b[:k], s[:k], w[:k], tuple(int(c) for c in counts)
 
+    # ---- another frame, and two maps in one (include/obvi_map_frame.h) ----
+    def _frame_fn(self, name):
+        try:
+            f = getattr(self._lib, self._pre + name)
+        except AttributeError:
+            raise ObviError("%s%s: this library cannot move or join maps (include/obvi_map_frame.h is served by libobvi_ba.so only)" % (self._pre, name))
+        f.restype = C.c_int
+        return f
+
+    def transform(self, ba, transform, cov=None):
+        """A new Map: this one moved into another frame by T_new<-old = transform ([4] tx ty tz psi for od 7, [6] translation and axis-angle for od 9), whose
+        covariance is cov ([dT][dT]; None: the transform is exact).  Same objects, same numbers."""
+        dT = 4 if self.od == 7 else 6
+        t = _f64(transform, (dT,))
+        s = None if cov is None else _f64(cov, (dT, dT))
+        new = C.c_void_p()
+        rc = self._frame_fn("map_transform")(ba._h, self._m, _ptr(t, C.c_double), _ptr(s, C.c_double), C.byref(new))
+        return self._conditioned(ba, rc, new, "map_transform")
+
+    def join(self, ba, other):
+        """A new Map of this one's objects followed by `other`'s, the two uncorrelated: blockdiag of the covariances, copied as the device holds them."""
+        new = C.c_void_p()
+        rc = self._frame_fn("map_join")(ba._h, self._m, other._m, C.byref(new))
+        return self._conditioned(ba, rc, new, "map_join")
+
     def close(self):
         if self._m:
             f = getattr(self._lib, self._pre + "map_destroy")

@@ -14,7 +14,10 @@ the same call on ONE handle that holds the joint problem.
 round trip that merges without it: obvi_map_get, the same formula in numpy, obvi_map_create.
 --match: which objects are duplicates -- obvi_map_match over all 19 900 pairs of the 200-object map (whole block, no labels), both waits
 included, against the only route without it: obvi_map_get and the same statistic vectorised in numpy; nothing is uploaded again on either side.
-usage (GPU box, repo root): python scripts/map_bench.py [--update | --extend | --merge | --match | --shared K]"""
+--move: another frame -- obvi_map_transform of the 200-object map without and with a transform covariance, wait included, against the round
+trip that moves it without the entry: obvi_map_get, the same formula in numpy, obvi_map_create; obvi_map_join of two 200-object maps; and the move of a
+800-object map (5 600 rows, 251 MB), where the covariance kernel is most of the call, beside the copy bandwidth obvi_ba_measure_peaks reports.
+usage (GPU box, repo root): python scripts/map_bench.py [--update | --extend | --merge | --match | --move | --shared K]"""
 import os
 import sys
 import time
@@ -317,6 +320,76 @@ def match():
     mp.close()
 
 
+def numpy_move(mean, cov, T, Sigma):
+    """The formulas of include/obvi_map_frame.h on the host (od 7)."""
+    n = len(mean)
+    c, s = np.cos(T[3]), np.sin(T[3])
+    J = np.eye(OD)
+    J[:2, :2] = [[c, -s], [s, c]]
+    mu = mean @ J.T
+    mu[:, :3] += T[:3]
+    mu[:, 3] += T[3]
+    Cn = np.einsum("ik,akbl,jl->aibj", J, (0.5 * (cov + cov.T)).reshape(n, OD, n, OD), J).reshape(n * OD, n * OD)
+    if Sigma is not None:
+        G = np.zeros((n, OD, 4))
+        G[:, :3, :3], G[:, 3, 3] = np.eye(3), 1.0
+        G[:, 0, 3], G[:, 1, 3] = -s * mean[:, 0] - c * mean[:, 1], c * mean[:, 0] - s * mean[:, 1]
+        G = G.reshape(n * OD, 4)
+        Cn += G @ (0.5 * (Sigma + Sigma.T)) @ G.T
+    return mu, 0.5 * (Cn + Cn.T)
+
+
+def move():
+    """the map moved into another frame, and two maps joined.  The device entries against the round trip a session needs without them."""
+    rng = np.random.default_rng(1)
+    mean, cov = rng.normal(size=(N_MAP, OD)), spd(rng, N_MAP * OD)
+    mp = obvi_ba.Map.create(mean, cov, object_block_size=OD)
+    ba = obvi_ba.BundleAdjuster(object_block_size=OD)
+    ba.set_cameras(synth.K_DEFAULT[None], synth.EXT_DEFAULT[None])
+    ba.set_poses(np.zeros((1, 6)), np.ones(1, np.uint8))
+    ba.set_points(np.zeros((0, 3)), np.zeros(0, np.uint8))
+    ba.set_objects(np.zeros((1, OD)), np.zeros(1, np.uint8))
+    T = np.array([3.0, -2.0, 0.5, 0.7])
+    A = rng.normal(size=(4, 4))
+    for Sigma in (None, 1e-2 * (A @ A.T + 4 * np.eye(4))):
+        last = {}
+
+        def round_trip():
+            old_mean, old_cov = mp.get()
+            mu, Cn = numpy_move(old_mean, old_cov, T, Sigma)
+            with obvi_ba.Map.create(mu, Cn, object_block_size=OD) as new:
+                last["host"] = (mu, Cn, new.n_objects)
+
+        def device():
+            with mp.transform(ba, T, Sigma) as new:
+                last["n"] = new.n_objects
+        base, b = timed(round_trip)
+        dev, d = timed(device)
+        with mp.transform(ba, T, Sigma) as new:
+            mu, Cn = new.get()
+        print("%d objects (%d rows), %s: round trip %s   obvi_map_transform %s  (x %.1f)   |C' - numpy's| / |C'| %.1e"
+              % (N_MAP, N_MAP * OD, "exact transform" if Sigma is None else "with Sigma", base, dev, b / d, np.abs(Cn - last["host"][1]).max() / np.abs(Cn).max()))
+
+    def join():
+        with mp.join(ba, mp) as new:
+            assert new.n_objects == 2 * N_MAP
+    print("obvi_map_join of two %d-object maps (%d rows, %.1f MB written): %s" % (N_MAP, 2 * N_MAP * OD, 8e-6 * (2 * N_MAP * OD) ** 2, timed(join)[0]))
+    mp.close()
+    n_big = 800
+    N = n_big * OD
+    big = 1e-3 * rng.normal(size=(N, N))
+    big += big.T
+    np.fill_diagonal(big, 1.0)
+    peaks = ba.measure_peaks()
+    with obvi_ba.Map.create(rng.normal(size=(n_big, OD)), big, object_block_size=OD) as wide:
+        def device_big():
+            wide.transform(ba, T, Sigma).close()
+        txt, ms = timed(device_big)
+        print("%d objects (%d rows, %.0f MB read and as much written): obvi_map_transform %s -- the whole call, allocation, two launches and the wait: %.0f GB/s   "
+              "(copy bandwidth of obvi_ba_measure_peaks: %.0f GB/s)" % (n_big, N, 8e-6 * N * N, txt, 2 * 8e-6 * N * N / ms, peaks["hbm_copy_gbs"]))
+    ba.close()
+
+
 def shared(n_sessions):
     """the map entries on handles that exchange shared objects."""
     import dist_util
@@ -381,4 +454,4 @@ if __name__ == "__main__":
     if "--shared" in sys.argv[1:]:
         shared(int(sys.argv[sys.argv.index("--shared") + 1]))
         sys.exit(0)
-    match() if "--match" in sys.argv[1:] else merge() if "--merge" in sys.argv[1:] else extend() if "--extend" in sys.argv[1:] else update() if "--update" in sys.argv[1:] else main()
+    move() if "--move" in sys.argv[1:] else match() if "--match" in sys.argv[1:] else merge() if "--merge" in sys.argv[1:] else extend() if "--extend" in sys.argv[1:] else update() if "--update" in sys.argv[1:] else main()
