@@ -298,6 +298,29 @@ struct MapFrameDev {
 void launch_map_transform(hipStream_t s, const MapFrameDev& f);
 // out = (mean_a, mean_b), blockdiag(cov_a, cov_b), copied entry by entry: one launch.  The two maps may be the same one.
 void launch_map_join(hipStream_t s, int64_t rows_a, const double* mean_a, const double* cov_a, int64_t rows_b, const double* mean_b, const double* cov_b, double* out_mean, double* out_cov);
+// One map located in another from the constellations of their object centres (include/obvi_map_locate.h; map_kernels.hip).  rec: [na + nb][12] -- centre,
+// the lower triangle of the symmetrised centre block (00 10 11 20 21 22), three unused -- A's objects first; lab beside it.  Rows of the seed count are
+// (a1, a2) over the whole na x na square (a1 >= a2: empty), so that the scan's order is the seeds' lexicographic one.
+constexpr int kLocateRec = 12, kLocateMaxObjects = 819;
+constexpr int64_t kLocateMaxSeeds = 1 << 20;
+struct MapLocateDev {
+  int32_t od, na, nb, min_inliers, iterations, has_label_a, has_label_b;
+  double dmin, tol, gate;
+  int64_t seed_cap;                                          // room of seeds / inl / cost: min(all seeds, kLocateMaxSeeds); more compatible seeds: nothing behind the scan runs
+  int64_t found, out;                                        // second half only: the hypotheses with >= min_inliers, and how many of them are reported
+  const double* mean_a; const double* cov_a; const double* mean_b; const double* cov_b;
+  const int32_t* label_a; const int32_t* label_b;            // [na], [nb]; read only with has_label_*
+  double* rec; int32_t* lab;                                 // [na + nb][12], [na + nb]
+  int64_t* row_cnt; int64_t* row_off; int64_t* totals;       // [na na][2] tested, compatible; [na na] compatible in the rows before; [3] the counts of the header
+  uint32_t* seeds; int32_t* inl; double* cost;               // [seed_cap][4], [seed_cap], [seed_cap]
+  int64_t* blk_cnt; int64_t* blk_off;                        // per 256 hypotheses: those with >= min_inliers, and those in the blocks before
+  uint32_t* qlist; uint32_t* sel;                            // [found] their hypothesis numbers in ascending order; [out] the reported ones by rank
+  uint32_t* out_seed; double* out_T; double* out_cov; int32_t* out_inl; double* out_cost; int32_t* out_partner;   // [out] x 4, 4, 16, 1, 1, nb
+};
+// first half, up to the counts: stage, count, scan, scatter, score, count and scan of the hypotheses that qualify.  na, nb >= 2.
+void launch_map_locate_score(hipStream_t s, const MapLocateDev& m);
+// second half, found >= out >= 1 known: the qualifying hypotheses compacted, ranked, and the first `out` refined
+void launch_map_locate_report(hipStream_t s, const MapLocateDev& m);
 // the posterior of the handle form: the k x k blocks of launch_cov_pairs (pair a k + b: objects a, b) -> dense P, and the objects' current values -> pm
 void launch_map_posterior_layout(hipStream_t s, const double* blocks, const double* objects, const uint32_t* obj_idx, int32_t k, int32_t od, double* P, double* pm);
 

@@ -9,6 +9,7 @@
 //                      posterior, and the map grown by a window's new objects or gathered (what the last two share: map_window.h)
 //   map_merge.cpp, map_match.cpp   duplicate objects of the map fused, and proposed (with the host-only resolver between the two)
 //   map_frame.cpp  the map moved into another frame under an uncertain transform; two maps joined
+//   map_locate.cpp one map located in another from the constellations of their object centres: the transform the move takes
 #ifndef OBVI_BA_HANDLE_H_
 #define OBVI_BA_HANDLE_H_
 #include "../../include/obvi_ba.h"
@@ -203,6 +204,9 @@ struct obvi_ba_handle {
   DevBuf<int32_t> d_mt_label; DevBuf<double> d_mt_diag, d_mt_stat, d_mt_out; DevBuf<int64_t> d_mt_cnt; DevBuf<uint32_t> d_mt_idx;
   // obvi_map_transform (map_frame.cpp): the objects' Jk, G and G Sigma_s of MapFrameDev, one after the other; empty until the first call
   DevBuf<double> d_mf_jac;
+  // obvi_map_locate (map_locate.cpp): the labels of both maps and the objects' records; the rows' and blocks' counts, offsets and the totals; the compatible seeds with their inliers and costs; the qualifying
+  // and the reported hypotheses; what is reported (doubles: transform, covariance, cost; ints: seed, inliers, partners); empty until the first call
+  DevBuf<int32_t> d_ml_label, d_ml_lab, d_ml_inl, d_ml_iout; DevBuf<double> d_ml_rec, d_ml_cost, d_ml_dout; DevBuf<int64_t> d_ml_cnt; DevBuf<uint32_t> d_ml_seeds, d_ml_list;
   DevBuf<double> d_bb_blk;                                    // per-factor blocks of the bounding-box factors (k_bbox_gather)
   DevBuf<double> d_sm_blk; DevBuf<uint32_t> d_smt_ptr, d_smt_idx;   // deterministic mode: the same for the priors and relative-pose factors (k_small_gather)
   int32_t bb_pairs_unique = 1;

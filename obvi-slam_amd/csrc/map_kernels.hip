@@ -17,7 +17,9 @@
 // (include/obvi_map_match.h): every pair's difference in units of its own covariance, one lane per pair, and the pairs within the gate compacted in (a, b) order
 // by counts and a scan.
 // After it: the map moved into another frame under an uncertain transform, object-aligned block pair by block pair, and two maps joined
-// (include/obvi_map_frame.h).
+// (include/obvi_map_frame.h).  Last: one map located in another from the constellations of their object centres (include/obvi_map_locate.h): compatible
+// seeds counted, scanned and scattered; every hypothesis scored with both maps' centres and centre blocks in local memory; the qualifying ones ranked by
+// counting; the reported ones refined, one wavefront each.
 #include "chol_tile.h"
 
 namespace obvi {
@@ -1062,7 +1064,403 @@ __global__ void __launch_bounds__(kThreads) k_mf_join(int64_t na, const double* 
   if (blockIdx.y == 0) out_mean[j] = j < na ? mean_a[j] : mean_b[j - na];
 }
 
+// ==== one map located in another from the constellations of their object centres (include/obvi_map_locate.h; MapLocateDev, ba_device.h) =================
+// Under the rules above.  Every count is a sum of integers, every output position comes from a scan of counts or from a rank that is a count, and the sums
+// of the refinement run down one lane's objects and then through wave_sum: nothing depends on the order in which workgroups run.  What the scoring and the
+// refining kernel must agree on bit for bit -- the seed's transform, a pair's statistic -- is formed by the same functions with contraction off.
+
+// object o of either map (A's first): centre, the lower triangle of its symmetrised centre block, its label (no labels: 0)
+__global__ void __launch_bounds__(64) k_ml_stage(MapLocateDev m) {
+  const int o = blockIdx.x * 64 + threadIdx.x;
+  if (o >= m.na + m.nb) return;
+  const bool in_a = o < m.na;
+  const int i = in_a ? o : o - m.na;
+  const int64_t ld = (int64_t)(in_a ? m.na : m.nb) * m.od;
+  const double* mu = (in_a ? m.mean_a : m.mean_b) + (int64_t)i * m.od;
+  const double* C = (in_a ? m.cov_a : m.cov_b) + ((int64_t)i * m.od) * ld + (int64_t)i * m.od;
+  double* r = m.rec + (int64_t)o * kLocateRec;
+  r[0] = mu[0]; r[1] = mu[1]; r[2] = mu[2];
+  r[3] = 0.5 * (C[0] + C[0]);
+  r[4] = 0.5 * (C[ld] + C[1]); r[5] = 0.5 * (C[ld + 1] + C[ld + 1]);
+  r[6] = 0.5 * (C[2 * ld] + C[2]); r[7] = 0.5 * (C[2 * ld + 1] + C[ld + 2]); r[8] = 0.5 * (C[2 * ld + 2] + C[2 * ld + 2]);
+  r[9] = 0.0; r[10] = 0.0; r[11] = 0.0;
+  m.lab[o] = in_a ? (m.has_label_a ? m.label_a[i] : 0) : (m.has_label_b ? m.label_b[i] : 0);
+}
+
+// a seed: 0 not tested (labels), 1 tested, 2 compatible; every operation rounded on its own, as in k_mt_pairs' distance test
+__device__ __forceinline__ int ml_seed_test(const double* pa1, const double* pa2, const double* pb1, const double* pb2, int la1, int la2, int lb1, int lb2, double dmin, double tol) {
+  if (!(la1 >= 0 && la1 == lb1 && la2 >= 0 && la2 == lb2)) return 0;
+  const double ux = __dsub_rn(pa2[0], pa1[0]), uy = __dsub_rn(pa2[1], pa1[1]), vx = __dsub_rn(pb2[0], pb1[0]), vy = __dsub_rn(pb2[1], pb1[1]);
+  const double nu = sqrt(__dadd_rn(__dmul_rn(ux, ux), __dmul_rn(uy, uy))), nv = sqrt(__dadd_rn(__dmul_rn(vx, vx), __dmul_rn(vy, vy)));
+  const double dz = __dsub_rn(__dsub_rn(pa2[2], pa1[2]), __dsub_rn(pb2[2], pb1[2]));
+  return (nu >= dmin && nv >= dmin && fabs(__dsub_rn(nu, nv)) <= tol && fabs(dz) <= tol) ? 2 : 1;
+}
+// its transform (tx ty tz psi)
+__device__ __forceinline__ void ml_hypothesis(const double* pa1, const double* pa2, const double* pb1, const double* pb2, double* T) {
+  const double ux = __dsub_rn(pa2[0], pa1[0]), uy = __dsub_rn(pa2[1], pa1[1]), vx = __dsub_rn(pb2[0], pb1[0]), vy = __dsub_rn(pb2[1], pb1[1]);
+  const double psi = atan2(__dsub_rn(__dmul_rn(vx, uy), __dmul_rn(vy, ux)), __dadd_rn(__dmul_rn(vx, ux), __dmul_rn(vy, uy)));
+  const double c = cos(psi), s = sin(psi);
+  const double ax = __dmul_rn(0.5, __dadd_rn(pa1[0], pa2[0])), ay = __dmul_rn(0.5, __dadd_rn(pa1[1], pa2[1])), az = __dmul_rn(0.5, __dadd_rn(pa1[2], pa2[2]));
+  const double bx = __dmul_rn(0.5, __dadd_rn(pb1[0], pb2[0])), by = __dmul_rn(0.5, __dadd_rn(pb1[1], pb2[1])), bz = __dmul_rn(0.5, __dadd_rn(pb1[2], pb2[2]));
+  T[0] = __dsub_rn(ax, __dsub_rn(__dmul_rn(c, bx), __dmul_rn(s, by)));
+  T[1] = __dsub_rn(ay, __dadd_rn(__dmul_rn(s, bx), __dmul_rn(c, by)));
+  T[2] = __dsub_rn(az, bz);
+  T[3] = psi;
+}
+// the lower triangle (00 10 11 20 21 22) of Rz B Rz^T from B's
+__device__ __forceinline__ void ml_rotate_block(const double* B, double c, double s, double* R) {
+#pragma clang fp contract(off)
+  const double m00 = c * B[0] - s * B[1], m01 = c * B[1] - s * B[2], m10 = s * B[0] + c * B[1], m11 = s * B[1] + c * B[2];
+  R[0] = m00 * c - m01 * s; R[1] = m10 * c - m11 * s; R[2] = m10 * s + m11 * c;
+  R[3] = B[3] * c - B[4] * s; R[4] = B[3] * s + B[4] * c; R[5] = B[5];
+}
+// S = A + R = L L^T by the unrolled Cholesky with k_map_potrf's pivot rule -- a select, never a branch -- and the pivot test of k_mt_pairs; false: singular
+__device__ __forceinline__ bool ml_factor(const double* A, const double* R, double* L, double* d) {
+#pragma clang fp contract(off)
+  const double s00 = A[0] + R[0], s10 = A[1] + R[1], s11 = A[2] + R[2], s20 = A[3] + R[3], s21 = A[4] + R[4], s22 = A[5] + R[5];
+  const bool ok0 = s00 > 0.0 && isfinite(s00);
+  d[0] = sqrt(ok0 ? s00 : 1.0);
+  L[0] = s10 / d[0]; L[1] = s20 / d[0];
+  const double p1 = s11 - L[0] * L[0];
+  const bool ok1 = p1 > 0.0 && isfinite(p1);
+  d[1] = sqrt(ok1 ? p1 : 1.0);
+  L[2] = (s21 - L[1] * L[0]) / d[1];
+  const double p2 = (s22 - L[1] * L[1]) - L[2] * L[2];
+  const bool ok2 = p2 > 0.0 && isfinite(p2);
+  d[2] = sqrt(ok2 ? p2 : 1.0);
+  const double pmin = fmin(d[0], fmin(d[1], d[2])), pmax = fmax(d[0], fmax(d[1], d[2]));
+  return ok0 && ok1 && ok2 && pmin * pmin > 1e-13 * pmax * pmax;
+}
+// y = L^-1 e
+__device__ __forceinline__ void ml_forward(const double* L, const double* d, double e0, double e1, double e2, double* y) {
+#pragma clang fp contract(off)
+  y[0] = e0 / d[0];
+  y[1] = (e1 - L[0] * y[0]) / d[1];
+  y[2] = ((e2 - L[1] * y[0]) - L[2] * y[1]) / d[2];
+}
+// object b of B under (T, c = cos psi, s = sin psi): the smallest statistic over the objects of A that carry its label, and which one (-1: none)
+__device__ __forceinline__ int ml_partner(const double* rec, const int32_t* lab, int na, int b, const double* T, double c, double s, double* best_out) {
+#pragma clang fp contract(off)
+  const int32_t lb = lab[na + b];
+  double best = INFINITY;
+  int who = -1;
+  if (lb >= 0) {
+    const double* pb = rec + (int64_t)(na + b) * kLocateRec;
+    const double qx = (c * pb[0] - s * pb[1]) + T[0], qy = (s * pb[0] + c * pb[1]) + T[1], qz = pb[2] + T[2];
+    double R[6];
+    ml_rotate_block(pb + 3, c, s, R);
+    for (int a = 0; a < na; ++a) {
+      if (lab[a] != lb) continue;
+      const double* pa = rec + (int64_t)a * kLocateRec;
+      double L[3], d[3], y[3];
+      const bool ok = ml_factor(pa + 3, R, L, d);
+      ml_forward(L, d, pa[0] - qx, pa[1] - qy, pa[2] - qz, y);
+      const double st = (y[0] * y[0] + y[1] * y[1]) + y[2] * y[2];
+      if (ok && st < best) { best = st; who = a; }
+    }
+  }
+  *best_out = best;
+  return who;
+}
+
+// row (a1, a2) of the na x na square: its tested and its compatible seeds
+__global__ void __launch_bounds__(kThreads) k_ml_count(MapLocateDev m) {
+  __shared__ int32_t part[2][kThreads / 64];
+  const int a1 = blockIdx.y, a2 = blockIdx.x, tid = threadIdx.x, na = m.na, nb = m.nb;
+  int32_t c[2] = {0, 0};
+  if (a1 < a2) {
+    const double* pa1 = m.rec + (int64_t)a1 * kLocateRec; const double* pa2 = m.rec + (int64_t)a2 * kLocateRec;
+    const int32_t la1 = m.lab[a1], la2 = m.lab[a2];
+    for (int j = tid; j < nb * nb; j += kThreads) {
+      const int b1 = j / nb, b2 = j - b1 * nb;
+      if (b1 == b2) continue;
+      const int code = ml_seed_test(pa1, pa2, m.rec + (int64_t)(na + b1) * kLocateRec, m.rec + (int64_t)(na + b2) * kLocateRec, la1, la2, m.lab[na + b1], m.lab[na + b2], m.dmin, m.tol);
+      c[0] += code >= 1 ? 1 : 0; c[1] += code == 2 ? 1 : 0;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+#pragma unroll
+    for (int x = 32; x >= 1; x >>= 1) c[i] += __shfl_xor(c[i], x, 64);
+    if ((tid & 63) == 0) part[i][tid >> 6] = c[i];
+  }
+  __syncthreads();
+  if (tid < 2) { int64_t sum = 0; for (int w = 0; w < kThreads / 64; ++w) sum += part[tid][w]; m.row_cnt[2 * ((int64_t)a1 * na + a2) + tid] = sum; }
+}
+
+// one workgroup: off[i] = the counts [i][stride] of the entries before i, and their sum; the two uses: the rows' seeds, the blocks' qualifying hypotheses
+__device__ __forceinline__ int64_t ml_scan(const int64_t* cnt, int stride, int64_t n, int64_t* off, int64_t* part) {
+  const int tid = threadIdx.x;
+  const int64_t per = (n + kThreads - 1) / kThreads, lo = tid * per < n ? tid * per : n, hi = lo + per < n ? lo + per : n;
+  int64_t c = 0;
+  for (int64_t i = lo; i < hi; ++i) c += cnt[stride * i];
+  part[tid] = c;
+  __syncthreads();
+  if (tid == 0) {
+    int64_t run = 0;
+    for (int x = 0; x < kThreads; ++x) { const int64_t v = part[x]; part[x] = run; run += v; }
+    part[kThreads] = run;
+  }
+  __syncthreads();
+  int64_t o = part[tid];
+  for (int64_t i = lo; i < hi; ++i) { off[i] = o; o += cnt[stride * i]; }
+  return part[kThreads];
+}
+__global__ void __launch_bounds__(kThreads) k_ml_scan(MapLocateDev m) {
+  __shared__ int64_t part[kThreads + 1], tested[kThreads];
+  const int tid = threadIdx.x;
+  const int64_t rows = (int64_t)m.na * m.na, per = (rows + kThreads - 1) / kThreads, lo = tid * per < rows ? tid * per : rows, hi = lo + per < rows ? lo + per : rows;
+  int64_t t = 0;
+  for (int64_t i = lo; i < hi; ++i) t += m.row_cnt[2 * i];
+  tested[tid] = t;
+  const int64_t compatible = ml_scan(m.row_cnt + 1, 2, rows, m.row_off, part);
+  if (tid == 0) {
+    int64_t sum = 0;
+    for (int x = 0; x < kThreads; ++x) sum += tested[x];
+    m.totals[0] = sum; m.totals[1] = compatible; m.totals[2] = 0;
+  }
+}
+
+// where a workgroup's hits go: the hits of the threads before this one, and (all) of the whole workgroup; wcnt: [kThreads / 64]
+__device__ __forceinline__ int ml_place(bool hit, int32_t* wcnt, int* all) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const uint64_t votes = __ballot(hit);
+  __syncthreads();
+  if (lane == 0) wcnt[wv] = __popcll(votes);
+  __syncthreads();
+  int before = __popcll(votes & ((1ull << lane) - 1ull));
+  *all = 0;
+  for (int w = 0; w < kThreads / 64; ++w) { before += w < wv ? wcnt[w] : 0; *all += wcnt[w]; }
+  return before;
+}
+
+// row (a1, a2): its compatible seeds to their places behind row_off, in the order of (b1, b2)
+__global__ void __launch_bounds__(kThreads) k_ml_scatter(MapLocateDev m) {
+  __shared__ int32_t wcnt[kThreads / 64];
+  const int a1 = blockIdx.y, a2 = blockIdx.x, tid = threadIdx.x, na = m.na, nb = m.nb;
+  const int64_t row = (int64_t)a1 * na + a2;
+  if (a1 >= a2 || m.totals[1] > m.seed_cap || m.row_cnt[2 * row + 1] == 0) return;
+  const double* pa1 = m.rec + (int64_t)a1 * kLocateRec; const double* pa2 = m.rec + (int64_t)a2 * kLocateRec;
+  const int32_t la1 = m.lab[a1], la2 = m.lab[a2];
+  int64_t base = m.row_off[row];
+  for (int j0 = 0; j0 < nb * nb; j0 += kThreads) {
+    const int j = j0 + tid, b1 = j / nb, b2 = j - b1 * nb;
+    const bool hit = j < nb * nb && b1 != b2 &&
+                     ml_seed_test(pa1, pa2, m.rec + (int64_t)(na + b1) * kLocateRec, m.rec + (int64_t)(na + b2) * kLocateRec, la1, la2, m.lab[na + b1], m.lab[na + b2], m.dmin, m.tol) == 2;
+    int all;
+    const int before = ml_place(hit, wcnt, &all);
+    if (hit) { uint32_t* sd = m.seeds + 4 * (base + before); sd[0] = (uint32_t)a1; sd[1] = (uint32_t)a2; sd[2] = (uint32_t)b1; sd[3] = (uint32_t)b2; }
+    base += all;
+  }
+}
+
+// The hot launch.  Both maps' records and labels in local memory (all of it dynamic: 100 bytes an object, 80 KiB at the object limit, two workgroups a
+// compute unit).  kLocateLanes neighbouring lanes share a hypothesis: lane g walks the objects b = g, g + 16, ... of B and, for each, every a -- all lanes read
+// the same record of A at the same time, a broadcast -- and after each round the sixteen minima go round the group in ascending b, so every lane of the group
+// forms the same count and the same sum, in the order the header states.  (One lane a hypothesis left a 200 x 60 search with its 2 860 hypotheses on twelve
+// compute units for 5.8 ms.)
+constexpr int kLocateLanes = 16;
+__global__ void __launch_bounds__(kThreads) k_ml_score(MapLocateDev m) {
+  extern __shared__ __attribute__((aligned(16))) char ml_lds[];
+  const int64_t H = m.totals[1];
+  if (H > m.seed_cap || (int64_t)blockIdx.x * (kThreads / kLocateLanes) >= H) return;
+  const int n = m.na + m.nb, na = m.na, nb = m.nb, tid = threadIdx.x, g = tid % kLocateLanes;
+  double* rec = reinterpret_cast<double*>(ml_lds);
+  int32_t* lab = reinterpret_cast<int32_t*>(rec + (int64_t)n * kLocateRec);
+  for (int e = tid; e < n * kLocateRec; e += kThreads) rec[e] = m.rec[e];
+  for (int e = tid; e < n; e += kThreads) lab[e] = m.lab[e];
+  __syncthreads();
+  const int64_t h = (int64_t)blockIdx.x * (kThreads / kLocateLanes) + tid / kLocateLanes;
+  if (h >= H) return;   // whole groups leave: the exchanges below stay inside a group
+  const uint32_t* sd = m.seeds + 4 * h;
+  double T[4];
+  ml_hypothesis(rec + sd[0] * kLocateRec, rec + sd[1] * kLocateRec, rec + (na + sd[2]) * kLocateRec, rec + (na + sd[3]) * kLocateRec, T);
+  const double c = cos(T[3]), s = sin(T[3]);
+  int32_t inl = 0;
+  double cost = 0.0;
+  for (int b0 = 0; b0 < nb; b0 += kLocateLanes) {
+    double best = INFINITY;
+    if (b0 + g < nb) ml_partner(rec, lab, na, b0 + g, T, c, s, &best);
+#pragma unroll
+    for (int x = 0; x < kLocateLanes; ++x) {
+      const double v = __shfl(best, x, kLocateLanes);
+      if (v <= m.gate) { ++inl; cost += v; }
+    }
+  }
+  if (g == 0) { m.inl[h] = inl; m.cost[h] = cost; }
+}
+
+// 256 hypotheses: how many qualify
+__device__ __forceinline__ bool ml_qualifies(const MapLocateDev& m, int64_t h) { const int64_t H = m.totals[1]; return H <= m.seed_cap && h < H && m.inl[h] >= m.min_inliers; }
+__global__ void __launch_bounds__(kThreads) k_ml_qcount(MapLocateDev m) {
+  __shared__ int32_t wcnt[kThreads / 64];
+  int all;
+  ml_place(ml_qualifies(m, (int64_t)blockIdx.x * kThreads + threadIdx.x), wcnt, &all);
+  if (threadIdx.x == 0) m.blk_cnt[blockIdx.x] = all;
+}
+__global__ void __launch_bounds__(kThreads) k_ml_qscan(MapLocateDev m) {
+  __shared__ int64_t part[kThreads + 1];
+  const int64_t found = ml_scan(m.blk_cnt, 1, (m.seed_cap + kThreads - 1) / kThreads, m.blk_off, part);
+  if (threadIdx.x == 0) m.totals[2] = found;
+}
+// ... and their numbers, in ascending order
+__global__ void __launch_bounds__(kThreads) k_ml_qscatter(MapLocateDev m) {
+  __shared__ int32_t wcnt[kThreads / 64];
+  const int64_t h = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  const bool hit = ml_qualifies(m, h);
+  int all;
+  const int before = ml_place(hit, wcnt, &all);
+  if (hit) m.qlist[m.blk_off[blockIdx.x] + before] = (uint32_t)h;
+}
+
+// The rank of a qualifying hypothesis is the number of those that precede it -- more inliers, then the lower cost, then the lower seed index (the hypothesis
+// number: the seeds were compacted in that order) -- a count, whatever order the workgroups run in.  The first `out` ranks are the report.
+__global__ void __launch_bounds__(kThreads) k_ml_rank(MapLocateDev m) {
+  __shared__ int32_t ki[kThreads];
+  __shared__ double kc[kThreads];
+  __shared__ uint32_t kh[kThreads];
+  const int tid = threadIdx.x;
+  const int64_t q = (int64_t)blockIdx.x * kThreads + tid;
+  const bool valid = q < m.found;
+  const uint32_t mh = valid ? m.qlist[q] : 0u;
+  const int32_t mi = valid ? m.inl[mh] : 0;
+  const double mc = valid ? m.cost[mh] : 0.0;
+  int64_t before = 0;
+  for (int64_t t0 = 0; t0 < m.found; t0 += kThreads) {
+    __syncthreads();
+    const int64_t j = t0 + tid;
+    const uint32_t hh = j < m.found ? m.qlist[j] : 0u;
+    ki[tid] = j < m.found ? m.inl[hh] : -1; kc[tid] = j < m.found ? m.cost[hh] : 0.0; kh[tid] = hh;
+    __syncthreads();
+    for (int x = 0; x < kThreads; ++x) {
+      const int32_t i = ki[x];
+      const double cx = kc[x];
+      before += (i > mi || (i == mi && (cx < mc || (cx == mc && kh[x] < mh)))) ? 1 : 0;
+    }
+  }
+  if (valid && before < m.out) m.sel[before] = mh;
+}
+
+// One wavefront per reported hypothesis: the partners (lane l: objects l, l + 64, ... of B), then the Gauss-Newton steps on the inliers with the partners held,
+// H (lower triangle, ten sums) and g (four) down each lane's objects and through wave_sum, the 4 x 4 solve on every lane alike.
+__global__ void __launch_bounds__(64) k_ml_refine(MapLocateDev m) {
+  const int r = blockIdx.x, lane = threadIdx.x, na = m.na, nb = m.nb;
+  const uint32_t hh = m.sel[r];
+  const uint32_t* sd = m.seeds + 4 * (int64_t)hh;
+  double T[4];
+  ml_hypothesis(m.rec + sd[0] * kLocateRec, m.rec + sd[1] * kLocateRec, m.rec + (na + sd[2]) * kLocateRec, m.rec + (na + sd[3]) * kLocateRec, T);
+  int32_t* pr = m.out_partner + (int64_t)r * nb;
+  {
+    const double c = cos(T[3]), s = sin(T[3]);
+    for (int b = lane; b < nb; b += 64) {
+      double best;
+      const int who = ml_partner(m.rec, m.lab, na, b, T, c, s, &best);
+      pr[b] = best <= m.gate ? who : -1;
+    }
+  }
+  double Hi[10];   // the lower triangle of H^-1, row by row
+  for (int it = 0; it <= m.iterations; ++it) {
+    const double c = cos(T[3]), s = sin(T[3]);
+    double acc[14];
+#pragma unroll
+    for (int i = 0; i < 14; ++i) acc[i] = 0.0;
+    for (int b = lane; b < nb; b += 64) {
+      const int a = pr[b];
+      if (a < 0) continue;
+      const double* pb = m.rec + (int64_t)(na + b) * kLocateRec; const double* pa = m.rec + (int64_t)a * kLocateRec;
+      double R[6], L[3], d[3], y[3], z[4][3];
+      ml_rotate_block(pb + 3, c, s, R);
+      if (!ml_factor(pa + 3, R, L, d)) continue;
+      ml_forward(L, d, pa[0] - ((c * pb[0] - s * pb[1]) + T[0]), pa[1] - ((s * pb[0] + c * pb[1]) + T[1]), pa[2] - (pb[2] + T[2]), y);
+      ml_forward(L, d, 1.0, 0.0, 0.0, z[0]); ml_forward(L, d, 0.0, 1.0, 0.0, z[1]); ml_forward(L, d, 0.0, 0.0, 1.0, z[2]);
+      ml_forward(L, d, -s * pb[0] - c * pb[1], c * pb[0] - s * pb[1], 0.0, z[3]);   // Rz'(psi) p_b
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+#pragma unroll
+        for (int l = 0; l <= k; ++l) acc[k * (k + 1) / 2 + l] += (z[k][0] * z[l][0] + z[k][1] * z[l][1]) + z[k][2] * z[l][2];
+        acc[10 + k] += (z[k][0] * y[0] + z[k][1] * y[1]) + z[k][2] * y[2];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 14; ++i) acc[i] = wave_sum(acc[i]);
+    // H = L L^T in place (the pivot rule again), then W = L^-1 and H^-1 = W^T W
+    double W[10];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+      for (int k = 0; k < j; ++k) {
+        const double ljk = acc[j * (j + 1) / 2 + k];
+#pragma unroll
+        for (int i = j; i < 4; ++i) acc[i * (i + 1) / 2 + j] -= acc[i * (i + 1) / 2 + k] * ljk;
+      }
+      const double p = acc[j * (j + 1) / 2 + j];
+      const double dj = sqrt((p > 0.0 && isfinite(p)) ? p : 1.0);
+      acc[j * (j + 1) / 2 + j] = dj;
+#pragma unroll
+      for (int i = j + 1; i < 4; ++i) acc[i * (i + 1) / 2 + j] /= dj;
+    }
+#pragma unroll
+    for (int cc = 0; cc < 4; ++cc) {   // column cc of W, rows cc .. 3
+#pragma unroll
+      for (int i = cc; i < 4; ++i) {
+        double sum = i == cc ? 1.0 : 0.0;
+#pragma unroll
+        for (int k = cc; k < i; ++k) sum -= acc[i * (i + 1) / 2 + k] * W[k * (k + 1) / 2 + cc];
+        W[i * (i + 1) / 2 + cc] = sum / acc[i * (i + 1) / 2 + i];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int j = 0; j <= i; ++j) {
+        double sum = 0.0;
+#pragma unroll
+        for (int k = i; k < 4; ++k) sum += W[k * (k + 1) / 2 + i] * W[k * (k + 1) / 2 + j];
+        Hi[i * (i + 1) / 2 + j] = sum;
+      }
+    }
+    if (it < m.iterations) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        double sum = 0.0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sum += Hi[i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i] * acc[10 + j];
+        T[i] += sum;
+      }
+    }
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      m.out_seed[4 * (int64_t)r + i] = sd[i];
+      m.out_T[4 * (int64_t)r + i] = T[i];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) m.out_cov[16 * (int64_t)r + 4 * i + j] = Hi[i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i];
+    }
+    m.out_inl[r] = m.inl[hh]; m.out_cost[r] = m.cost[hh];
+  }
+}
+
 }  // namespace
+
+void launch_map_locate_score(hipStream_t s, const MapLocateDev& m) {
+  const int n = m.na + m.nb;
+  const unsigned blocks = (unsigned)((m.seed_cap + kThreads - 1) / kThreads);
+  const size_t lds = ((size_t)n * (kLocateRec * sizeof(double) + sizeof(int32_t)) + 15) & ~(size_t)15;
+  hipLaunchKernelGGL(k_ml_stage, dim3((n + 63) / 64), dim3(64), 0, s, m);
+  hipLaunchKernelGGL(k_ml_count, dim3(m.na, m.na), dim3(kThreads), 0, s, m);
+  hipLaunchKernelGGL(k_ml_scan, dim3(1), dim3(kThreads), 0, s, m);
+  hipLaunchKernelGGL(k_ml_scatter, dim3(m.na, m.na), dim3(kThreads), 0, s, m);
+  if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_ml_score), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);   // a refusal shows as the launch's error
+  hipLaunchKernelGGL(k_ml_score, dim3(blocks * kLocateLanes), dim3(kThreads), lds, s, m);
+  hipLaunchKernelGGL(k_ml_qcount, dim3(blocks), dim3(kThreads), 0, s, m);
+  hipLaunchKernelGGL(k_ml_qscan, dim3(1), dim3(kThreads), 0, s, m);
+}
+void launch_map_locate_report(hipStream_t s, const MapLocateDev& m) {
+  hipLaunchKernelGGL(k_ml_qscatter, dim3((unsigned)((m.seed_cap + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, m);
+  hipLaunchKernelGGL(k_ml_rank, dim3((unsigned)((m.found + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, m);
+  hipLaunchKernelGGL(k_ml_refine, dim3((unsigned)m.out), dim3(64), 0, s, m);
+}
 
 void launch_map_transform(hipStream_t s, const MapFrameDev& f) {
   const int B = T / f.od, nb = (f.n + B - 1) / B;

@@ -5,6 +5,7 @@ The same class can bind any library exporting the ABI under another symbol prefi
 tests use that to drive the CPU oracle (oracle/libobvi_oracle.so, prefix "oracle_") with the
 very same arrays.  Nothing here computes anything; a missing library raises.
 """
+import collections
 import ctypes as C
 import os
 
@@ -81,6 +82,14 @@ class ParallaxParams(C.Structure):
 
     def __init__(self, min_pixel=5.0, min_transl=0.1, min_orient=0.05, enforce_pixel=True, enforce_pose=False):
         super().__init__(min_pixel, min_transl, min_orient, int(enforce_pixel), int(enforce_pose))
+
+
+class LocateParams(C.Structure):
+    """obvi_map_locate_params (include/obvi_map_locate.h)."""
+    _fields_ = [("pair_min_distance", C.c_double), ("pair_tolerance", C.c_double), ("inlier_gate", C.c_double), ("min_inliers", C.c_int32), ("refine_iterations", C.c_int32)]
+
+
+Located = collections.namedtuple("Located", "seed transform transform_cov inliers cost partner counts move")
 
 
 class ObviError(RuntimeError):
@@ -312,6 +321,46 @@ class Map:
         new = C.c_void_p()
         rc = self._frame_fn("map_join")(ba._h, self._m, other._m, C.byref(new))
         return self._conditioned(ba, rc, new, "map_join")
+
+    # ---- where another map lies in this one (include/obvi_map_locate.h) ----
+    def locate(self, ba, other, pair_min_distance, pair_tolerance, inlier_gate, min_inliers=3, refine_iterations=3, labels=None, other_labels=None, capacity=None):
+        """Located(seed [k][4], transform [k][4], transform_cov [k][4][4], inliers [k], cost [k], partner [k][n_other], counts, move [k][dT]): the transforms
+        T_self<-other = (tx ty tz psi) that lay `other`'s object centres onto this map's, best first; counts = (seeds tested, seeds compatible, hypotheses with
+        >= min_inliers).  move is what Map.transform of `other` takes: transform itself for od 7, (t, 0, 0, psi) for od 9.  capacity None: a count-only
+        call, then one of the exact size."""
+        try:
+            f = getattr(self._lib, self._pre + "map_locate")
+        except AttributeError:
+            raise ObviError("%smap_locate: this library cannot locate a map in another (include/obvi_map_locate.h is served by libobvi_ba.so only)" % self._pre)
+        f.restype = C.c_int
+        na, nb = self.n_objects, other.n_objects
+        la = None if labels is None else np.ascontiguousarray(labels, dtype=np.int32).ravel()
+        lb = None if other_labels is None else np.ascontiguousarray(other_labels, dtype=np.int32).ravel()
+        if (la is not None and len(la) != na) or (lb is not None and len(lb) != nb):
+            raise ObviError("map_locate: labels must name every object of their map")
+        params = LocateParams(float(pair_min_distance), float(pair_tolerance), float(inlier_gate), int(min_inliers), int(refine_iterations))
+        counts = np.zeros(3, np.int64)
+
+        def call(cap, seed, t, cov, inl, cost, partner):
+            ba._check(f(ba._h, self._m, other._m, _ptr(la, C.c_int32), _ptr(lb, C.c_int32), C.byref(params), C.c_int64(cap), _ptr(seed, C.c_uint32), _ptr(t, C.c_double),
+                        _ptr(cov, C.c_double), _ptr(inl, C.c_int32), _ptr(cost, C.c_double), _ptr(partner, C.c_int32), _ptr(counts, C.c_int64)), "map_locate")
+
+        counted = capacity is None
+        if counted:
+            call(0, None, None, None, None, None, None)
+            capacity = counts[2]
+        capacity = int(capacity)
+        if capacity < 0:
+            call(capacity, None, None, None, None, None, None)         # refused: raises
+        seed, t, cov = np.zeros((capacity, 4), np.uint32), np.zeros((capacity, 4)), np.zeros((capacity, 4, 4))
+        inl, cost, partner = np.zeros(capacity, np.int32), np.zeros(capacity), np.full((capacity, nb), -1, np.int32)
+        if capacity > 0:
+            call(capacity, seed, t, cov, inl, cost, partner)
+        elif not counted:
+            call(0, None, None, None, None, None, None)
+        k = min(capacity, int(counts[2]))
+        move = t[:k].copy() if self.od == 7 else np.concatenate([t[:k, :3], np.zeros((k, 2)), t[:k, 3:]], axis=1)
+        return Located(seed[:k], t[:k], cov[:k], inl[:k], cost[:k], partner[:k], tuple(int(c) for c in counts), move)
 
     def close(self):
         if self._m:

@@ -17,7 +17,10 @@ included, against the only route without it: obvi_map_get and the same statistic
 --move: another frame -- obvi_map_transform of the 200-object map without and with a transform covariance, wait included, against the round
 trip that moves it without the entry: obvi_map_get, the same formula in numpy, obvi_map_create; obvi_map_join of two 200-object maps; and the move of a
 800-object map (5 600 rows, 251 MB), where the covariance kernel is most of the call, beside the copy bandwidth obvi_ba_measure_peaks reports.
-usage (GPU box, repo root): python scripts/map_bench.py [--update | --extend | --merge | --match | --move | --shared K]"""
+--locate: where another map lies -- obvi_map_locate of a 60-object moved and noisy part of the 200-object map in that map (no labels: 70 million
+seeds), both waits and the refinement of the best 16 hypotheses included, against the only route without it: obvi_map_get of both maps and the same
+hypothesise-and-score search vectorised in numpy.
+usage (GPU box, repo root): python scripts/map_bench.py [--update | --extend | --merge | --match | --move | --locate | --shared K]"""
 import os
 import sys
 import time
@@ -390,6 +393,101 @@ def move():
     ba.close()
 
 
+def numpy_locate(mean_a, cov_a, mean_b, cov_b, dmin, tol, gate, min_inliers):
+    """The search of include/obvi_map_locate.h on the host, fp64, up to the ranking: (counts, best seed, its inliers, its cost)."""
+    def records(mean, cov):
+        n = len(mean)
+        Cs = 0.5 * (cov + cov.T)
+        return mean[:, :3], np.array([Cs[OD * o:OD * o + 3, OD * o:OD * o + 3] for o in range(n)])
+    pa, A = records(mean_a, cov_a)
+    pb, B = records(mean_b, cov_b)
+    na, nb = len(pa), len(pb)
+    a1, a2 = np.triu_indices(na, 1)
+    b1, b2 = np.divmod(np.arange(nb * nb), nb)
+    b1, b2 = b1[b1 != b2], b2[b1 != b2]
+    u, v = pa[a2] - pa[a1], pb[b2] - pb[b1]
+    nu, nv = np.hypot(u[:, 0], u[:, 1]), np.hypot(v[:, 0], v[:, 1])
+    rows, cols = np.flatnonzero(nu >= dmin), np.flatnonzero(nv >= dmin)
+    seeds = []
+    for r0 in range(0, len(rows), 512):                                # 512 rows of A pairs against every B pair at a time
+        r = rows[r0:r0 + 512]
+        ok = (np.abs(nu[r, None] - nv[None, cols]) <= tol) & (np.abs(u[r, 2][:, None] - v[cols, 2][None, :]) <= tol)
+        i, j = np.nonzero(ok)
+        seeds.append(np.column_stack([a1[r[i]], a2[r[i]], b1[cols[j]], b2[cols[j]]]))
+    seeds = np.concatenate(seeds)
+    sa1, sa2, sb1, sb2 = seeds.T
+    su, sv = pa[sa2] - pa[sa1], pb[sb2] - pb[sb1]
+    psi = np.arctan2(sv[:, 0] * su[:, 1] - sv[:, 1] * su[:, 0], sv[:, 0] * su[:, 0] + sv[:, 1] * su[:, 1])
+    cs, sn = np.cos(psi), np.sin(psi)
+    ma, mb = 0.5 * (pa[sa1] + pa[sa2]), 0.5 * (pb[sb1] + pb[sb2])
+    t = np.column_stack([ma[:, 0] - (cs * mb[:, 0] - sn * mb[:, 1]), ma[:, 1] - (sn * mb[:, 0] + cs * mb[:, 1]), ma[:, 2] - mb[:, 2]])
+    inl, cost = np.zeros(len(seeds), np.int64), np.zeros(len(seeds))
+    for h0 in range(0, len(seeds), 64):
+        h = slice(h0, h0 + 64)
+        R = np.zeros((len(cs[h]), 3, 3))
+        R[:, 0, 0], R[:, 0, 1], R[:, 1, 0], R[:, 1, 1], R[:, 2, 2] = cs[h], -sn[h], sn[h], cs[h], 1.0
+        e = pa[None, None] - (np.einsum("hij,bj->hbi", R, pb) + t[h, None])[:, :, None]
+        S = A[None, None] + np.einsum("hij,bjk,hlk->hbil", R, B, R)[:, :, None]
+        s = np.einsum("hbai,hbai->hba", e, np.linalg.solve(S, e[..., None])[..., 0])
+        best = s.min(axis=2)
+        inl[h], cost[h] = (best <= gate).sum(axis=1), np.where(best <= gate, best, 0.0).sum(axis=1)
+    q = np.flatnonzero(inl >= min_inliers)
+    first = q[np.lexsort((q, cost[q], -inl[q]))[0]]
+    return (na * (na - 1) // 2 * nb * (nb - 1), len(seeds), len(q)), seeds[first], int(inl[first]), float(cost[first])
+
+
+def locate():
+    """one map located in another.  The device entry against the only route without it."""
+    rng = np.random.default_rng(1)
+    n_b = 60
+    mean = rng.normal(size=(N_MAP, OD))
+    mean[:, :2], mean[:, 2] = rng.uniform(-50.0, 50.0, size=(N_MAP, 2)), rng.uniform(0.0, 3.0, size=N_MAP)
+    cov = spd(rng, N_MAP * OD)
+    cov *= 0.03 ** 2 / np.diag(cov).mean()
+    T = np.array([-4.0, 2.5, 0.3, -1.1])
+    c, s = np.cos(T[3]), np.sin(T[3])
+    part = rng.permutation(N_MAP)[:n_b]
+    mean_b = mean[part].copy()
+    mean_b[:, :3] = (mean[part, :3] - T[:3]) @ np.array([[c, -s, 0], [s, c, 0], [0, 0, 1.0]])
+    cov_b = spd(rng, n_b * OD)
+    cov_b *= 0.03 ** 2 / np.diag(cov_b).mean()
+    mean_b += (np.linalg.cholesky(cov_b) @ rng.normal(size=n_b * OD)).reshape(n_b, OD)
+    ma, mb = obvi_ba.Map.create(mean, cov, object_block_size=OD), obvi_ba.Map.create(mean_b, cov_b, object_block_size=OD)
+    ba = obvi_ba.BundleAdjuster(object_block_size=OD)
+    ba.set_cameras(synth.K_DEFAULT[None], synth.EXT_DEFAULT[None])
+    ba.set_poses(np.zeros((1, 6)), np.ones(1, np.uint8))
+    ba.set_points(np.zeros((0, 3)), np.zeros(0, np.uint8))
+    ba.set_objects(np.zeros((1, OD)), np.zeros(1, np.uint8))
+    dmin, tol, gate, min_inliers = 5.0, 0.05, 16.0, 10
+    last = {}
+
+    def round_trip():
+        a_mean, a_cov = ma.get()
+        b_mean, b_cov = mb.get()
+        last["host"] = numpy_locate(a_mean, a_cov, b_mean, b_cov, dmin, tol, gate, min_inliers)
+
+    def device():
+        last["dev"] = ma.locate(ba, mb, dmin, tol, gate, min_inliers, 3, capacity=16)
+    dev, d = timed(device)
+    loc = last["dev"]
+    if "--device-only" in sys.argv[1:]:                                 # a profiler's run: the device entry alone
+        print("%d objects against %d of them moved, counts %s: obvi_map_locate, 16 reported and refined %s" % (N_MAP, n_b, loc.counts, dev))
+        return
+    base, b = timed(round_trip)
+    counts, seed, inl, cost = last["host"]
+    print("%d objects against %d of them moved, %d seeds, %d compatible, %d hypotheses with >= %d inliers: obvi_map_get x 2 + numpy %s   obvi_map_locate, 16 reported and refined %s  (x %.0f)"
+          % ((N_MAP, n_b) + loc.counts + (min_inliers, base, dev, b / d)))
+    print("same counts: %s   same best seed: %s   inliers %d / %d   |cost - numpy's| / cost %.1e   located T %s (made with %s)   its sigmas %s"
+          % (counts == loc.counts, np.array_equal(seed, loc.seed[0]), loc.inliers[0], inl, abs(loc.cost[0] - cost) / cost, np.round(loc.transform[0], 4), T,
+             np.round(np.sqrt(np.diag(loc.transform_cov[0])), 5)))
+    peaks = ba.measure_peaks()
+    print("obvi_ba_measure_peaks: %d compute units at %.0f MHz -- %.1f TFLOP/s of fp64 vector FMAs at 128 FLOP a clock and compute unit; fp64 MFMA issue rate %.1f TFLOP/s"
+          % (peaks["compute_units"], peaks["clock_mhz"], 128e-6 * peaks["compute_units"] * peaks["clock_mhz"], peaks["mfma_f64_issue_tflops"]))
+    ba.close()
+    ma.close()
+    mb.close()
+
+
 def shared(n_sessions):
     """the map entries on handles that exchange shared objects."""
     import dist_util
@@ -454,4 +552,4 @@ if __name__ == "__main__":
     if "--shared" in sys.argv[1:]:
         shared(int(sys.argv[sys.argv.index("--shared") + 1]))
         sys.exit(0)
-    move() if "--move" in sys.argv[1:] else match() if "--match" in sys.argv[1:] else merge() if "--merge" in sys.argv[1:] else extend() if "--extend" in sys.argv[1:] else update() if "--update" in sys.argv[1:] else main()
+    locate() if "--locate" in sys.argv[1:] else move() if "--move" in sys.argv[1:] else match() if "--match" in sys.argv[1:] else merge() if "--merge" in sys.argv[1:] else extend() if "--extend" in sys.argv[1:] else update() if "--update" in sys.argv[1:] else main()
