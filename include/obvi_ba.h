@@ -344,7 +344,8 @@ int obvi_ba_debug_reduced_solve(obvi_ba_handle* h, double radius, const double* 
  * min(16, usable CPUs)) [15] usable CPUs of the process (affinity mask and cgroup quota) [16] LM steps that were re-run because a workgroup of the
  * fused level kernel of the tile Cholesky timed out waiting for its jobs [17] 1 while the handle is on the fused schedule
  * [18] wavefront pieces of k_point_pass [19] points of k_point_pass_long (tracks over 64 sightings) [20] observation pairs of k_schur_blocks (the pairs outside
- * the strips; [6] counts both kinds) [21] batches of all k_schur_window workgroups.  Returns the number of entries written. */
+ * the strips; [6] counts both kinds) [21] batches of all k_schur_window workgroups [22] tile columns per column group of the strips the plan was built for
+ * (5: the wide geometry, 3: the narrow one; 5 before the first plan).  Returns the number of entries written. */
 int obvi_ba_get_problem_stats(const obvi_ba_handle* h, double* out, int32_t cap);
 /* level 0 (default): no events; level 1: one HIP event pair per phase of an LM step (about 40 us of host and device time per
  * iteration: a dozen records and as many elapsed-time queries); level 2: additionally an event after every launch of the

@@ -26,6 +26,7 @@ Knobs read_knobs() {
   set_flag("OBVI_TAIL_SPATIAL", k.tail_spatial);
   set_int("OBVI_PAIR_BITMAP_MAX", k.pair_bitmap_max);
   set_int("OBVI_SCHUR_WGS", k.schur_wgs);
+  set_i64("OBVI_SCHUR_WIDE_BELOW", k.schur_wide_below);
   set_flag("OBVI_PLAN_SLOTS_ON_HOST", k.slots_on_host);
   set_int("OBVI_UPD_CHUNK", k.upd_chunk); k.upd_chunk = std::max(1, k.upd_chunk);
   set_int("OBVI_SLICE_MAX", k.slice_max);
@@ -660,12 +661,13 @@ int obvi_ba_get_problem_stats(const obvi_ba_handle* h, double* out, int32_t cap)
   int64_t act_rp = 0, act_bb = 0;
   for (uint8_t a : h->h_rp_active) act_rp += a != 0;
   for (uint8_t a : h->h_bb_active) act_bb += a != 0;
-  const double v[22] = {(double)h->nPv, (double)h->nOv, (double)h->nLv, (double)h->m_canon, (double)h->nt, (double)h->nblk, (double)(h->npairs + h->npairs_window),
+  const double v[23] = {(double)h->nPv, (double)h->nOv, (double)h->nLv, (double)h->m_canon, (double)h->nt, (double)h->nblk, (double)(h->npairs + h->npairs_window),
                         (double)h->ntiles, (double)h->n_trsm_jobs, (double)h->n_upd_products, h->chol_flops, (double)act_rp, (double)act_bb,
                         (double)h->nlevels, (double)h->knobs.host_threads, (double)usable_cpus(),
                         (double)h->potrf_wait_timeouts, h->fused_potrf ? 1.0 : 0.0,   // [16] LM steps re-run because a potrf workgroup of the fused level kernel timed out waiting for its jobs, [17] the fused schedule is still on
-                        (double)h->n_point_waves, (double)h->n_long_points, (double)h->npairs, (double)h->nbatches};   // [18..21] how the host cut the point pass and the Schur strips (obvi_ba.h)
-  const int n = std::min<int>(cap, 22);
+                        (double)h->n_point_waves, (double)h->n_long_points, (double)h->npairs, (double)h->nbatches,   // [18..21] how the host cut the point pass and the Schur strips (obvi_ba.h)
+                        (double)(h->schur_narrow ? SchurNarrow::kGroupCols : SchurWide::kGroupCols)};   // [22] the strip geometry of the plan
+  const int n = std::min<int>(cap, 23);
   for (int i = 0; i < n; ++i) out[i] = v[i];
   return n;
 }

@@ -381,15 +381,21 @@ void launch_schur_blocks(hipStream_t s, int64_t nblk, const uint32_t* blk_row, c
                          const ReducedDev& rd);
 // strip geometry of k_schur_window, shared with the host code that builds the visit lists and decides which pairs
 // the strip covers: row chunks of kSchurRows frames, columns = the kSchurWindowFrames frames ending with the chunk, cut
-// into groups of kSchurGroupCols 16-wide tile columns; visits are streamed through LDS in batches of at most
-// kSchurBatchVisits visits / kSchurBatchBytes of 144-byte slots
-constexpr int kSchurRows = 8, kSchurWindowFrames = 40, kSchurGroupCols = 5, kSchurBatchBytes = 32768, kSchurBatchVisits = 128;
+// into groups of Geom::kGroupCols 16-wide tile columns; visits are streamed through LDS in batches of at most
+// kSchurBatchVisits visits / Geom::kBatchBytes of 144-byte slots
+constexpr int kSchurRows = 8, kSchurWindowFrames = 40, kSchurBatchVisits = 128;
+// The two strip geometries (the plan is built for one of them and the handle remembers which: obvi_ba_handle::schur_narrow).  Wide: a wavefront's accumulator is
+// 3 x 5 tiles (120 registers), two wavefronts per SIMD; every deterministic handle, whose sums are partitioned by the (chunk, group) lists.  Narrow: 3 x 3 tiles
+// (72 registers) and 24 KB batches, three wavefronts per SIMD and three workgroups per CU.  The chunk's own frames (8 frames = 3 tile columns) are the last group
+// of either.  kVisitGroup: visits a wavefront takes together (all their LDS reads, then all their products).
+struct SchurWide { static constexpr int kGroupCols = 5, kBatchBytes = 32768, kVisitGroup = 2; };
+struct SchurNarrow { static constexpr int kGroupCols = 3, kBatchBytes = 24576, kVisitGroup = 2; };
 // the slot tables of the strip kernel, filled on the device (plan_kernels.hip): per visit the point, its tile bits of the (chunk, group) work list
 // (bit 15: two records per frame), the slot its image starts at inside its batch and the offset of its slots from the first slot of its workgroup
 struct PlanVisit { uint32_t l; uint16_t twin_bits; uint16_t base; uint32_t rel; };
-void launch_plan_visit_slots(hipStream_t s, int64_t nvis, const PlanVisit* pv, const uint32_t* wg_ptr, const uint32_t* wg_slot0, int32_t nwg, const int32_t* wg_f0, const int32_t* wg_group,
+void launch_plan_visit_slots(hipStream_t s, bool narrow, int64_t nvis, const PlanVisit* pv, const uint32_t* wg_ptr, const uint32_t* wg_slot0, int32_t nwg, const int32_t* wg_f0, const int32_t* wg_group,
                              const uint32_t* point_ptr, const uint8_t* rp_active, const uint32_t* rp_pose, const int32_t* frame_of_pose, uint32_t zero16, uint32_t* visits, uint32_t* slot_src);
-void launch_schur_window(hipStream_t s, int64_t nwg, int has_twins, const BlocksDev& b, const PointDev& pt, const ReducedDev& rd, const int32_t* row_of_nat,
+void launch_schur_window(hipStream_t s, bool narrow, int64_t nwg, int has_twins, const BlocksDev& b, const PointDev& pt, const ReducedDev& rd, const int32_t* row_of_nat,
                          const uint32_t* wg_bptr, const uint32_t* bfirst, const uint32_t* bslot, const uint32_t* visits, const uint32_t* slot_src,
                          const int32_t* wg_f0, const int32_t* wg_group);
 // point back-substitution and the candidate poses / objects (with the candidate's pose cache, both layouts of launch_pose_cache), one launch

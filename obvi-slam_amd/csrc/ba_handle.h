@@ -58,6 +58,7 @@ struct Knobs {
   bool tail_spatial = true;             // OBVI_TAIL_SPATIAL: the shared tail along a Hilbert curve over the objects
   int pair_bitmap_max = 8192;           // OBVI_PAIR_BITMAP_MAX: variable poses up to which the pose pairs go through a bitmap
   int schur_wgs = 1536;                 // OBVI_SCHUR_WGS: workgroups of the Schur strip kernel
+  int64_t schur_wide_below = 400000;    // OBVI_SCHUR_WIDE_BELOW: reprojection observations below which a default handle keeps the wide strip geometry (0: narrow everywhere; 1 << 62: wide everywhere, as deterministic handles always are).  Not a measured crossover: narrow wins at 3 M observations, the two tie at 49 k, nothing between was measured
   bool slots_on_host = false;           // OBVI_PLAN_SLOTS_ON_HOST: the host fills the strip kernel's slot tables
   int upd_chunk = 2;                    // OBVI_UPD_CHUNK: tile products per update job (at least 1)
   int slice_max = 512;                  // OBVI_SLICE_MAX: levels with at most this many tile jobs are row-sliced
@@ -219,6 +220,7 @@ struct obvi_ba_handle {
   DevBuf<uint32_t> d_batch_first, d_batch_slot, d_slot_src;
   DevBuf<PlanVisit> d_plan_visits; DevBuf<uint32_t> d_plan_wg_ptr, d_plan_wg_slot0; DevBuf<int32_t> d_plan_frame;   // inputs of the device-side slot fill (plan.cpp, plan_kernels.hip)
   int32_t schur_twins = 0;
+  bool schur_narrow = false;             // the strip geometry the plan was built for (ba_device.h: SchurNarrow / SchurWide; PlanBuilder::schur_batches decides)
   int64_t nchunks = 0, npairs_window = 0;
   DevBuf<int32_t> d_tiles, d_lvl_k, d_trsm_ik, d_upd_ij, d_upd_kptr, d_upd_k, d_rh_i, d_rh_kptr, d_rh_k, d_col_ptr, d_col_i, d_bw_kj, d_bw_chains;
   DevBuf<int32_t> d_row_ptr, d_row_j, d_cov_slab, d_cov_cols, d_cov_first;   // row structure of L; covariance extraction scratch

@@ -1124,28 +1124,30 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(6))
 // K4a.  Schur complement on the matrix cores, point-centric, no atomics inside the loop.
 // Geometry.  The variable frames (trajectory order) are cut into row chunks of kSR = 8 frames = 48 rows = 3 MFMA row
 // tiles.  The strip of a chunk is the 48 x 240 part of S whose columns are the kSFr = 40 frames [f0 - 32, f0 + 8):
-// 3 x 15 tiles of v_mfma_f64_16x16x4_f64, cut into 3 column groups of kSGC = 5 tile columns.  A point is "visited" by
+// 3 x 15 tiles of v_mfma_f64_16x16x4_f64, cut into column groups of kSGC = Geom::kGroupCols tile columns (ba_device.h: three groups of 5, SchurWide, or five
+// of 3, SchurNarrow; the plan is built for one of them).  A point is "visited" by
 // every (chunk, group) in which it has a row frame and a column frame; with Zrow(i) the 3-vector of matrix row i
 // (row 6 fo + x  <->  Z[obs at frame fo][x][0..2]) a visit adds
 //     strip(i, n) += sum_k Zrow(i)[k] * Zrow(n)[k]          (K = 3, padded to the instruction's 4)
 // for the tiles the point covers (wave-uniform bits of the host-built visit record).
 // Parallelism.  A workgroup owns a slice of the visits of one (chunk, group); each of its 4 wavefronts is an
-// independent stream with a private 3 x 5 tile accumulator in registers (120 VGPRs, two wavefronts per SIMD) and takes
-// every 4th visit.  Nothing in the loop depends on another wavefront, and nothing in it touches global memory:
+// independent stream with a private 3 x kSGC tile accumulator in registers and takes every 4th visit.  Wide: 120 of 214 VGPRs and 69 808 B of LDS, two
+// wavefronts per SIMD.  Narrow: 72 of 148 VGPRs and 53 424 B, three wavefronts per SIMD (three workgroups per CU) -- a point is visited by more, narrower
+// groups (more records, more row operand reads, more slots gathered), and the LDS round trips of a visit are covered by one more wavefront.
+// Nothing in the loop depends on another wavefront, and nothing in it touches global memory:
 // Memory.  The host lays a visit out as consecutive 144-byte slots -- the point's Z record for each strip frame from
 // its first to its last row frame and column frame of the group (zeros for a frame it skips), its (u_l, 0) tail, and
-// for a stereo point the second record of each frame -- and cuts a workgroup's visits into batches of <= 32 KB.  A
+// for a stereo point the second record of each frame -- and cuts a workgroup's visits into batches of <= Geom::kBatchBytes (32 KB / 24 KB).  A
 // batch is one gather (slot table entry -> global_load_lds_dwordx4, all 256 lanes) issued while the previous batch is
 // multiplied; the table entries of the batch after that ride in registers.  An operand is then a single ds_read_b64 at
 // (slot + fo - first) * 144 + 8 (3 x + (l>>4)), lanes without an operand read a zero.
 // The workgroup adds its tiles to the tile grid once, at the end: the four streams' accumulators are summed through LDS, then fp64
-// hardware atomics (15 tiles per workgroup).
+// hardware atomics (3 kSGC tiles per workgroup).
 // Pairs whose frames are further apart than the strip (loop closures, very long tracks) go to k_schur_blocks.
 // ---------------------------------------------------------------------------------------
 constexpr int kSR = kSchurRows, kSFr = kSchurWindowFrames, kSBack = kSFr - kSR;
-constexpr int kSTR = kSR * 6 / 16, kSTC = kSFr * 6 / 16, kSDiag = kSBack * 6 / 16, kSWv = 4, kSGC = kSchurGroupCols;
-static_assert(kSR * 6 % 16 == 0 && kSFr * 6 % 16 == 0 && kSBack * 6 % 16 == 0 && kSFr <= 64 && kSTC % kSGC == 0, "strip must be whole MFMA tiles");
-static_assert(kSchurBatchBytes % (16 * 64 * kSWv) == 0, "a batch is whole gather instructions");
+constexpr int kSTR = kSR * 6 / 16, kSTC = kSFr * 6 / 16, kSDiag = kSBack * 6 / 16, kSWv = 4;
+static_assert(kSR * 6 % 16 == 0 && kSFr * 6 % 16 == 0 && kSBack * 6 % 16 == 0 && kSFr <= 64, "strip must be whole MFMA tiles");
 typedef double sf64x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) const void schur_gptr;
 typedef __attribute__((address_space(3))) void schur_lptr;
@@ -1168,22 +1170,22 @@ __device__ __forceinline__ void mfma_f64_acc(sf64x4& acc, double a, double bv) {
   asm volatile("s_nop 1\n\tv_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(bv));
 }
 
-#ifndef OBVI_SCHUR_VISIT_GROUP
-#define OBVI_SCHUR_VISIT_GROUP 2
-#endif
-template <bool TWIN>
+template <bool TWIN, class Geom>
 __global__ void __launch_bounds__(64 * kSWv) k_schur_window(BlocksDev b, PointDev pt, ReducedDev rd, const int32_t* __restrict__ row_of_nat,
                                                           const uint32_t* __restrict__ wg_bptr, const uint32_t* __restrict__ bfirst,
                                                           const uint32_t* __restrict__ bslot, const uint4* __restrict__ visits,
                                                           const uint32_t* __restrict__ slot_src, const int32_t* __restrict__ wg_f0,
                                                           const int32_t* __restrict__ wg_group) {
+  constexpr int kSGC = Geom::kGroupCols, kBatchBytes = Geom::kBatchBytes;
+  static_assert(kSTC % kSGC == 0 && kSTC - kSGC <= kSDiag, "whole column groups; the chunk's own frames lie in the last one");
+  static_assert(kBatchBytes % (16 * 64 * kSWv) == 0, "a batch is whole gather instructions");
   // two batch buffers as separate objects, each addressed statically (the loop below is unrolled by two): the compiler then
   // knows that the reads of one do not alias the gather in flight into the other and does not wait for it
-  __shared__ __attribute__((aligned(16))) unsigned char zbuf0[kSchurBatchBytes], zbuf1[kSchurBatchBytes];
+  __shared__ __attribute__((aligned(16))) unsigned char zbuf0[kBatchBytes], zbuf1[kBatchBytes];
   __shared__ __attribute__((aligned(16))) uint4 recbuf0[kSchurBatchVisits], recbuf1[kSchurBatchVisits];
   __shared__ __attribute__((aligned(16))) double zero2[2];
   __shared__ int32_t rown[kSFr];
-  constexpr int kIters = kSchurBatchBytes / 16 / (64 * kSWv);   // gather instructions per lane per batch
+  constexpr int kIters = kBatchBytes / 16 / (64 * kSWv);   // gather instructions per lane per batch
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int m = lane & 15, kq = lane >> 4;
   const int32_t f0 = wg_f0[blockIdx.x], fbase = f0 - kSBack, cbase = kSGC * wg_group[blockIdx.x];
@@ -1239,10 +1241,10 @@ __global__ void __launch_bounds__(64 * kSWv) k_schur_window(BlocksDev b, PointDe
   };
 
   // ---- one visit.  Record: x = byte offset of strip frame 0 in the batch image for the row operands (int32), y = the same for the
-  //      group's column operands, z = tail slot | distance to the second layer << 16, w = column tiles of the group in use (5 bits) | stereo << 15 | row tiles in use << 16
+  //      group's column operands, z = tail slot | distance to the second layer << 16, w = column tiles of the group in use (kSGC bits) | stereo << 15 | row tiles in use << 16
   // A visit in two halves -- load_ops issues every LDS read of the visit (row operands, the operands of the active column tiles,
   // (u_l, 0)), multiply does the rest -- so that a wavefront can take its visits two at a time: both records, then both sets of
-  // operands, are read together and the read latency (exposed at two wavefronts per SIMD) is paid once per pair.
+  // operands, are read together and the read latency (exposed at two wavefronts per SIMD, and still at three: the narrow geometry measured 408-415 us with single visits against 388-395 in pairs) is paid once per pair.
   struct Ops { double a[kSTR]; double b[kSGC]; double ul; uint32_t bits; };
   auto load_ops = [&](const uint32_t vx, const uint32_t vy, const uint32_t vz, const uint32_t vw, auto which) -> Ops {
     constexpr int bf = decltype(which)::value;
@@ -1304,7 +1306,7 @@ __global__ void __launch_bounds__(64 * kSWv) k_schur_window(BlocksDev b, PointDe
       const uint4 rv = rb_[x];
       return load_ops(__builtin_amdgcn_readfirstlane(rv.x), __builtin_amdgcn_readfirstlane(rv.y), __builtin_amdgcn_readfirstlane(rv.z), __builtin_amdgcn_readfirstlane(rv.w), which);
     };
-    constexpr int kVisitGroup = OBVI_SCHUR_VISIT_GROUP;   // visits a wavefront takes together
+    constexpr int kVisitGroup = Geom::kVisitGroup;   // visits a wavefront takes together
     uint32_t i = (uint32_t)wv;
     for (; i + (kVisitGroup - 1) * kSWv < nv; i += kVisitGroup * kSWv) {
       Ops o[kVisitGroup];
@@ -1323,7 +1325,7 @@ __global__ void __launch_bounds__(64 * kSWv) k_schur_window(BlocksDev b, PointDe
   // ---- add the workgroup's tiles to the tile grid: tile (r, cbase + c), lane, register q -> row 16 r + kq + 4 q, column 16 (cbase + c) + m.
   //      The four wavefronts hold private accumulators of the same strip: they are summed through LDS first (the batch buffers are free),
   //      tile column by tile column, so that the strip costs one set of atomics instead of four.
-  static_assert(kSWv * kSTR * 4 * 64 * sizeof(double) <= kSchurBatchBytes && (kSTR * 4) % kSWv == 0, "one tile column of every wavefront fits a batch buffer");
+  static_assert(kSWv * kSTR * 4 * 64 * sizeof(double) <= kBatchBytes && (kSTR * 4) % kSWv == 0, "one tile column of every wavefront fits a batch buffer");
   double* red = reinterpret_cast<double*>(&zbuf0[0]);   // [wavefront][r][q][lane]
   __syncthreads();
 #pragma unroll
@@ -2238,13 +2240,15 @@ void launch_schur_blocks(hipStream_t s, int64_t nblk, const uint32_t* blk_row, c
                          const uint32_t* pair_a, const uint32_t* pair_b, const uint32_t* obs_point, const PointDev& pt, const ReducedDev& rd) {
   if (nblk > 0) hipLaunchKernelGGL(k_schur_blocks, dim3((unsigned)(8 * ((nblk + 7) / 8))), dim3(kBlock), 0, s, nblk, blk_row, blk_col, blk_ptr, pair_a, pair_b, obs_point, pt, rd);
 }
-void launch_schur_window(hipStream_t s, int64_t nwg, int has_twins, const BlocksDev& b, const PointDev& pt, const ReducedDev& rd, const int32_t* row_of_nat,
+void launch_schur_window(hipStream_t s, bool narrow, int64_t nwg, int has_twins, const BlocksDev& b, const PointDev& pt, const ReducedDev& rd, const int32_t* row_of_nat,
                          const uint32_t* wg_bptr, const uint32_t* bfirst, const uint32_t* bslot, const uint32_t* visits, const uint32_t* slot_src,
                          const int32_t* wg_f0, const int32_t* wg_group) {
   if (nwg <= 0) return;
   const uint4* v = reinterpret_cast<const uint4*>(visits);
-  if (has_twins) hipLaunchKernelGGL(k_schur_window<true>, dim3((unsigned)nwg), dim3(64 * kSWv), 0, s, b, pt, rd, row_of_nat, wg_bptr, bfirst, bslot, v, slot_src, wg_f0, wg_group);
-  else hipLaunchKernelGGL(k_schur_window<false>, dim3((unsigned)nwg), dim3(64 * kSWv), 0, s, b, pt, rd, row_of_nat, wg_bptr, bfirst, bslot, v, slot_src, wg_f0, wg_group);
+#define OBVI_STRIPS(TWIN, GEOM) hipLaunchKernelGGL((k_schur_window<TWIN, GEOM>), dim3((unsigned)nwg), dim3(64 * kSWv), 0, s, b, pt, rd, row_of_nat, wg_bptr, bfirst, bslot, v, slot_src, wg_f0, wg_group)
+  if (narrow) { if (has_twins) OBVI_STRIPS(true, SchurNarrow); else OBVI_STRIPS(false, SchurNarrow); }
+  else { if (has_twins) OBVI_STRIPS(true, SchurWide); else OBVI_STRIPS(false, SchurWide); }
+#undef OBVI_STRIPS
 }
 void launch_backsub_apply(hipStream_t s, const BlocksDev& b, const ReprojDev& rp, const PointDev& pt, const ReducedDev& rd, const double* points,
                           double* points_cand, const double* poses, const double* objects, double* poses_cand, double* objects_cand, PoseCache* pc_cand, double* scal,

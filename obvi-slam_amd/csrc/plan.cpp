@@ -430,9 +430,18 @@ struct PlanBuilder {
       });
   }
 
+  // The strip geometry of this plan (ba_device.h).  Deterministic handles are always wide: their sums are partitioned by the (chunk, group) lists, and another
+  // width is another partition, hence other bits.  Default handles take the narrow geometry from Knobs::schur_wide_below reprojection observations on.
   void schur_batches() {
+    h->schur_narrow = !h->deterministic && h->n_rp >= h->knobs.schur_wide_below;
+    if (h->schur_narrow) schur_batches_of<SchurNarrow>(); else schur_batches_of<SchurWide>();
+  }
+  template <class Geom>
+  void schur_batches_of() {
     // one work list per (chunk, column group): the visits with a tile in that group
-    constexpr int kGroups = (kSchurWindowFrames * 6 / 16) / kSchurGroupCols, kGroupBits = 3 * kSchurGroupCols;
+    constexpr int kGroupCols = Geom::kGroupCols;
+    constexpr int kGroups = (kSchurWindowFrames * 6 / 16) / kGroupCols, kGroupBits = 3 * kGroupCols;
+    static_assert(kGroupBits <= 15, "PlanVisit::twin_bits: the group's tile bits below the stereo flag");
     struct GVisit { int32_t chunk, group; uint32_t l, beg, k; bool twin; uint32_t bits; };
     std::vector<GVisit> gv;   // the visits per (chunk, column group) work list
     {
@@ -479,7 +488,7 @@ struct PlanBuilder {
     wg_bptr.assign(1, 0); bfirst.assign(1, 0); bslot.assign(1, 0); visits.clear(); slot_src.clear();
     wg_f0.clear(); wg_group.clear();
 
-    constexpr uint32_t kBatchSlots = kSchurBatchBytes / 144;
+    constexpr uint32_t kBatchSlots = Geom::kBatchBytes / 144;
     auto visit_slots = [&](const GVisit& v, uint32_t base, std::vector<uint32_t>& out, uint32_t* rec) {
       // The image of a visit covers every strip frame that an ACTIVE tile of the visit touches -- row tiles that hold one of the point's
       // row frames, column tiles of the group that hold one of its column frames -- with the zero page for the frames the point does not
@@ -488,11 +497,11 @@ struct PlanBuilder {
       constexpr int kRowTile0 = SBACK * 6 / 16;
       uint32_t rows = 0;
       int32_t A0 = INT32_MAX, A1 = -1, B0 = INT32_MAX, B1 = -1;
-      for (int c = 0; c < kSchurGroupCols; ++c) {
+      for (int c = 0; c < kGroupCols; ++c) {
         const uint32_t t3 = (v.bits >> (3 * c)) & 7u;
         if (!t3) continue;
         rows |= t3;
-        const int t = kSchurGroupCols * v.group + c;
+        const int t = kGroupCols * v.group + c;
         B0 = std::min<int32_t>(B0, (16 * t) / 6); B1 = std::max<int32_t>(B1, (16 * t + 15) / 6);
       }
       for (int r = 0; r < 3; ++r)
@@ -533,9 +542,9 @@ struct PlanBuilder {
       rec[1] = (uint32_t)(144 * slotB0);                                  // ... column operands
       rec[2] = tail | (layer << 16);
       uint32_t cols = 0;
-      for (int c = 0; c < kSchurGroupCols; ++c) if ((v.bits >> (3 * c)) & 7u) cols |= 1u << c;
+      for (int c = 0; c < kGroupCols; ++c) if ((v.bits >> (3 * c)) & 7u) cols |= 1u << c;
       // the visit's tiles are (row tiles in use) x (column tiles in use), minus the tiles above the diagonal in the chunk's own group (a cut
-      // the kernel knows at compile time): two masks instead of 15 tile bits
+      // the kernel knows at compile time): two masks instead of 3 kGroupCols tile bits
       rec[3] = cols | (v.twin ? 1u << 15 : 0u) | (rows << 16);
     };
     // the workgroups (slices of the work lists) are independent: ranges of them on host threads, joined in order
@@ -556,11 +565,11 @@ struct PlanBuilder {
       constexpr int kRowTile0 = SBACK * 6 / 16;
       uint32_t rows = 0;
       int32_t A0 = INT32_MAX, A1 = -1, B0 = INT32_MAX, B1 = -1;
-      for (int c = 0; c < kSchurGroupCols; ++c) {
+      for (int c = 0; c < kGroupCols; ++c) {
         const uint32_t t3 = (v.bits >> (3 * c)) & 7u;
         if (!t3) continue;
         rows |= t3;
-        const int t = kSchurGroupCols * v.group + c;
+        const int t = kGroupCols * v.group + c;
         B0 = std::min<int32_t>(B0, (16 * t) / 6); B1 = std::max<int32_t>(B1, (16 * t + 15) / 6);
       }
       for (int r = 0; r < 3; ++r)
@@ -617,7 +626,7 @@ struct PlanBuilder {
     h->npairs_window = n_window_pairs;
 
     if (stage_times)
-      std::fprintf(stderr, "  schur plan: %zu visits, %zu workgroups, %zu batches (%.1f slots each), %zu slots = %.1f MB gathered per launch\n", gv.size(), wgs.size(), bslot.size() - 1,
+      std::fprintf(stderr, "  schur plan (%d tile columns per group): %zu visits, %zu workgroups, %zu batches (%.1f slots each), %zu slots = %.1f MB gathered per launch\n", kGroupCols, gv.size(), wgs.size(), bslot.size() - 1,
                    (double)total_slots / std::max<size_t>(1, bslot.size() - 1), total_slots, 144e-6 * (double)total_slots);
   }
 
@@ -908,7 +917,7 @@ struct PlanBuilder {
       for (int64_t pz = 0; pz < P; ++pz) if (pose_vid[pz] >= 0) frame_of_pose[pz] = nat[pz];
       h->d_plan_frame.upload(frame_of_pose, s); h->d_plan_visits.upload(plan_visits, s); h->d_plan_wg_ptr.upload(plan_wg_ptr, s); h->d_plan_wg_slot0.upload(plan_wg_slot0, s);
       h->d_chunk_points.resize(4 * plan_visits.size() + 4); h->d_slot_src.resize(total_slots + 4);
-      launch_plan_visit_slots(s, (int64_t)plan_visits.size(), h->d_plan_visits.get(), h->d_plan_wg_ptr.get(), h->d_plan_wg_slot0.get(), (int32_t)plan_wg_ptr.size(), h->d_chunk_f0.get(), h->d_chunk_group.get(),
+      launch_plan_visit_slots(s, h->schur_narrow, (int64_t)plan_visits.size(), h->d_plan_visits.get(), h->d_plan_wg_ptr.get(), h->d_plan_wg_slot0.get(), (int32_t)plan_wg_ptr.size(), h->d_chunk_f0.get(), h->d_chunk_group.get(),
                               h->d_point_ptr.get(), h->d_rp_active.get(), h->d_rp_pose.get(), h->d_plan_frame.get(), zero16, h->d_chunk_points.get(), h->d_slot_src.get());
       // (the kernel's inputs went through the pinned arena, or -- too big for it -- straight from vectors of this function: finish_upload() at its end waits then)
     }

@@ -2,7 +2,7 @@
 //
 // k_schur_window gathers, per visit (point x row chunk x column group), the point's Z records of every strip frame an active tile touches into
 // LDS: the plan holds, per visit, four words (where the row / column operands start in the batch image, the tail slot, tile masks) and, per slot,
-// the source of its 144 bytes.  Config #3: 0.8 M visits, 8.65 M slots.  Until round 4 the host filled both tables (a walk over every visit's
+// the source of its 144 bytes.  Config #3: 0.8 M visits, 8.65 M slots (wide strip geometry; narrow: 1.09 M, 10.5 M).  Until round 4 the host filled both tables (a walk over every visit's
 // observations: 95 ms on one thread, 26 ms on sixteen) and uploaded 48 MB; the walk is the same for every visit and independent of the others
 // once the host has dealt the visits to batches (sizes depend on a visit's tile bits alone), so it runs here: one lane per visit.
 // Same arithmetic, same order as plan.cpp's host version (OBVI_PLAN_SLOTS_ON_HOST=1), which stays as the check.
@@ -17,10 +17,12 @@ namespace {
 
 constexpr int W = kSchurWindowFrames, SR = kSchurRows, SBACK = W - SR, kRowTile0 = SBACK * 6 / 16;
 
+template <class Geom>
 __global__ void __launch_bounds__(256) k_plan_visit_slots(int64_t nvis, const PlanVisit* __restrict__ pv, const uint32_t* __restrict__ wg_ptr, const uint32_t* __restrict__ wg_slot0, int32_t nwg,
                                                          const int32_t* __restrict__ wg_f0, const int32_t* __restrict__ wg_group, const uint32_t* __restrict__ point_ptr,
                                                          const uint8_t* __restrict__ rp_active, const uint32_t* __restrict__ rp_pose, const int32_t* __restrict__ frame_of_pose,
                                                          uint32_t zero16, uint32_t* __restrict__ visits, uint32_t* __restrict__ slot_src) {
+  constexpr int kGroupCols = Geom::kGroupCols;
   const int64_t t = blockIdx.x * (int64_t)256 + threadIdx.x;
   if (t >= nvis) return;
   // the workgroup (slice of a (chunk, group) work list) the visit belongs to: the last g with wg_ptr[g] <= t
@@ -34,11 +36,11 @@ __global__ void __launch_bounds__(256) k_plan_visit_slots(int64_t nvis, const Pl
   uint32_t rows = 0, cols = 0;
   int32_t A0 = INT32_MAX, A1 = -1, B0 = INT32_MAX, B1 = -1;
 #pragma unroll
-  for (int c = 0; c < kSchurGroupCols; ++c) {
+  for (int c = 0; c < kGroupCols; ++c) {
     const uint32_t t3 = (bits >> (3 * c)) & 7u;
     if (!t3) continue;
     rows |= t3; cols |= 1u << c;
-    const int tc = kSchurGroupCols * group + c;
+    const int tc = kGroupCols * group + c;
     B0 = min(B0, (16 * tc) / 6); B1 = max(B1, (16 * tc + 15) / 6);
   }
 #pragma unroll
@@ -90,10 +92,12 @@ __global__ void __launch_bounds__(256) k_plan_visit_slots(int64_t nvis, const Pl
 
 }  // namespace
 
-void launch_plan_visit_slots(hipStream_t s, int64_t nvis, const PlanVisit* pv, const uint32_t* wg_ptr, const uint32_t* wg_slot0, int32_t nwg, const int32_t* wg_f0, const int32_t* wg_group,
+void launch_plan_visit_slots(hipStream_t s, bool narrow, int64_t nvis, const PlanVisit* pv, const uint32_t* wg_ptr, const uint32_t* wg_slot0, int32_t nwg, const int32_t* wg_f0, const int32_t* wg_group,
                              const uint32_t* point_ptr, const uint8_t* rp_active, const uint32_t* rp_pose, const int32_t* frame_of_pose, uint32_t zero16, uint32_t* visits, uint32_t* slot_src) {
-  if (nvis > 0) hipLaunchKernelGGL(k_plan_visit_slots, dim3((unsigned)((nvis + 255) / 256)), dim3(256), 0, s, nvis, pv, wg_ptr, wg_slot0, nwg, wg_f0, wg_group, point_ptr, rp_active, rp_pose,
-                                   frame_of_pose, zero16, visits, slot_src);
+  if (nvis <= 0) return;
+  const dim3 grid((unsigned)((nvis + 255) / 256));
+  if (narrow) hipLaunchKernelGGL(k_plan_visit_slots<SchurNarrow>, grid, dim3(256), 0, s, nvis, pv, wg_ptr, wg_slot0, nwg, wg_f0, wg_group, point_ptr, rp_active, rp_pose, frame_of_pose, zero16, visits, slot_src);
+  else hipLaunchKernelGGL(k_plan_visit_slots<SchurWide>, grid, dim3(256), 0, s, nvis, pv, wg_ptr, wg_slot0, nwg, wg_f0, wg_group, point_ptr, rp_active, rp_pose, frame_of_pose, zero16, visits, slot_src);
 }
 
 }  // namespace obvi

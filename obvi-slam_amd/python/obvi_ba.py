@@ -908,11 +908,11 @@ class BundleAdjuster:
         return rc, lhs.ravel()[:mm * mm].reshape(mm, mm).copy(), rhs[:mm].copy(), y[:mm].copy(), row[:mm].copy()
 
     def problem_stats(self):
-        buf = (C.c_double * 22)()
-        n = self._fn("ba_get_problem_stats")(self._h, buf, C.c_int32(22))
+        buf = (C.c_double * 23)()
+        n = self._fn("ba_get_problem_stats")(self._h, buf, C.c_int32(23))
         names = ["poses_var", "objects_var", "points_var", "reduced_rows", "tiles_per_dim", "schur_blocks", "schur_pairs",
                  "tiles_nonzero", "trsm_jobs", "update_jobs", "chol_flops", "reproj_active", "bbox_active", "chol_levels", "host_threads", "usable_cpus",
-                 "potrf_wait_timeouts", "fused_potrf", "point_pieces", "long_points", "schur_pairs_blocks", "schur_batches"]
+                 "potrf_wait_timeouts", "fused_potrf", "point_pieces", "long_points", "schur_pairs_blocks", "schur_batches", "schur_group_cols"]
         return {names[i]: buf[i] for i in range(n)}
 
     def set_profiling(self, level):

@@ -16,17 +16,18 @@ cd /tmp && export TMPDIR=/tmp
 # (the legs of the default command that are not the timed workload -- CPU baseline, deterministic-mode comparison, end-to-end two-phase run -- are
 #  switched off under the profiler, so that a kernel's average is over the launches of the timed configuration only)
 LEGS="--full --no-cpu-baseline --no-deterministic-leg --no-end-to-end"
-rm -rf /tmp/pr_trace; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pr_trace -o cfg3 -- python $R/bench.py $LEGS > $OUT/${TAG}_bench_cfg3_under_rocprof.json 2> $OUT/rocprof.err
+# (every GPU step under its own time limit; a step that fails, faults or runs into its limit ends the script: nothing more is started on that card)
+rm -rf /tmp/pr_trace; timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pr_trace -o cfg3 -- python $R/bench.py $LEGS > $OUT/${TAG}_bench_cfg3_under_rocprof.json 2> $OUT/rocprof.err || exit $?
 cp $(find /tmp/pr_trace -name "*kernel_stats.csv" | head -1) $OUT/${TAG}_kernel_stats_cfg3.csv
 for C in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pr_$C
-  timeout 600 rocprofv3 --pmc $C --output-format csv -d /tmp/pr_$C -o cfg3 -- python $R/bench.py --steps 4 --warmup 1 $LEGS > /dev/null 2> $OUT/pmc_$C.err
+  timeout -k 10 600 rocprofv3 --pmc $C --output-format csv -d /tmp/pr_$C -o cfg3 -- python $R/bench.py --steps 4 --warmup 1 $LEGS > /dev/null 2> $OUT/pmc_$C.err || exit $?
 done
 F=$(find /tmp/pr_FETCH_SIZE -name "*counter_collection.csv" | head -1); W=$(find /tmp/pr_WRITE_SIZE -name "*counter_collection.csv" | head -1)
 python3 $R/scripts/pmc_summary.py "$F" "$W" $OUT/${TAG}_pmc_traffic.json > $OUT/${TAG}_pmc_traffic_cfg3.txt
 rm -rf /tmp/pr_sq
-timeout 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE \
-  --output-format csv -d /tmp/pr_sq -o cfg3 -- python $R/bench.py --steps 4 --warmup 1 $LEGS > /dev/null 2> $OUT/pmc_sq.err
+timeout -k 10 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE \
+  --output-format csv -d /tmp/pr_sq -o cfg3 -- python $R/bench.py --steps 4 --warmup 1 $LEGS > /dev/null 2> $OUT/pmc_sq.err || exit $?
 python3 - "$(find /tmp/pr_sq -name '*counter_collection.csv' | head -1)" $OUT/${TAG}_sq_counters.json <<'PY'
 import collections, csv, json, re, sys
 tot = collections.defaultdict(lambda: collections.defaultdict(float)); n = collections.defaultdict(lambda: collections.defaultdict(int))
@@ -66,7 +67,7 @@ json.dump({"tag": tag, "kernel_source_sha": sha, "files": {"bench": tag + "_benc
           open(os.path.join(out, "manifest.json"), "w"), indent=1)
 PY
 cp $OUT/manifest.json $OUT/${TAG}_kernel_stats_cfg3.csv $OUT/${TAG}_pmc_traffic.json $OUT/${TAG}_sq_counters.json $R/profiles/ 2>/dev/null
-timeout 900 python $R/bench.py --full > $OUT/${TAG}_bench_cfg3.json 2> $OUT/bench.err
+timeout -k 10 900 python $R/bench.py --full > $OUT/${TAG}_bench_cfg3.json 2> $OUT/bench.err || exit $?
 python3 - $OUT $TAG $SHA <<'PY'
 import json, os, subprocess, sys
 out, tag, sha = sys.argv[1:4]
