@@ -8,8 +8,8 @@
 //                             src/refactoring/visual_feature_processing/orb_output_low_level_feature_reader.cpp:25-236, include/file_io/features_ests_with_id_io.h:14-62
 // Rules of that reader kept here: a later sighting of the same (feature, frame, camera) replaces the earlier one (:184-186); frames behind the limit of
 // LimitTrajectoryEvaluationParams are skipped (:48-53); a feature seen in ONE frame only is dropped (:66-70); a feature without an initial position is dropped (:73-79).
-// Bounding boxes (--bounding_boxes_by_node_id_file) need the data-association front end, which is out of scope: sessions from these files are visual-feature
-// sessions (BASELINE config #1's shape), optionally on top of a long-term map.
+// Bounding boxes (--bounding_boxes_by_node_id_file): the data association exists (include/obvi_bbox_frontend.h on the device, obvi_bounding_box_front_end.h around it); what
+// remains is the reader of the box file, so sessions from these files are still visual-feature sessions (BASELINE config #1's shape), optionally on top of a long-term map.
 #ifndef OBVI_HOST_REFERENCE_INPUTS_IO_H_
 #define OBVI_HOST_REFERENCE_INPUTS_IO_H_
 

@@ -84,6 +84,14 @@ class ParallaxParams(C.Structure):
         super().__init__(min_pixel, min_transl, min_orient, int(enforce_pixel), int(enforce_pose))
 
 
+class BboxFrontendParams(C.Structure):
+    """obvi_bbox_frontend_params (include/obvi_bbox_frontend.h); defaults: FeatureBasedBbAssociationParams."""
+    _fields_ = [("bounding_box_inflation_size", C.c_double), ("min_overlapping_features_for_match", C.c_double)]
+
+    def __init__(self, inflation=0.0, min_overlap=2.0):
+        super().__init__(inflation, min_overlap)
+
+
 class LocateParams(C.Structure):
     """obvi_map_locate_params (include/obvi_map_locate.h)."""
     _fields_ = [("pair_min_distance", C.c_double), ("pair_tolerance", C.c_double), ("inlier_gate", C.c_double), ("min_inliers", C.c_int32), ("refine_iterations", C.c_int32)]
@@ -407,6 +415,27 @@ def map_match_resolve(od, a, b, stat, max_pairs=None, library=None, prefix="obvi
     if rc != 0:
         raise ObviError("%smap_match_resolve failed: status %d" % (prefix, rc))
     return drop[:q.value], keep[:q.value], sel[:q.value]
+
+
+def bbox_assign(is_match, score, n_pending, library=None, prefix="obvi_"):
+    """(assigned, is_new) of the boxes of one round (BundleAdjuster.bbox_associate): the matches taken greedily by descending score, ties by box then candidate
+    index; a box left over opens a new pending object numbered from n_pending upwards.  Host only: no handle, no device."""
+    path = library or default_library_path()
+    if not os.path.exists(path):
+        raise ObviError("%s not found: build it with __graft_entry__.build() -- there is no CPU fallback" % path)
+    try:
+        f = getattr(C.CDLL(path), prefix + "bbox_frontend_assign")
+    except AttributeError:
+        raise ObviError("%sbbox_frontend_assign: this library cannot associate bounding boxes (include/obvi_bbox_frontend.h is served by libobvi_ba.so only)" % prefix)
+    f.restype = C.c_int
+    m, sc = np.ascontiguousarray(is_match, dtype=np.uint8), _f64(score)
+    if m.ndim != 2 or m.shape != sc.shape:
+        raise ObviError("bbox_assign: is_match and score must be [n_box][n_cand] both")
+    assigned, is_new = np.zeros(m.shape[0], np.int64), np.zeros(m.shape[0], np.uint8)
+    rc = f(C.c_int64(m.shape[0]), C.c_int64(m.shape[1]), C.c_int64(int(n_pending)), _ptr(m, C.c_uint8), _ptr(sc, C.c_double), _ptr(assigned, C.c_int64), _ptr(is_new, C.c_uint8))
+    if rc != 0:
+        raise ObviError("%sbbox_frontend_assign failed: status %d" % (prefix, rc))
+    return assigned, is_new
 
 
 class BundleAdjuster:
@@ -780,6 +809,26 @@ class BundleAdjuster:
         self._check(self._frontend_fn("frontend_parallax")(self._h, C.c_int64(len(fp) - 1), _ptr(fp, C.c_uint64), _ptr(hp, C.c_uint8), _ptr(po, C.c_double), _ptr(op, C.c_uint64),
                                                           _ptr(px, C.c_double), C.byref(prm), _ptr(out, C.c_uint8)), "frontend_parallax")
         return out
+
+    # ---- bounding-box data association (include/obvi_bbox_frontend.h) ---------------------------
+    def bbox_associate(self, feat_id, feat_pixel, box_corners, box_label, cand_label, view_ptr, feat_ptr, view_feat, params=None):
+        """One (frame, camera) round up to the assignment: (in_box [n_box][n_feat], feats_in_box [n_box], overlap [n_box][n_views], is_match [n_box][n_cand],
+        score [n_box][n_cand]); score is NaN where is_match is 0 (the library writes it only where there is a match)."""
+        fi = np.ascontiguousarray(feat_id, dtype=np.uint64).ravel(); fx = _f64(feat_pixel, (-1, 2))
+        bc = _f64(box_corners, (-1, 4)); bl = np.ascontiguousarray(box_label, dtype=np.int32).ravel(); cl = np.ascontiguousarray(cand_label, dtype=np.int32).ravel()
+        vp = np.ascontiguousarray(view_ptr, dtype=np.uint64).ravel(); fp = np.ascontiguousarray(feat_ptr, dtype=np.uint64).ravel()
+        vf = np.ascontiguousarray(view_feat, dtype=np.uint64).ravel()
+        if len(fx) != len(fi) or len(bl) != len(bc) or len(vp) != len(cl) + 1 or len(fp) < 1:
+            raise ObviError("bbox_associate: array lengths disagree")
+        prm = params or BboxFrontendParams()
+        nf, nb, nc, nv = len(fi), len(bc), len(cl), len(fp) - 1
+        in_box, count, overlap = np.zeros((nb, nf), np.uint8), np.zeros(nb, np.uint32), np.zeros((nb, nv), np.uint32)
+        match, score = np.zeros((nb, nc), np.uint8), np.full((nb, nc), np.nan)
+        self._check(self._frontend_fn("bbox_frontend_associate")(self._h, C.c_int64(nf), _ptr(fi, C.c_uint64), _ptr(fx, C.c_double), C.c_int64(nb), _ptr(bc, C.c_double), _ptr(bl, C.c_int32),
+                                                                C.c_int64(nc), _ptr(cl, C.c_int32), C.c_int64(nv), _ptr(vp, C.c_uint64), C.c_int64(len(vf)), _ptr(fp, C.c_uint64),
+                                                                _ptr(vf, C.c_uint64), C.byref(prm), _ptr(in_box, C.c_uint8), _ptr(count, C.c_uint32), _ptr(overlap, C.c_uint32),
+                                                                _ptr(match, C.c_uint8), _ptr(score, C.c_double)), "bbox_frontend_associate")
+        return in_box, count, overlap, match, score
 
     # ---- state ---------------------------------------------------------------------------
     def reset(self):
