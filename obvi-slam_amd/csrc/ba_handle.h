@@ -7,7 +7,8 @@
 //   lm.cpp      one LM step on the device (submit_step: assemble, factor, trial point, publish and wait) and the trust-region loop (obvi_ba_solve)
 //   map_resident.cpp, map_update.cpp, map_extend.cpp   the device-resident map (struct obvi_map): group priors cut from it, the map conditioned on a window's
 //                      posterior, and the map grown by a window's new objects or gathered (what the last two share: map_window.h)
-//   map_merge.cpp, map_match.cpp   duplicate objects of the map fused, and proposed (with the host-only resolver between the two)
+//   map_merge.cpp, map_match.cpp   duplicate objects of the map fused, and proposed (with the host-only resolver between the two); these two, map_frame.cpp and
+//                      map_locate.cpp keep their device arrays for one call only, in d_map_ws (map_window.h: carve_workspace)
 //   map_frame.cpp  the map moved into another frame under an uncertain transform; two maps joined
 //   map_locate.cpp one map located in another from the constellations of their object centres: the transform the move takes
 #ifndef OBVI_BA_HANDLE_H_
@@ -199,15 +200,8 @@ struct obvi_ba_handle {
   DevBuf<double> d_mc_A, d_mc_Li, d_mc_Wt, d_mc_Csym, d_mc_x, d_mc_partial, d_mc_status;
   // obvi_map_condition* / obvi_map_extend* (map_update.cpp, map_extend.cpp): the posterior as uploaded or laid out (covariance, then mean), the window's session objects, the tile operands of MapUpdateDev
   DevBuf<double> d_mu_post, d_mu_tiles; DevBuf<uint32_t> d_mu_obj;
-  // obvi_map_merge (map_merge.cpp): the pairs' survivors and the new map's objects, the offsets followed by the noise blocks, the tile operands of MapMergeDev
-  DevBuf<uint32_t> d_mm_keep, d_mm_kept; DevBuf<double> d_mm_in, d_mm_tiles;
-  // obvi_map_match (map_match.cpp): the labels, the compacted diagonal blocks, the [n][n] statistics, the rows' counts, offsets and the totals, the reported pairs (a, then b; stat, then yaw offset); empty until the first call
-  DevBuf<int32_t> d_mt_label; DevBuf<double> d_mt_diag, d_mt_stat, d_mt_out; DevBuf<int64_t> d_mt_cnt; DevBuf<uint32_t> d_mt_idx;
-  // obvi_map_transform (map_frame.cpp): the objects' Jk, G and G Sigma_s of MapFrameDev, one after the other; empty until the first call
-  DevBuf<double> d_mf_jac;
-  // obvi_map_locate (map_locate.cpp): the labels of both maps and the objects' records; the rows' and blocks' counts, offsets and the totals; the compatible seeds with their inliers and costs; the qualifying
-  // and the reported hypotheses; what is reported (doubles: transform, covariance, cost; ints: seed, inliers, partners); empty until the first call
-  DevBuf<int32_t> d_ml_label, d_ml_lab, d_ml_inl, d_ml_iout; DevBuf<double> d_ml_rec, d_ml_cost, d_ml_dout; DevBuf<int64_t> d_ml_cnt; DevBuf<uint32_t> d_ml_seeds, d_ml_list;
+  // the workspace of the entries whose device arrays live for one call (merge, match, transform, locate): carved anew by each (map_window.h: carve_workspace); empty until the first call
+  DevBuf<char> d_map_ws;
   DevBuf<double> d_bb_blk;                                    // per-factor blocks of the bounding-box factors (k_bbox_gather)
   DevBuf<double> d_sm_blk; DevBuf<uint32_t> d_smt_ptr, d_smt_idx;   // deterministic mode: the same for the priors and relative-pose factors (k_small_gather)
   int32_t bb_pairs_unique = 1;

@@ -19,7 +19,6 @@ int obvi_map_transform(obvi_ba_handle* h, const obvi_map* map, const double* tra
   hipStream_t s = h->stream;
   const int64_t n = map->n;
   const MapCutDev m = window_cut(h, 0, nullptr);   // the status record alone, zeroed
-  h->d_mf_jac.resize((size_t)(n * K * (K + 2 * dT)));
   std::unique_ptr<obvi_map, MapDeleter> fresh = allocate_map(map->device, od, n);
   inherit_power_start(fresh.get(), map, s);
   MapFrameDev f{};
@@ -27,7 +26,8 @@ int obvi_map_transform(obvi_ba_handle* h, const obvi_map* map, const double* tra
   std::copy(transform, transform + dT, f.transform);
   if (transform_cov) for (int i = 0; i < dT; ++i) for (int j = 0; j < dT; ++j) f.sigma[i * dT + j] = 0.5 * (transform_cov[i * dT + j] + transform_cov[j * dT + i]);
   f.map_mean = map->d_mean; f.map_cov = map->d_cov;
-  f.J = h->d_mf_jac.get(); f.G = f.J + n * K * K; f.GS = f.G + n * K * dT;
+  // k_mf_jac writes J of every object, and G and GS when there is a Sigma_s: they are read only then
+  carve_workspace(h, [&](Carver& c) { f.J = c.take<double>(n * K * K); f.G = c.take<double>(n * K * dT); f.GS = c.take<double>(n * K * dT); });
   f.out_mean = fresh->d_mean; f.out_cov = fresh->d_cov; f.status = m.status;
   launch_map_transform(s, f);
   { const int rc = finish_window_call(h, false, "", "map_transform: a non-finite entry in the new map"); if (rc != OBVI_OK) return rc; }

@@ -13,12 +13,13 @@
 // map, plus the cross block; the condition IS the extension by no object, and both end in the scatter of the window's whole block); duplicate objects of the
 // map merged (include/obvi_map_merge.h: the innovation covariance of the pairs built in a one-group cut and factored as any cut, the gain tiles of the
 // surviving rows alone, then the downdate through the survivors' row table with Z = Y, sign -, straight into the smaller map).  Every read of a symmetrised
-// entry of a map or a posterior goes through stage_sym / sym_at.  Last part: duplicate objects of the map proposed
-// (include/obvi_map_match.h): every pair's difference in units of its own covariance, one lane per pair, and the pairs within the gate compacted in (a, b) order
-// by counts and a scan.
+// entry of a map or a posterior goes through stage_sym / sym_at.  Then the ordered compaction the two report entries share -- compact_counts (a workgroup's
+// counts per thread to its sums), compact_scan (one workgroup: the exclusive scan of a strided count array, and its total), compact_place (a workgroup's hits to
+// their places, by ballot) -- and its first user: duplicate objects of the map proposed (include/obvi_map_match.h): every pair's difference in units of its own
+// covariance, one lane per pair, and the pairs within the gate compacted in (a, b) order.
 // After it: the map moved into another frame under an uncertain transform, object-aligned block pair by block pair, and two maps joined
 // (include/obvi_map_frame.h).  Last: one map located in another from the constellations of their object centres (include/obvi_map_locate.h): compatible
-// seeds counted, scanned and scattered; every hypothesis scored with both maps' centres and centre blocks in local memory; the qualifying ones ranked by
+// seeds counted, scanned and scattered by the same three helpers, as the qualifying hypotheses are; every hypothesis scored with both maps' centres and centre blocks in local memory; the qualifying ones ranked by
 // counting; the reported ones refined, one wavefront each.
 #include "chol_tile.h"
 
@@ -707,6 +708,55 @@ __global__ void __launch_bounds__(kThreads) k_mm_gather(MapMergeDev g) {
   for (int x = 0; x < T * T / kThreads; ++x) gt[tid + kThreads * x] = t[x];
 }
 
+// ==== the ordered compaction of the two report entries below: counts per row (or block), one scan, placement ===============================================
+// The match compacts its found pairs, the locate its compatible seeds and its qualifying hypotheses, all three through these.
+
+// a workgroup's K counts per thread -> its K sums at out[0 .. K); part: [K][kThreads / 64] in local memory
+template <int K>
+__device__ __forceinline__ void compact_counts(int32_t (&c)[K], int32_t (*part)[kThreads / 64], int64_t* out) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+#pragma unroll
+    for (int x = 32; x >= 1; x >>= 1) c[i] += __shfl_xor(c[i], x, 64);
+    if ((tid & 63) == 0) part[i][tid >> 6] = c[i];
+  }
+  __syncthreads();
+  if (tid < K) { int64_t sum = 0; for (int w = 0; w < kThreads / 64; ++w) sum += part[tid][w]; out[tid] = sum; }
+}
+
+// one workgroup: off[i] = the counts cnt[stride i] of the entries before i, and their sum; part: [kThreads + 1] in local memory
+__device__ __forceinline__ int64_t compact_scan(const int64_t* cnt, int stride, int64_t n, int64_t* off, int64_t* part) {
+  const int tid = threadIdx.x;
+  const int64_t per = (n + kThreads - 1) / kThreads, lo = tid * per < n ? tid * per : n, hi = lo + per < n ? lo + per : n;
+  int64_t c = 0;
+  for (int64_t i = lo; i < hi; ++i) c += cnt[stride * i];
+  part[tid] = c;
+  __syncthreads();
+  if (tid == 0) {
+    int64_t run = 0;
+    for (int x = 0; x < kThreads; ++x) { const int64_t v = part[x]; part[x] = run; run += v; }
+    part[kThreads] = run;
+  }
+  __syncthreads();
+  int64_t o = part[tid];
+  for (int64_t i = lo; i < hi; ++i) { off[i] = o; o += cnt[stride * i]; }
+  return part[kThreads];
+}
+
+// where a workgroup's hits go: the hits of the threads before this one, and (all) of the whole workgroup; wcnt: [kThreads / 64] in local memory
+__device__ __forceinline__ int compact_place(bool hit, int32_t* wcnt, int* all) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const uint64_t votes = __ballot(hit);
+  __syncthreads();
+  if (lane == 0) wcnt[wv] = __popcll(votes);
+  __syncthreads();
+  int before = __popcll(votes & ((1ull << lane) - 1ull));
+  *all = 0;
+  for (int w = 0; w < kThreads / 64; ++w) { before += w < wv ? wcnt[w] : 0; *all += wcnt[w]; }
+  return before;
+}
+
 // ==== duplicate objects of the map proposed (include/obvi_map_match.h; MapMatchDev, ba_device.h) ==========================================================
 // Under the rules above.  Every count is a sum of integers and every output position comes from the scan of the rows' counts: nothing depends on the order in
 // which workgroups run.
@@ -819,50 +869,38 @@ __global__ void __launch_bounds__(kThreads) k_mt_count(MapMatchDev m) {
     const double v = m.stat[(int64_t)a * n + b];
     c[0] += match_found(v, m.gate) ? 1 : 0; c[1] += v != kMatchNotTested ? 1 : 0; c[2] += v == kMatchSingular ? 1 : 0;
   }
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int x = 32; x >= 1; x >>= 1) c[i] += __shfl_xor(c[i], x, 64);
-    if ((tid & 63) == 0) part[i][tid >> 6] = c[i];
-  }
-  __syncthreads();
-  if (tid < 3) { int64_t sum = 0; for (int w = 0; w < kThreads / 64; ++w) sum += part[tid][w]; m.row_cnt[3 * (int64_t)a + tid] = sum; }
+  compact_counts(c, part, m.row_cnt + 3 * (int64_t)a);
 }
 
 // one workgroup: row_off[a] = found pairs of the rows before a, and the three totals
 __global__ void __launch_bounds__(kThreads) k_mt_scan(MapMatchDev m) {
-  __shared__ int64_t part[3][kThreads];
-  const int tid = threadIdx.x, n = m.n, per = (n + kThreads - 1) / kThreads, lo = min(n, tid * per), hi = min(n, lo + per);
-  int64_t c[3] = {0, 0, 0};
-  for (int a = lo; a < hi; ++a) for (int i = 0; i < 3; ++i) c[i] += m.row_cnt[3 * (int64_t)a + i];
-  for (int i = 0; i < 3; ++i) part[i][tid] = c[i];
-  __syncthreads();
-  if (tid < 3) {
-    int64_t run = 0;
-    for (int x = 0; x < kThreads; ++x) { const int64_t v = part[tid][x]; part[tid][x] = run; run += v; }
-    m.totals[tid] = run;
+  __shared__ int64_t part[kThreads + 1], rest[2][kThreads];
+  const int tid = threadIdx.x;
+  const int64_t n = m.n, per = (n + kThreads - 1) / kThreads, lo = tid * per < n ? tid * per : n, hi = lo + per < n ? lo + per : n;
+  int64_t t = 0, g = 0;
+  for (int64_t a = lo; a < hi; ++a) { t += m.row_cnt[3 * a + 1]; g += m.row_cnt[3 * a + 2]; }
+  rest[0][tid] = t; rest[1][tid] = g;
+  const int64_t found = compact_scan(m.row_cnt, 3, n, m.row_off, part);   // its barriers stand between the sums above and below
+  if (tid == 0) m.totals[0] = found;
+  if (tid < 2) {
+    int64_t sum = 0;
+    for (int x = 0; x < kThreads; ++x) sum += rest[tid][x];
+    m.totals[1 + tid] = sum;
   }
-  __syncthreads();
-  int64_t off = part[0][tid];
-  for (int a = lo; a < hi; ++a) { m.row_off[a] = off; off += m.row_cnt[3 * (int64_t)a]; }
 }
 
 // row a: its found pairs to their places behind row_off[a], in the order of b, up to `capacity`
 __global__ void __launch_bounds__(kThreads) k_mt_scatter(MapMatchDev m) {
   __shared__ int32_t wcnt[kThreads / 64];
-  const int a = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = m.n, od = m.od;
+  const int a = blockIdx.x, tid = threadIdx.x, n = m.n, od = m.od;
   if (m.row_cnt[3 * (int64_t)a] == 0) return;
   int64_t base = m.row_off[a];
   for (int b0 = a + 1; b0 < n && base < m.capacity; b0 += kThreads) {
     const int b = b0 + tid;
     const double v = b < n ? m.stat[(int64_t)a * n + b] : kMatchNotTested;
     const bool hit = match_found(v, m.gate);
-    const uint64_t votes = __ballot(hit);
-    __syncthreads();
-    if (lane == 0) wcnt[wv] = __popcll(votes);
-    __syncthreads();
-    int before = __popcll(votes & ((1ull << lane) - 1ull)), all = 0;
-    for (int w = 0; w < kThreads / 64; ++w) { before += w < wv ? wcnt[w] : 0; all += wcnt[w]; }
+    int all;
+    const int before = compact_place(hit, wcnt, &all);
     const int64_t pos = base + before;
     if (hit && pos < m.capacity) {
       m.out_a[pos] = (uint32_t)a; m.out_b[pos] = (uint32_t)b; m.out_stat[pos] = v;
@@ -1178,34 +1216,10 @@ __global__ void __launch_bounds__(kThreads) k_ml_count(MapLocateDev m) {
       c[0] += code >= 1 ? 1 : 0; c[1] += code == 2 ? 1 : 0;
     }
   }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-#pragma unroll
-    for (int x = 32; x >= 1; x >>= 1) c[i] += __shfl_xor(c[i], x, 64);
-    if ((tid & 63) == 0) part[i][tid >> 6] = c[i];
-  }
-  __syncthreads();
-  if (tid < 2) { int64_t sum = 0; for (int w = 0; w < kThreads / 64; ++w) sum += part[tid][w]; m.row_cnt[2 * ((int64_t)a1 * na + a2) + tid] = sum; }
+  compact_counts(c, part, m.row_cnt + 2 * ((int64_t)a1 * na + a2));
 }
 
-// one workgroup: off[i] = the counts [i][stride] of the entries before i, and their sum; the two uses: the rows' seeds, the blocks' qualifying hypotheses
-__device__ __forceinline__ int64_t ml_scan(const int64_t* cnt, int stride, int64_t n, int64_t* off, int64_t* part) {
-  const int tid = threadIdx.x;
-  const int64_t per = (n + kThreads - 1) / kThreads, lo = tid * per < n ? tid * per : n, hi = lo + per < n ? lo + per : n;
-  int64_t c = 0;
-  for (int64_t i = lo; i < hi; ++i) c += cnt[stride * i];
-  part[tid] = c;
-  __syncthreads();
-  if (tid == 0) {
-    int64_t run = 0;
-    for (int x = 0; x < kThreads; ++x) { const int64_t v = part[x]; part[x] = run; run += v; }
-    part[kThreads] = run;
-  }
-  __syncthreads();
-  int64_t o = part[tid];
-  for (int64_t i = lo; i < hi; ++i) { off[i] = o; o += cnt[stride * i]; }
-  return part[kThreads];
-}
+// one workgroup: row_off[row] = compatible seeds of the rows before it, and the totals
 __global__ void __launch_bounds__(kThreads) k_ml_scan(MapLocateDev m) {
   __shared__ int64_t part[kThreads + 1], tested[kThreads];
   const int tid = threadIdx.x;
@@ -1213,25 +1227,12 @@ __global__ void __launch_bounds__(kThreads) k_ml_scan(MapLocateDev m) {
   int64_t t = 0;
   for (int64_t i = lo; i < hi; ++i) t += m.row_cnt[2 * i];
   tested[tid] = t;
-  const int64_t compatible = ml_scan(m.row_cnt + 1, 2, rows, m.row_off, part);
+  const int64_t compatible = compact_scan(m.row_cnt + 1, 2, rows, m.row_off, part);
   if (tid == 0) {
     int64_t sum = 0;
     for (int x = 0; x < kThreads; ++x) sum += tested[x];
     m.totals[0] = sum; m.totals[1] = compatible; m.totals[2] = 0;
   }
-}
-
-// where a workgroup's hits go: the hits of the threads before this one, and (all) of the whole workgroup; wcnt: [kThreads / 64]
-__device__ __forceinline__ int ml_place(bool hit, int32_t* wcnt, int* all) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const uint64_t votes = __ballot(hit);
-  __syncthreads();
-  if (lane == 0) wcnt[wv] = __popcll(votes);
-  __syncthreads();
-  int before = __popcll(votes & ((1ull << lane) - 1ull));
-  *all = 0;
-  for (int w = 0; w < kThreads / 64; ++w) { before += w < wv ? wcnt[w] : 0; *all += wcnt[w]; }
-  return before;
 }
 
 // row (a1, a2): its compatible seeds to their places behind row_off, in the order of (b1, b2)
@@ -1248,7 +1249,7 @@ __global__ void __launch_bounds__(kThreads) k_ml_scatter(MapLocateDev m) {
     const bool hit = j < nb * nb && b1 != b2 &&
                      ml_seed_test(pa1, pa2, m.rec + (int64_t)(na + b1) * kLocateRec, m.rec + (int64_t)(na + b2) * kLocateRec, la1, la2, m.lab[na + b1], m.lab[na + b2], m.dmin, m.tol) == 2;
     int all;
-    const int before = ml_place(hit, wcnt, &all);
+    const int before = compact_place(hit, wcnt, &all);
     if (hit) { uint32_t* sd = m.seeds + 4 * (base + before); sd[0] = (uint32_t)a1; sd[1] = (uint32_t)a2; sd[2] = (uint32_t)b1; sd[3] = (uint32_t)b2; }
     base += all;
   }
@@ -1295,12 +1296,12 @@ __device__ __forceinline__ bool ml_qualifies(const MapLocateDev& m, int64_t h) {
 __global__ void __launch_bounds__(kThreads) k_ml_qcount(MapLocateDev m) {
   __shared__ int32_t wcnt[kThreads / 64];
   int all;
-  ml_place(ml_qualifies(m, (int64_t)blockIdx.x * kThreads + threadIdx.x), wcnt, &all);
+  compact_place(ml_qualifies(m, (int64_t)blockIdx.x * kThreads + threadIdx.x), wcnt, &all);
   if (threadIdx.x == 0) m.blk_cnt[blockIdx.x] = all;
 }
 __global__ void __launch_bounds__(kThreads) k_ml_qscan(MapLocateDev m) {
   __shared__ int64_t part[kThreads + 1];
-  const int64_t found = ml_scan(m.blk_cnt, 1, (m.seed_cap + kThreads - 1) / kThreads, m.blk_off, part);
+  const int64_t found = compact_scan(m.blk_cnt, 1, (m.seed_cap + kThreads - 1) / kThreads, m.blk_off, part);
   if (threadIdx.x == 0) m.totals[2] = found;
 }
 // ... and their numbers, in ascending order
@@ -1309,7 +1310,7 @@ __global__ void __launch_bounds__(kThreads) k_ml_qscatter(MapLocateDev m) {
   const int64_t h = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   const bool hit = ml_qualifies(m, h);
   int all;
-  const int before = ml_place(hit, wcnt, &all);
+  const int before = compact_place(hit, wcnt, &all);
   if (hit) m.qlist[m.blk_off[blockIdx.x] + before] = (uint32_t)h;
 }
 

@@ -1,6 +1,6 @@
 // map_locate.cpp -- include/obvi_map_locate.h: one device-resident map located in another from the constellations of their object centres (map_kernels.hip).
-// The host checks the arguments, lays the workspaces out in the handle's own d_ml_* buffers, launches up to the counts and reads them back; when hypotheses
-// are to be reported it launches their ranking and refinement and reads those back.  Two waits at the most.
+// The host checks the arguments, carves the workspaces out of the handle's one-call workspace (map_window.h), launches up to the counts and ends in the report
+// tail it shares with the match (finish_report): when hypotheses are to be reported, their ranking and refinement are launched between its two waits.
 #include "map_window.h"
 #include "../../include/obvi_map_locate.h"
 
@@ -29,49 +29,42 @@ int obvi_map_locate(obvi_ba_handle* h, const obvi_map* a, const obvi_map* b, con
   const int od = h->od;
   const int64_t rows = na * na, all_seeds = (na * (na - 1) / 2) * (nb * (nb - 1)), seed_cap = std::min(all_seeds, kLocateMaxSeeds), blocks = (seed_cap + 255) / 256;
   const int64_t cap = std::min(capacity, seed_cap);
-  if (label_a || label_b) h->d_ml_label.resize((size_t)(na + nb));
-  if (label_a) h2d_async(h->d_ml_label.get(), label_a, sizeof(int32_t) * (size_t)na, s);
-  if (label_b) h2d_async(h->d_ml_label.get() + na, label_b, sizeof(int32_t) * (size_t)nb, s);
-  h->d_ml_rec.resize((size_t)((na + nb) * kLocateRec)); h->d_ml_lab.resize((size_t)(na + nb));
-  h->d_ml_cnt.resize((size_t)(3 * rows + 3 + 2 * blocks));
-  h->d_ml_seeds.resize((size_t)(4 * seed_cap)); h->d_ml_inl.resize((size_t)seed_cap); h->d_ml_cost.resize((size_t)seed_cap);
-  h->d_ml_list.resize((size_t)(seed_cap + cap + 4 * cap)); h->d_ml_dout.resize((size_t)(21 * cap)); h->d_ml_iout.resize((size_t)((1 + nb) * cap));
   MapLocateDev m{};
   m.od = od; m.na = (int32_t)na; m.nb = (int32_t)nb; m.min_inliers = p.min_inliers; m.iterations = p.refine_iterations;
   m.has_label_a = label_a ? 1 : 0; m.has_label_b = label_b ? 1 : 0;
   m.dmin = p.pair_min_distance; m.tol = p.pair_tolerance; m.gate = p.inlier_gate; m.seed_cap = seed_cap;
   m.mean_a = a->d_mean; m.cov_a = a->d_cov; m.mean_b = b->d_mean; m.cov_b = b->d_cov;
-  m.label_a = h->d_ml_label.get(); m.label_b = h->d_ml_label.get() + na;
-  m.rec = h->d_ml_rec.get(); m.lab = h->d_ml_lab.get();
-  m.row_cnt = h->d_ml_cnt.get(); m.row_off = m.row_cnt + 2 * rows; m.totals = m.row_off + rows; m.blk_cnt = m.totals + 3; m.blk_off = m.blk_cnt + blocks;
-  m.seeds = h->d_ml_seeds.get(); m.inl = h->d_ml_inl.get(); m.cost = h->d_ml_cost.get();
-  m.qlist = h->d_ml_list.get(); m.sel = m.qlist + seed_cap; m.out_seed = m.sel + cap;
-  m.out_T = h->d_ml_dout.get(); m.out_cov = m.out_T + 4 * cap; m.out_cost = m.out_cov + 16 * cap;
-  m.out_inl = h->d_ml_iout.get(); m.out_partner = m.out_inl + cap;
+  int32_t* d_label_a = nullptr; int32_t* d_label_b = nullptr;
+  carve_workspace(h, [&](Carver& c) {
+    if (label_a) d_label_a = c.take<int32_t>(na);
+    if (label_b) d_label_b = c.take<int32_t>(nb);
+    m.rec = c.take<double>((na + nb) * kLocateRec); m.lab = c.take<int32_t>(na + nb);
+    m.row_cnt = c.take<int64_t>(2 * rows); m.row_off = c.take<int64_t>(rows); m.totals = c.take<int64_t>(3);
+    m.blk_cnt = c.take<int64_t>(blocks); m.blk_off = c.take<int64_t>(blocks);
+    m.seeds = c.take<uint32_t>(4 * seed_cap); m.inl = c.take<int32_t>(seed_cap); m.cost = c.take<double>(seed_cap);   // entries [0, totals[1]) are written, and no other is read
+    m.qlist = c.take<uint32_t>(seed_cap); m.sel = c.take<uint32_t>(cap); m.out_seed = c.take<uint32_t>(4 * cap);
+    m.out_T = c.take<double>(4 * cap); m.out_cov = c.take<double>(16 * cap); m.out_cost = c.take<double>(cap);
+    m.out_inl = c.take<int32_t>(cap); m.out_partner = c.take<int32_t>(nb * cap);
+  });
+  if (label_a) h2d_async(d_label_a, label_a, sizeof(int32_t) * (size_t)na, s);
+  if (label_b) h2d_async(d_label_b, label_b, sizeof(int32_t) * (size_t)nb, s);
+  m.label_a = d_label_a; m.label_b = d_label_b;
   launch_map_locate_score(s, m);
-  OBVI_HIP(hipGetLastError());
-  int64_t totals[3];
-  OBVI_HIP(hipMemcpyAsync(totals, m.totals, sizeof(totals), hipMemcpyDeviceToHost, s));
-  sync(h);   // the first wait: the three counts
-  if (totals[1] > seed_cap) {
-    counts[0] = totals[0]; counts[1] = totals[1]; counts[2] = 0;
-    return fail(h, OBVI_ERR_OUT_OF_RANGE, "map_locate: more than OBVI_MAP_LOCATE_MAX_SEEDS compatible seeds: tighten pair_tolerance or add labels");
-  }
-  const int64_t out = std::min(totals[2], cap);
-  if (out > 0) {
-    m.found = totals[2]; m.out = out;
-    launch_map_locate_report(s, m);
-    OBVI_HIP(hipGetLastError());
-    OBVI_HIP(hipMemcpyAsync(seed, m.out_seed, sizeof(uint32_t) * 4 * out, hipMemcpyDeviceToHost, s));
-    OBVI_HIP(hipMemcpyAsync(transform, m.out_T, sizeof(double) * 4 * out, hipMemcpyDeviceToHost, s));
-    if (transform_cov) OBVI_HIP(hipMemcpyAsync(transform_cov, m.out_cov, sizeof(double) * 16 * out, hipMemcpyDeviceToHost, s));
-    OBVI_HIP(hipMemcpyAsync(inliers, m.out_inl, sizeof(int32_t) * out, hipMemcpyDeviceToHost, s));
-    OBVI_HIP(hipMemcpyAsync(cost, m.out_cost, sizeof(double) * out, hipMemcpyDeviceToHost, s));
-    if (partner) OBVI_HIP(hipMemcpyAsync(partner, m.out_partner, sizeof(int32_t) * nb * out, hipMemcpyDeviceToHost, s));
-    sync(h);   // the second: the hypotheses, only when there are some to report
-  }
-  std::copy(totals, totals + 3, counts);
-  return OBVI_OK;
+  return finish_report(h, m.totals, 2, cap,
+                       {{seed, m.out_seed, sizeof(uint32_t) * 4}, {transform, m.out_T, sizeof(double) * 4}, {transform_cov, m.out_cov, sizeof(double) * 16}, {inliers, m.out_inl, sizeof(int32_t)},
+                        {cost, m.out_cost, sizeof(double)}, {partner, m.out_partner, sizeof(int32_t) * (size_t)nb}},
+                       counts, [&](const int64_t* totals, int64_t out) {
+    if (totals[1] > seed_cap) {
+      counts[0] = totals[0]; counts[1] = totals[1]; counts[2] = 0;
+      return fail(h, OBVI_ERR_OUT_OF_RANGE, "map_locate: more than OBVI_MAP_LOCATE_MAX_SEEDS compatible seeds: tighten pair_tolerance or add labels");
+    }
+    if (out > 0) {   // the second half, between the two waits
+      m.found = totals[2]; m.out = out;
+      launch_map_locate_report(s, m);
+      OBVI_HIP(hipGetLastError());
+    }
+    return (int)OBVI_OK;
+  });
   OBVI_API_END(h)
 }
 

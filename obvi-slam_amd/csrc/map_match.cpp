@@ -1,6 +1,6 @@
-// map_match.cpp -- include/obvi_map_match.h: duplicate objects of a device-resident map proposed (map_kernels.hip).  The host checks the arguments, lays the
-// workspaces out in the handle's own d_mt_* buffers, launches, reads the three totals back and then the pairs that were found.  The resolver that turns the
-// pairs into the lists of obvi_map_merge is plain host code below it.
+// map_match.cpp -- include/obvi_map_match.h: duplicate objects of a device-resident map proposed (map_kernels.hip).  The host checks the arguments, carves the
+// workspaces out of the handle's one-call workspace (map_window.h), launches, and ends in the report tail it shares with the locate (finish_report).  The
+// resolver that turns the pairs into the lists of obvi_map_merge is plain host code below it.
 #include "map_window.h"
 #include "../../include/obvi_map_match.h"
 
@@ -23,31 +23,22 @@ int obvi_map_match(obvi_ba_handle* h, const obvi_map* map, const int32_t* label,
   OBVI_HIP(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   const int64_t n = map->n, cap = std::min(capacity, n * (n - 1) / 2);
-  if (label) h->d_mt_label.upload(label, (size_t)n, s);
-  h->d_mt_diag.resize((size_t)(n * od * od)); h->d_mt_stat.resize((size_t)(n * n)); h->d_mt_cnt.resize((size_t)(4 * n + 3));
-  h->d_mt_idx.resize((size_t)(2 * cap)); h->d_mt_out.resize((size_t)(2 * cap));
   MapMatchDev m{};
   m.od = od; m.n = (int32_t)n; m.mask = row_mask ? row_mask : (1u << od) - 1u; m.use_dist = std::isinf(max_centre_distance) ? 0 : 1;
   m.gate = gate; m.dist2 = max_centre_distance * max_centre_distance; m.period = yaw_period; m.capacity = cap;
-  m.map_mean = map->d_mean; m.map_cov = map->d_cov; m.label = label ? h->d_mt_label.get() : nullptr;
-  m.diag = h->d_mt_diag.get(); m.stat = h->d_mt_stat.get();
-  m.row_cnt = h->d_mt_cnt.get(); m.row_off = m.row_cnt + 3 * n; m.totals = m.row_off + n;
-  m.out_a = h->d_mt_idx.get(); m.out_b = m.out_a + cap; m.out_stat = h->d_mt_out.get(); m.out_yaw = m.out_stat + cap;
+  m.map_mean = map->d_mean; m.map_cov = map->d_cov;
+  int32_t* d_label = nullptr;
+  carve_workspace(h, [&](Carver& c) {
+    if (label) d_label = c.take<int32_t>(n);
+    m.diag = c.take<double>(n * od * od); m.stat = c.take<double>(n * n);   // stat: k_mt_pairs writes the pairs a < b, and nothing else is read
+    m.row_cnt = c.take<int64_t>(3 * n); m.row_off = c.take<int64_t>(n); m.totals = c.take<int64_t>(3);
+    m.out_a = c.take<uint32_t>(cap); m.out_b = c.take<uint32_t>(cap); m.out_stat = c.take<double>(cap); m.out_yaw = c.take<double>(cap);
+  });
+  if (label) h2d_async(d_label, label, sizeof(int32_t) * (size_t)n, s);
+  m.label = d_label;
   launch_map_match(s, m);
-  OBVI_HIP(hipGetLastError());
-  int64_t totals[3];
-  OBVI_HIP(hipMemcpyAsync(totals, m.totals, sizeof(totals), hipMemcpyDeviceToHost, s));
-  sync(h);   // the first wait: the three totals
-  const int64_t out = std::min(totals[0], cap);
-  if (out > 0) {
-    OBVI_HIP(hipMemcpyAsync(idx_a, m.out_a, sizeof(uint32_t) * out, hipMemcpyDeviceToHost, s));
-    OBVI_HIP(hipMemcpyAsync(idx_b, m.out_b, sizeof(uint32_t) * out, hipMemcpyDeviceToHost, s));
-    OBVI_HIP(hipMemcpyAsync(stat, m.out_stat, sizeof(double) * out, hipMemcpyDeviceToHost, s));
-    OBVI_HIP(hipMemcpyAsync(yaw_offset, m.out_yaw, sizeof(double) * out, hipMemcpyDeviceToHost, s));
-    sync(h);   // the second: the pairs, only when there are some to report
-  }
-  std::copy(totals, totals + 3, counts);
-  return OBVI_OK;
+  return finish_report(h, m.totals, 0, cap, {{idx_a, m.out_a, sizeof(uint32_t)}, {idx_b, m.out_b, sizeof(uint32_t)}, {stat, m.out_stat, sizeof(double)}, {yaw_offset, m.out_yaw, sizeof(double)}},
+                       counts, [](const int64_t*, int64_t) { return (int)OBVI_OK; });
   OBVI_API_END(h)
 }
 

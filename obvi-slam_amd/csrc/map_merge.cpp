@@ -33,21 +33,25 @@ int obvi_map_merge(obvi_ba_handle* h, const obvi_map* map, int64_t q, const uint
   kept.reserve((size_t)(n - q));
   for (int64_t o = 0; o < n; ++o) if (!dropped[o]) { where[o] = (uint32_t)kept.size(); kept.push_back((uint32_t)o); }
   for (int64_t r = 0; r < q; ++r) where[drop_idx[r]] = where[keep_idx[r]];
-  std::vector<double> in((size_t)(Q + (noise ? q * nn : 0)), 0.0);
-  if (offset) std::copy(offset, offset + Q, in.begin());
-  if (noise) std::copy(noise, noise + q * nn, in.begin() + Q);
+  const std::vector<double> no_offset(offset ? (size_t)0 : (size_t)Q, 0.0);
   const int64_t N = n * od, NK = (n - q) * od, nQ = map_group_slabs(Q), nK = map_group_slabs(NK), tile = (int64_t)kTile * kTile;
   const MapCutDev m = window_cut(h, q, drop_idx);
-  h->d_mm_keep.upload(keep_idx, (size_t)q, s); h->d_mm_kept.upload(kept, s); h->d_mm_in.upload(in, s);
-  h->d_mm_tiles.resize((size_t)((nQ * nQ + 2 * nK * nQ) * tile + kTile * nQ));
   std::unique_ptr<obvi_map, MapDeleter> fresh = allocate_map(map->device, od, n - q);
   inherit_power_start(fresh.get(), map, s);
   MapMergeDev g{};
   g.od = od; g.N = (int32_t)N; g.Q = (int32_t)Q; g.NK = (int32_t)NK; g.nQ = (int32_t)nQ; g.nK = (int32_t)nK;
-  g.cut = m; g.keep = h->d_mm_keep.get(); g.kept = h->d_mm_kept.get();
-  g.offset = h->d_mm_in.get(); g.noise = noise ? h->d_mm_in.get() + Q : nullptr;
-  g.map_mean = map->d_mean; g.map_cov = map->d_cov;
-  g.Wn = h->d_mm_tiles.get(); g.G = g.Wn + nQ * nQ * tile; g.Y = g.G + nK * nQ * tile; g.v = g.Y + nK * nQ * tile;
+  g.cut = m; g.map_mean = map->d_mean; g.map_cov = map->d_cov;
+  uint32_t* d_keep = nullptr; uint32_t* d_kept = nullptr; double* d_offset = nullptr; double* d_noise = nullptr;
+  carve_workspace(h, [&](Carver& c) {
+    d_keep = c.take<uint32_t>(q); d_kept = c.take<uint32_t>(n - q); d_offset = c.take<double>(Q);
+    if (noise) d_noise = c.take<double>(q * nn);
+    g.Wn = c.take<double>(nQ * nQ * tile); g.G = c.take<double>(nK * nQ * tile); g.Y = c.take<double>(nK * nQ * tile);   // whole tiles by k_mu_operands, k_mm_gather, k_mu_gemm
+    g.v = c.take<double>(kTile * nQ);                                                                                   // all 64 nQ rows by k_map_wd
+  });
+  h2d_async(d_keep, keep_idx, sizeof(uint32_t) * (size_t)q, s); h2d_async(d_kept, kept.data(), sizeof(uint32_t) * kept.size(), s);
+  h2d_async(d_offset, offset ? offset : no_offset.data(), sizeof(double) * (size_t)Q, s);
+  if (noise) h2d_async(d_noise, noise, sizeof(double) * (size_t)(q * nn), s);
+  g.keep = d_keep; g.kept = d_kept; g.offset = d_offset; g.noise = d_noise;
   g.out_mean = fresh->d_mean; g.out_cov = fresh->d_cov;
   launch_map_merge(s, g, map->d_x0);
   { const int rc = finish_window_call(h, true, "map_merge: the covariance of the pairs' differences is not SPD, or numerically singular (a pair that is already merged?)",

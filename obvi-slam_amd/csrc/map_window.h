@@ -2,11 +2,14 @@
 // or gathered; map_merge.cpp: its duplicates merged): the checks of the window's map objects, the one-group cut of those objects in the handle's scratch
 // buffers, the device view of the update, allocate_map, the end of a call on the cut's status record (finish_window_call), the posterior's way to the device
 // (upload_posterior, posterior_from_handle), fold_window -- the one routine that brings a window back into a map -- and the start vector a map is given at birth.
+// For the entries whose device arrays live for one call (map_merge.cpp, map_match.cpp, map_frame.cpp, map_locate.cpp): carve_workspace, which lays an entry's
+// arrays out in the handle's one grow-only workspace; and finish_report, the two-wait tail of the two entries that report lists (match, locate).
 #ifndef OBVI_MAP_WINDOW_H_
 #define OBVI_MAP_WINDOW_H_
 #include "ba_handle.h"
 #include "../../include/obvi_map_resident.h"
 
+#include <initializer_list>
 #include <memory>
 
 namespace obvi_lib {
@@ -145,6 +148,49 @@ inline int finish_window_call(obvi_ba_handle* h, bool factored, const std::strin
   sync(h);
   if (factored && !window_cut_spd(st)) return fail(h, OBVI_ERR_NUMERICAL, not_spd);
   if (st[MS_NONFINITE] != 0.0) return fail(h, OBVI_ERR_NUMERICAL, non_finite);
+  return OBVI_OK;
+}
+
+// The workspace of the entries whose device arrays live for one call -- merge, match, transform, locate; each ends in a wait, so nothing in it outlives its
+// call -- carved out of the handle's d_map_ws.  An entry lists its arrays once, as take<element type>(count), in a function that runs twice: once to measure,
+// once, the buffer grown to the sum, to hand the pointers out at offsets that are multiples of 256 bytes.  The regions of one call alias those of the last in
+// another way every time: whatever a kernel reads must have been written on the stream by this call (the *Dev structs of ba_device.h say by whom).
+struct Carver {
+  char* base; size_t bytes = 0;
+  template <class T> T* take(int64_t count) {
+    T* p = base ? reinterpret_cast<T*>(base + bytes) : nullptr;
+    bytes += (sizeof(T) * (size_t)count + 255) & ~(size_t)255;
+    return p;
+  }
+};
+template <class List>
+inline void carve_workspace(obvi_ba_handle* h, List&& list) {
+  Carver measure{nullptr};
+  list(measure);
+  h->d_map_ws.resize(measure.bytes);
+  Carver hand_out{h->d_map_ws.get()};
+  list(hand_out);
+}
+
+// The end of a report entry (match, locate), after the launches that leave three int64 totals at d_totals.  The launch-error check and the totals read back
+// behind the first wait; then between(totals, out), out = min(totals[found_at], cap) the entries to report: what the entry refuses on the totals (anything but
+// OBVI_OK is returned as it is) and the launches that need them; then the first `out` entries of every caller array (host NULL: an optional array left out)
+// and the second wait, only when out > 0; the totals into counts last.  Nothing behind entry `out` of a caller's array is written.
+struct ReportArray { void* host; const void* dev; size_t entry_bytes; };
+template <class Between>
+inline int finish_report(obvi_ba_handle* h, const int64_t* d_totals, int found_at, int64_t cap, std::initializer_list<ReportArray> arrays, int64_t* counts, Between&& between) {
+  hipStream_t s = h->stream;
+  OBVI_HIP(hipGetLastError());
+  int64_t totals[3];
+  OBVI_HIP(hipMemcpyAsync(totals, d_totals, sizeof(totals), hipMemcpyDeviceToHost, s));
+  sync(h);   // the first wait: the three totals
+  const int64_t out = std::min(totals[found_at], cap);
+  { const int rc = between(totals, out); if (rc != OBVI_OK) return rc; }
+  if (out > 0) {
+    for (const ReportArray& a : arrays) if (a.host) OBVI_HIP(hipMemcpyAsync(a.host, a.dev, a.entry_bytes * (size_t)out, hipMemcpyDeviceToHost, s));
+    sync(h);   // the second: the entries, only when there are some to report
+  }
+  std::copy(totals, totals + 3, counts);
   return OBVI_OK;
 }
 

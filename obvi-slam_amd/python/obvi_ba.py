@@ -121,22 +121,53 @@ def _ptr(a, ctype):
     return None if a is None else a.ctypes.data_as(C.POINTER(ctype))
 
 
+def _library_path(library=None):
+    """`library`, or the default build; a build that is not there raises: nothing computes in its place."""
+    path = library or default_library_path()
+    if not os.path.exists(path):
+        raise ObviError("%s not found: build it with __graft_entry__.build() -- there is no CPU fallback" % path)
+    return path
+
+
+def _entry(lib, prefix, name, header="obvi_ba.h", restype=C.c_int):
+    """lib's function prefix + name, its restype set.  A library that lacks it (the oracle mirrors include/obvi_ba.h alone) raises, naming the entry and its header."""
+    try:
+        f = getattr(lib, prefix + name)
+    except AttributeError:
+        raise ObviError("%s%s: this library does not have the entry (include/%s is served by libobvi_ba.so only)" % (prefix, name, header))
+    f.restype = restype
+    return f
+
+
+def _count_then_fill(capacity, counts, found_at, call, alloc):
+    """The capacity protocol of the two report entries (Map.match, Map.locate).  call(cap, arrays) runs the entry -- arrays None: NULL pointers -- and fills
+    counts; alloc(cap) makes the output arrays.  capacity None: a call with capacity 0, then one of the exact size counts[found_at]; a negative one is passed
+    through to be refused; 0: the count-only call alone.  Returns (arrays, k), k the entries that were reported."""
+    counted = capacity is None
+    if counted:
+        call(0, None)
+        capacity = counts[found_at]
+    capacity = int(capacity)
+    if capacity < 0:
+        call(capacity, None)                                           # refused: raises
+    arrays = alloc(capacity)
+    if capacity > 0:
+        call(capacity, arrays)
+    elif not counted:
+        call(0, None)
+    return arrays, min(capacity, int(counts[found_at]))
+
+
 class Map:
     """A long-term map on the device (include/obvi_map_resident.h): means [n][od] and the joint covariance [n od][n od] of its n objects, uploaded once and
     immutable; any BundleAdjuster on the same device cuts its group priors from it (set_map_group_priors_from_map)."""
 
     def __init__(self, mean, cov, device_id=0, object_block_size=7, library=None, prefix="obvi_"):
-        path = library or default_library_path()
-        if not os.path.exists(path):
-            raise ObviError("%s not found: build it with __graft_entry__.build() -- there is no CPU fallback" % path)
+        path = _library_path(library)
         self._lib = C.CDLL(path)
         self._pre = prefix
         self._m = C.c_void_p()
-        try:
-            f = getattr(self._lib, prefix + "map_create")
-        except AttributeError:
-            raise ObviError("%smap_create: this library has no device-resident map (include/obvi_map_resident.h is served by libobvi_ba.so only)" % prefix)
-        f.restype = C.c_int
+        f = _entry(self._lib, prefix, "map_create", "obvi_map_resident.h")
         self.od = int(object_block_size) or 7
         mu = _f64(mean, (-1, self.od))
         cv = _f64(cov, (len(mu) * self.od, len(mu) * self.od))
@@ -154,15 +185,10 @@ class Map:
         f.restype = C.c_int64
         return int(f(self._m))
 
-    # ---- the way back (include/obvi_map_update.h) ----
-    def _update_fn(self, name):
-        try:
-            f = getattr(self._lib, self._pre + name)
-        except AttributeError:
-            raise ObviError("%s%s: this library cannot read or condition a map (include/obvi_map_update.h is served by libobvi_ba.so only)" % (self._pre, name))
-        f.restype = C.c_int
-        return f
+    def _entry(self, name, header):
+        return _entry(self._lib, self._pre, name, header)
 
+    # ---- the way back (include/obvi_map_update.h) ----
     def _conditioned(self, ba, rc, new, what):
         ba._check(rc, what)
         m = Map.__new__(Map)
@@ -173,7 +199,7 @@ class Map:
         """(mean [n][od], cov [n od][n od]) as the device holds them."""
         n = self.n_objects
         mean, cov = np.zeros((n, self.od)), np.zeros((n * self.od, n * self.od))
-        rc = self._update_fn("map_get")(self._m, _ptr(mean, C.c_double), _ptr(cov, C.c_double))
+        rc = self._entry("map_get", "obvi_map_update.h")(self._m, _ptr(mean, C.c_double), _ptr(cov, C.c_double))
         if rc != 0:
             raise ObviError("%smap_get failed: status %d" % (self._pre, rc))
         return mean, cov
@@ -184,7 +210,7 @@ class Map:
         mu = _f64(post_mean, (len(mid), self.od))
         cv = _f64(post_cov, (len(mid) * self.od, len(mid) * self.od))
         new = C.c_void_p()
-        rc = self._update_fn("map_condition")(ba._h, self._m, C.c_int64(len(mid)), _ptr(mid, C.c_uint32), _ptr(mu, C.c_double), _ptr(cv, C.c_double), C.byref(new))
+        rc = self._entry("map_condition", "obvi_map_update.h")(ba._h, self._m, C.c_int64(len(mid)), _ptr(mid, C.c_uint32), _ptr(mu, C.c_double), _ptr(cv, C.c_double), C.byref(new))
         return self._conditioned(ba, rc, new, "map_condition")
 
     def condition_on(self, ba, obj_idx, map_idx):
@@ -193,18 +219,10 @@ class Map:
         if len(oid) != len(mid):
             raise ObviError("map_condition_on_handle: obj_idx and map_idx differ in length")
         new = C.c_void_p()
-        rc = self._update_fn("map_condition_on_handle")(ba._h, self._m, C.c_int64(len(mid)), _ptr(oid, C.c_uint32), _ptr(mid, C.c_uint32), C.byref(new))
+        rc = self._entry("map_condition_on_handle", "obvi_map_update.h")(ba._h, self._m, C.c_int64(len(mid)), _ptr(oid, C.c_uint32), _ptr(mid, C.c_uint32), C.byref(new))
         return self._conditioned(ba, rc, new, "map_condition_on_handle")
 
     # ---- a map that grows (include/obvi_map_extend.h) ----
-    def _extend_fn(self, name):
-        try:
-            f = getattr(self._lib, self._pre + name)
-        except AttributeError:
-            raise ObviError("%s%s: this library cannot grow or gather a map (include/obvi_map_extend.h is served by libobvi_ba.so only)" % (self._pre, name))
-        f.restype = C.c_int
-        return f
-
     @classmethod
     def _unborn(cls, ba):
         """No map yet: what from_posterior / from_handle extend.  It takes the library, prefix and block size of `ba`."""
@@ -220,7 +238,7 @@ class Map:
         mu = _f64(post_mean, (k, self.od))
         cv = _f64(post_cov, (k * self.od, k * self.od))
         new = C.c_void_p()
-        rc = self._extend_fn("map_extend")(ba._h, self._m, C.c_int64(len(mid)), _ptr(mid, C.c_uint32) if len(mid) else None, C.c_int64(int(n_new)),
+        rc = self._entry("map_extend", "obvi_map_extend.h")(ba._h, self._m, C.c_int64(len(mid)), _ptr(mid, C.c_uint32) if len(mid) else None, C.c_int64(int(n_new)),
                                            _ptr(mu, C.c_double), _ptr(cv, C.c_double), C.byref(new))
         return self._conditioned(ba, rc, new, "map_extend")
 
@@ -231,7 +249,7 @@ class Map:
         if len(old) != len(mid):
             raise ObviError("map_extend_on_handle: obj_old and map_idx differ in length")
         new = C.c_void_p()
-        rc = self._extend_fn("map_extend_on_handle")(ba._h, self._m, C.c_int64(len(mid)), _ptr(old, C.c_uint32) if len(old) else None,
+        rc = self._entry("map_extend_on_handle", "obvi_map_extend.h")(ba._h, self._m, C.c_int64(len(mid)), _ptr(old, C.c_uint32) if len(old) else None,
                                                      _ptr(mid, C.c_uint32) if len(mid) else None, C.c_int64(len(fresh)), _ptr(fresh, C.c_uint32), C.byref(new))
         return self._conditioned(ba, rc, new, "map_extend_on_handle")
 
@@ -239,7 +257,7 @@ class Map:
         """A new Map of this one's objects map_idx, in that order, copied as the device holds them: a subset is the marginal, all of them a permutation."""
         mid = np.ascontiguousarray(map_idx, dtype=np.uint32).ravel()
         new = C.c_void_p()
-        rc = self._extend_fn("map_select")(ba._h, self._m, C.c_int64(len(mid)), _ptr(mid, C.c_uint32), C.byref(new))
+        rc = self._entry("map_select", "obvi_map_extend.h")(ba._h, self._m, C.c_int64(len(mid)), _ptr(mid, C.c_uint32), C.byref(new))
         return self._conditioned(ba, rc, new, "map_select")
 
     @classmethod
@@ -259,11 +277,7 @@ class Map:
         drop, keep = np.ascontiguousarray(drop_idx, dtype=np.uint32).ravel(), np.ascontiguousarray(keep_idx, dtype=np.uint32).ravel()
         if len(drop) != len(keep):
             raise ObviError("map_merge: drop_idx and keep_idx differ in length")
-        try:
-            f = getattr(self._lib, self._pre + "map_merge")
-        except AttributeError:
-            raise ObviError("%smap_merge: this library cannot merge objects of a map (include/obvi_map_merge.h is served by libobvi_ba.so only)" % self._pre)
-        f.restype = C.c_int
+        f = self._entry("map_merge", "obvi_map_merge.h")
         d = None if offset is None else _f64(offset, (len(drop), self.od))
         r = None if noise is None else _f64(noise, (len(drop), self.od, self.od))
         where = np.zeros(self.n_objects, np.uint32)
@@ -276,44 +290,21 @@ class Map:
     def match(self, ba, gate, labels=None, row_mask=0, max_centre_distance=float("inf"), yaw_period=0.0, capacity=None):
         """(a, b, stat, yaw_offset, counts): the pairs a < b of this map's objects whose difference, on the rows of row_mask, is within `gate` in units of its own
         covariance, in (a, b) order; counts = (found, tested, singular).  capacity None: a count-only call, then one of the exact size."""
-        try:
-            f = getattr(self._lib, self._pre + "map_match")
-        except AttributeError:
-            raise ObviError("%smap_match: this library cannot match objects of a map (include/obvi_map_match.h is served by libobvi_ba.so only)" % self._pre)
-        f.restype = C.c_int
+        f = self._entry("map_match", "obvi_map_match.h")
         lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.int32).ravel()
         if lab is not None and len(lab) != self.n_objects:
             raise ObviError("map_match: labels must name every object of the map")
         counts = np.zeros(3, np.int64)
 
-        def call(cap, a, b, s, w):
+        def call(cap, arrays):
+            a, b, s, w = arrays or (None,) * 4
             ba._check(f(ba._h, self._m, _ptr(lab, C.c_int32), C.c_uint32(int(row_mask)), C.c_double(gate), C.c_double(max_centre_distance), C.c_double(yaw_period),
                         C.c_int64(cap), _ptr(a, C.c_uint32), _ptr(b, C.c_uint32), _ptr(s, C.c_double), _ptr(w, C.c_double), _ptr(counts, C.c_int64)), "map_match")
 
-        counted = capacity is None
-        if counted:
-            call(0, None, None, None, None)
-            capacity = counts[0]
-        capacity = int(capacity)
-        if capacity < 0:
-            call(capacity, None, None, None, None)                     # refused: raises
-        a, b, s, w = np.zeros(capacity, np.uint32), np.zeros(capacity, np.uint32), np.zeros(capacity), np.zeros(capacity)
-        if capacity > 0:
-            call(capacity, a, b, s, w)
-        elif not counted:
-            call(0, None, None, None, None)
-        k = min(capacity, int(counts[0]))
+        (a, b, s, w), k = _count_then_fill(capacity, counts, 0, call, lambda cap: (np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros(cap), np.zeros(cap)))
         return a[:k], b[:k], s[:k], w[:k], tuple(int(c) for c in counts)
 
     # ---- another frame, and two maps in one (include/obvi_map_frame.h) ----
-    def _frame_fn(self, name):
-        try:
-            f = getattr(self._lib, self._pre + name)
-        except AttributeError:
-            raise ObviError("%s%s: this library cannot move or join maps (include/obvi_map_frame.h is served by libobvi_ba.so only)" % (self._pre, name))
-        f.restype = C.c_int
-        return f
-
     def transform(self, ba, transform, cov=None):
         """A new Map: this one moved into another frame by T_new<-old = transform ([4] tx ty tz psi for od 7, [6] translation and axis-angle for od 9), whose
         covariance is cov ([dT][dT]; None: the transform is exact).  Same objects, same numbers."""
@@ -321,13 +312,13 @@ class Map:
         t = _f64(transform, (dT,))
         s = None if cov is None else _f64(cov, (dT, dT))
         new = C.c_void_p()
-        rc = self._frame_fn("map_transform")(ba._h, self._m, _ptr(t, C.c_double), _ptr(s, C.c_double), C.byref(new))
+        rc = self._entry("map_transform", "obvi_map_frame.h")(ba._h, self._m, _ptr(t, C.c_double), _ptr(s, C.c_double), C.byref(new))
         return self._conditioned(ba, rc, new, "map_transform")
 
     def join(self, ba, other):
         """A new Map of this one's objects followed by `other`'s, the two uncorrelated: blockdiag of the covariances, copied as the device holds them."""
         new = C.c_void_p()
-        rc = self._frame_fn("map_join")(ba._h, self._m, other._m, C.byref(new))
+        rc = self._entry("map_join", "obvi_map_frame.h")(ba._h, self._m, other._m, C.byref(new))
         return self._conditioned(ba, rc, new, "map_join")
 
     # ---- where another map lies in this one (include/obvi_map_locate.h) ----
@@ -336,11 +327,7 @@ class Map:
         T_self<-other = (tx ty tz psi) that lay `other`'s object centres onto this map's, best first; counts = (seeds tested, seeds compatible, hypotheses with
         >= min_inliers).  move is what Map.transform of `other` takes: transform itself for od 7, (t, 0, 0, psi) for od 9.  capacity None: a count-only
         call, then one of the exact size."""
-        try:
-            f = getattr(self._lib, self._pre + "map_locate")
-        except AttributeError:
-            raise ObviError("%smap_locate: this library cannot locate a map in another (include/obvi_map_locate.h is served by libobvi_ba.so only)" % self._pre)
-        f.restype = C.c_int
+        f = self._entry("map_locate", "obvi_map_locate.h")
         na, nb = self.n_objects, other.n_objects
         la = None if labels is None else np.ascontiguousarray(labels, dtype=np.int32).ravel()
         lb = None if other_labels is None else np.ascontiguousarray(other_labels, dtype=np.int32).ravel()
@@ -349,24 +336,15 @@ class Map:
         params = LocateParams(float(pair_min_distance), float(pair_tolerance), float(inlier_gate), int(min_inliers), int(refine_iterations))
         counts = np.zeros(3, np.int64)
 
-        def call(cap, seed, t, cov, inl, cost, partner):
+        def call(cap, arrays):
+            seed, t, cov, inl, cost, partner = arrays or (None,) * 6
             ba._check(f(ba._h, self._m, other._m, _ptr(la, C.c_int32), _ptr(lb, C.c_int32), C.byref(params), C.c_int64(cap), _ptr(seed, C.c_uint32), _ptr(t, C.c_double),
                         _ptr(cov, C.c_double), _ptr(inl, C.c_int32), _ptr(cost, C.c_double), _ptr(partner, C.c_int32), _ptr(counts, C.c_int64)), "map_locate")
 
-        counted = capacity is None
-        if counted:
-            call(0, None, None, None, None, None, None)
-            capacity = counts[2]
-        capacity = int(capacity)
-        if capacity < 0:
-            call(capacity, None, None, None, None, None, None)         # refused: raises
-        seed, t, cov = np.zeros((capacity, 4), np.uint32), np.zeros((capacity, 4)), np.zeros((capacity, 4, 4))
-        inl, cost, partner = np.zeros(capacity, np.int32), np.zeros(capacity), np.full((capacity, nb), -1, np.int32)
-        if capacity > 0:
-            call(capacity, seed, t, cov, inl, cost, partner)
-        elif not counted:
-            call(0, None, None, None, None, None, None)
-        k = min(capacity, int(counts[2]))
+        def alloc(cap):
+            return (np.zeros((cap, 4), np.uint32), np.zeros((cap, 4)), np.zeros((cap, 4, 4)), np.zeros(cap, np.int32), np.zeros(cap), np.full((cap, nb), -1, np.int32))
+
+        (seed, t, cov, inl, cost, partner), k = _count_then_fill(capacity, counts, 2, call, alloc)
         move = t[:k].copy() if self.od == 7 else np.concatenate([t[:k, :3], np.zeros((k, 2)), t[:k, 3:]], axis=1)
         return Located(seed[:k], t[:k], cov[:k], inl[:k], cost[:k], partner[:k], tuple(int(c) for c in counts), move)
 
@@ -393,14 +371,8 @@ class Map:
 def map_match_resolve(od, a, b, stat, max_pairs=None, library=None, prefix="obvi_"):
     """(drop, keep, sel): candidate pairs a < b with their statistics (Map.match) resolved, greedily in ascending (stat, a, b) order, into lists Map.merge accepts
     as they are -- no object dropped twice, no dropped object kept; sel[i] is the position of selected pair i in the input.  Host only: no handle, no device."""
-    path = library or default_library_path()
-    if not os.path.exists(path):
-        raise ObviError("%s not found: build it with __graft_entry__.build() -- there is no CPU fallback" % path)
-    try:
-        f = getattr(C.CDLL(path), prefix + "map_match_resolve")
-    except AttributeError:
-        raise ObviError("%smap_match_resolve: this library cannot match objects of a map (include/obvi_map_match.h is served by libobvi_ba.so only)" % prefix)
-    f.restype = C.c_int
+    path = _library_path(library)
+    f = _entry(C.CDLL(path), prefix, "map_match_resolve", "obvi_map_match.h")
     ia, ib = np.ascontiguousarray(a, dtype=np.uint32).ravel(), np.ascontiguousarray(b, dtype=np.uint32).ravel()
     st = _f64(stat).ravel()
     if not len(ia) == len(ib) == len(st):
@@ -420,14 +392,8 @@ def map_match_resolve(od, a, b, stat, max_pairs=None, library=None, prefix="obvi
 def bbox_assign(is_match, score, n_pending, library=None, prefix="obvi_"):
     """(assigned, is_new) of the boxes of one round (BundleAdjuster.bbox_associate): the matches taken greedily by descending score, ties by box then candidate
     index; a box left over opens a new pending object numbered from n_pending upwards.  Host only: no handle, no device."""
-    path = library or default_library_path()
-    if not os.path.exists(path):
-        raise ObviError("%s not found: build it with __graft_entry__.build() -- there is no CPU fallback" % path)
-    try:
-        f = getattr(C.CDLL(path), prefix + "bbox_frontend_assign")
-    except AttributeError:
-        raise ObviError("%sbbox_frontend_assign: this library cannot associate bounding boxes (include/obvi_bbox_frontend.h is served by libobvi_ba.so only)" % prefix)
-    f.restype = C.c_int
+    path = _library_path(library)
+    f = _entry(C.CDLL(path), prefix, "bbox_frontend_assign", "obvi_bbox_frontend.h")
     m, sc = np.ascontiguousarray(is_match, dtype=np.uint8), _f64(score)
     if m.ndim != 2 or m.shape != sc.shape:
         raise ObviError("bbox_assign: is_match and score must be [n_box][n_cand] both")
@@ -442,9 +408,7 @@ class BundleAdjuster:
     """One handle == one GPU == one HIP stream (include/obvi_ba.h)."""
 
     def __init__(self, device_id=0, library=None, prefix="obvi_", reprojection_variant=0, deterministic=False, object_block_size=7):
-        path = library or default_library_path()
-        if not os.path.exists(path):
-            raise ObviError("%s not found: build it with __graft_entry__.build() -- there is no CPU fallback" % path)
+        path = _library_path(library)
         self._lib = C.CDLL(path)
         self._pre = prefix
         self._h = C.c_void_p()
@@ -457,9 +421,10 @@ class BundleAdjuster:
         self.P = self.L = self.O = 0
 
     def _fn(self, name):
-        f = getattr(self._lib, self._pre + name)
-        f.restype = C.c_int64 if name in ("ba_num_residuals", "ba_num_factors") else C.c_int
-        return f
+        return _entry(self._lib, self._pre, name, restype=C.c_int64 if name in ("ba_num_residuals", "ba_num_factors") else C.c_int)
+
+    def _entry(self, name, header):
+        return _entry(self._lib, self._pre, name, header)
 
     def _check(self, rc, what):
         if rc != 0:
@@ -558,11 +523,7 @@ class BundleAdjuster:
 
     def set_map_pair_priors(self, obj_a, obj_b, mean_a, mean_b, cov_joint, form=None, huber=1.0):
         """Joint Gaussian priors on object pairs (include/obvi_map_prior.h): cov_joint [n][2od][2od]; form None = all joint, else MAP_PAIR_JOINT / MAP_PAIR_CONDITIONAL per pair."""
-        try:
-            f = getattr(self._lib, self._pre + "map_set_pair_priors")
-        except AttributeError:
-            raise ObviError("%smap_set_pair_priors: this library has no map pair priors (include/obvi_map_prior.h is served by libobvi_ba.so only)" % self._pre)
-        f.restype = C.c_int
+        f = self._entry("map_set_pair_priors", "obvi_map_prior.h")
         ia = np.ascontiguousarray(obj_a, dtype=np.uint32)
         ib = np.ascontiguousarray(obj_b, dtype=np.uint32)
         n2 = 2 * self.od
@@ -575,11 +536,7 @@ class BundleAdjuster:
     def set_map_group_priors(self, groups, means, covs, huber=1.0):
         """Joint Gaussian priors on groups of objects (include/obvi_map_group_prior.h): groups = a list of object-index lists, means = per group [k][od],
         covs = per group [k od][k od]; empty lists clear the factors."""
-        try:
-            f = getattr(self._lib, self._pre + "map_set_group_priors")
-        except AttributeError:
-            raise ObviError("%smap_set_group_priors: this library has no map group priors (include/obvi_map_group_prior.h is served by libobvi_ba.so only)" % self._pre)
-        f.restype = C.c_int
+        f = self._entry("map_set_group_priors", "obvi_map_group_prior.h")
         sizes = [len(g) for g in groups]
         ptr = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
         idx = np.ascontiguousarray(np.concatenate([np.asarray(g, dtype=np.uint32).ravel() for g in groups]) if groups else np.zeros(0), dtype=np.uint32)
@@ -595,11 +552,7 @@ class BundleAdjuster:
     def set_map_group_priors_from_map(self, map, groups, map_idx, huber=1.0):
         """Group priors cut from a device-resident map (include/obvi_map_resident.h): groups = a list of object-index lists, map_idx = per group the members' map
         objects; means and covariances are the map's, gathered and factored on the device.  Empty lists clear the factors."""
-        try:
-            f = getattr(self._lib, self._pre + "map_set_group_priors_from_map")
-        except AttributeError:
-            raise ObviError("%smap_set_group_priors_from_map: this library has no map group priors (include/obvi_map_resident.h is served by libobvi_ba.so only)" % self._pre)
-        f.restype = C.c_int
+        f = self._entry("map_set_group_priors_from_map", "obvi_map_resident.h")
         sizes = [len(g) for g in groups]
         ptr = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
         idx = np.ascontiguousarray(np.concatenate([np.asarray(g, dtype=np.uint32).ravel() for g in groups]) if groups else np.zeros(0), dtype=np.uint32)
@@ -670,22 +623,14 @@ class BundleAdjuster:
         return out
 
     # ---- covariance blocks by selected inversion (include/obvi_cov.h; not in the oracle: an oracle-backed adjuster raises) ----
-    def _cov_fn(self, name):
-        try:
-            f = getattr(self._lib, self._pre + name)
-        except AttributeError:
-            raise ObviError("%s%s: this library has no selected-inversion covariance (include/obvi_cov.h is served by libobvi_ba.so only)" % (self._pre, name))
-        f.restype = C.c_int
-        return f
-
     def covariance_compute(self):
         """Linearise at the current estimate, factorise the undamped reduced system and invert it on the factor's tile pattern."""
-        self._check(self._cov_fn("cov_compute")(self._h), "cov_compute")
+        self._check(self._entry("cov_compute", "obvi_cov.h")(self._h), "cov_compute")
 
     def covariance_compute_pairs(self, kind_a, idx_a, kind_b, idx_b):
         """covariance_compute, after which cross_covariances also serves the pairs declared here: any kinds (0 pose / 1 feature / 2 object), on the pattern or not."""
         ka, ia, kb, ib = self._cov_pairs(kind_a, idx_a, kind_b, idx_b)
-        self._check(self._cov_fn("cov_compute_pairs")(self._h, C.c_int64(len(ia)), _ptr(ka, C.c_uint8), _ptr(ia, C.c_uint32), _ptr(kb, C.c_uint8), _ptr(ib, C.c_uint32)),
+        self._check(self._entry("cov_compute_pairs", "obvi_cov.h")(self._h, C.c_int64(len(ia)), _ptr(ka, C.c_uint8), _ptr(ia, C.c_uint32), _ptr(kb, C.c_uint8), _ptr(ib, C.c_uint32)),
                     "cov_compute_pairs")
 
     def covariance_debug_compute_pairs(self, kind_a=(), idx_a=(), kind_b=(), idx_b=(), lhs_in=None, m_cap=4096):
@@ -700,7 +645,7 @@ class BundleAdjuster:
             m_cap = len(lin)                      # (a handle whose system has more rows refuses; fewer is caught below)
         lhs, row = np.zeros((m_cap, m_cap)), np.full(m_cap, -1, dtype=np.int32)
         m = C.c_int32(0)
-        rc = self._cov_fn("cov_debug_compute_pairs")(self._h, C.c_int64(len(ia)), _ptr(ka, C.c_uint8), _ptr(ia, C.c_uint32), _ptr(kb, C.c_uint8), _ptr(ib, C.c_uint32),
+        rc = self._entry("cov_debug_compute_pairs", "obvi_cov.h")(self._h, C.c_int64(len(ia)), _ptr(ka, C.c_uint8), _ptr(ia, C.c_uint32), _ptr(kb, C.c_uint8), _ptr(ib, C.c_uint32),
                                                      _ptr(lin, C.c_double) if lhs_in is not None else None, _ptr(lhs, C.c_double), _ptr(row, C.c_int32),
                                                      C.c_int32(m_cap), C.byref(m))
         if lhs_in is not None and rc in (0, -6) and m.value != len(lin):
@@ -712,7 +657,7 @@ class BundleAdjuster:
     def _cov_own(self, name, idx, dim):
         i = np.ascontiguousarray(idx, dtype=np.uint32)
         out = np.zeros((len(i), dim, dim))
-        self._check(self._cov_fn(name)(self._h, C.c_int64(len(i)), _ptr(i, C.c_uint32), _ptr(out, C.c_double)), name)
+        self._check(self._entry(name, "obvi_cov.h")(self._h, C.c_int64(len(i)), _ptr(i, C.c_uint32), _ptr(out, C.c_double)), name)
         return out
 
     def pose_covariances(self, idx):
@@ -738,7 +683,7 @@ class BundleAdjuster:
         sz = dim(ka) * dim(kb)
         off = np.ascontiguousarray(np.concatenate([[0], np.cumsum(sz)]).astype(np.int64))
         out = np.zeros(int(off[-1]))
-        self._check(self._cov_fn("cov_cross_blocks")(self._h, C.c_int64(len(ia)), _ptr(ka, C.c_uint8), _ptr(ia, C.c_uint32), _ptr(kb, C.c_uint8), _ptr(ib, C.c_uint32),
+        self._check(self._entry("cov_cross_blocks", "obvi_cov.h")(self._h, C.c_int64(len(ia)), _ptr(ka, C.c_uint8), _ptr(ia, C.c_uint32), _ptr(kb, C.c_uint8), _ptr(ib, C.c_uint32),
                                                      _ptr(out, C.c_double), _ptr(off, C.c_int64)), "cov_cross_blocks")
         da, db = dim(ka), dim(kb)
         return [out[off[i]:off[i + 1]].reshape(da[i], db[i]) for i in range(len(ia))]
@@ -747,14 +692,14 @@ class BundleAdjuster:
         """1 per pair whose cross block cross_covariances can serve."""
         ka, ia, kb, ib = self._cov_pairs(kind_a, idx_a, kind_b, idx_b)
         on = np.zeros(len(ia), dtype=np.uint8)
-        self._check(self._cov_fn("cov_on_pattern")(self._h, C.c_int64(len(ia)), _ptr(ka, C.c_uint8), _ptr(ia, C.c_uint32), _ptr(kb, C.c_uint8), _ptr(ib, C.c_uint32),
+        self._check(self._entry("cov_on_pattern", "obvi_cov.h")(self._h, C.c_int64(len(ia)), _ptr(ka, C.c_uint8), _ptr(ia, C.c_uint32), _ptr(kb, C.c_uint8), _ptr(ib, C.c_uint32),
                                                    _ptr(on, C.c_uint8)), "cov_on_pattern")
         return on
 
     def covariance_stats(self):
         """(linearise + factorise ms, selected inversion ms, scratch bytes) of the last covariance_compute."""
         a, b, n = C.c_double(0.0), C.c_double(0.0), C.c_int64(0)
-        self._check(self._cov_fn("cov_get_stats")(self._h, C.byref(a), C.byref(b), C.byref(n)), "cov_get_stats")
+        self._check(self._entry("cov_get_stats", "obvi_cov.h")(self._h, C.byref(a), C.byref(b), C.byref(n)), "cov_get_stats")
         return a.value, b.value, n.value
 
     def set_parameter_priors(self, block_kind, block_idx, param_idx, mean, std_dev):
@@ -771,11 +716,6 @@ class BundleAdjuster:
         return p, l, o
 
     # ---- visual-feature front-end gating (include/obvi_frontend.h) --------------------------
-    def _frontend_fn(self, name):
-        f = getattr(self._lib, self._pre + name)      # obvi_frontend_* / oracle_frontend_*
-        f.restype = C.c_int
-        return f
-
     def epipolar_votes(self, K, ext, poses, cand_pose, cand_cam, cand_pixel, ref_ptr, ref_pose, ref_cam, ref_pixel, ref_frame, ref_skip, params=None):
         K, ext, poses = _f64(K, (-1, 4)), _f64(ext, (-1, 7)), _f64(poses, (-1, 6))
         cp = np.ascontiguousarray(cand_pose, dtype=np.uint32); cc = np.ascontiguousarray(cand_cam, dtype=np.uint16); cx = _f64(cand_pixel, (-1, 2))
@@ -784,7 +724,7 @@ class BundleAdjuster:
         prm = params or EpipolarParams()
         n = len(cp)
         votes, voters, inl = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint8)
-        self._check(self._frontend_fn("frontend_epipolar_votes")(self._h, C.c_int32(len(K)), _ptr(K, C.c_double), _ptr(ext, C.c_double), C.c_int64(len(poses)), _ptr(poses, C.c_double),
+        self._check(self._entry("frontend_epipolar_votes", "obvi_frontend.h")(self._h, C.c_int32(len(K)), _ptr(K, C.c_double), _ptr(ext, C.c_double), C.c_int64(len(poses)), _ptr(poses, C.c_double),
                                                                 C.c_int64(n), _ptr(cp, C.c_uint32), _ptr(cc, C.c_uint16), _ptr(cx, C.c_double), _ptr(rp, C.c_uint64), _ptr(ro, C.c_uint32),
                                                                 _ptr(rc, C.c_uint16), _ptr(rx, C.c_double), _ptr(rf, C.c_uint32), _ptr(rs, C.c_uint8), C.byref(prm),
                                                                 _ptr(votes, C.c_uint32), _ptr(voters, C.c_uint32), _ptr(inl, C.c_uint8)), "frontend_epipolar_votes")
@@ -796,7 +736,7 @@ class BundleAdjuster:
         rp = np.ascontiguousarray(ref_ptr, dtype=np.uint64); ro = np.ascontiguousarray(ref_pose, dtype=np.uint32); rc = np.ascontiguousarray(ref_cam, dtype=np.uint16)
         rx = _f64(ref_pixel, (-1, 2))
         err = np.zeros((len(ro), 2))
-        self._check(self._frontend_fn("frontend_epipolar_errors")(self._h, C.c_int32(len(K)), _ptr(K, C.c_double), _ptr(ext, C.c_double), C.c_int64(len(poses)), _ptr(poses, C.c_double),
+        self._check(self._entry("frontend_epipolar_errors", "obvi_frontend.h")(self._h, C.c_int32(len(K)), _ptr(K, C.c_double), _ptr(ext, C.c_double), C.c_int64(len(poses)), _ptr(poses, C.c_double),
                                                                  C.c_int64(len(cp)), _ptr(cp, C.c_uint32), _ptr(cc, C.c_uint16), _ptr(cx, C.c_double), _ptr(rp, C.c_uint64), _ptr(ro, C.c_uint32),
                                                                  _ptr(rc, C.c_uint16), _ptr(rx, C.c_double), _ptr(err, C.c_double)), "frontend_epipolar_errors")
         return err
@@ -806,7 +746,7 @@ class BundleAdjuster:
         op = np.ascontiguousarray(obs_ptr, dtype=np.uint64); px = _f64(pixels, (-1, 2))
         prm = params or ParallaxParams()
         out = np.zeros(len(fp) - 1, np.uint8)
-        self._check(self._frontend_fn("frontend_parallax")(self._h, C.c_int64(len(fp) - 1), _ptr(fp, C.c_uint64), _ptr(hp, C.c_uint8), _ptr(po, C.c_double), _ptr(op, C.c_uint64),
+        self._check(self._entry("frontend_parallax", "obvi_frontend.h")(self._h, C.c_int64(len(fp) - 1), _ptr(fp, C.c_uint64), _ptr(hp, C.c_uint8), _ptr(po, C.c_double), _ptr(op, C.c_uint64),
                                                           _ptr(px, C.c_double), C.byref(prm), _ptr(out, C.c_uint8)), "frontend_parallax")
         return out
 
@@ -824,7 +764,7 @@ class BundleAdjuster:
         nf, nb, nc, nv = len(fi), len(bc), len(cl), len(fp) - 1
         in_box, count, overlap = np.zeros((nb, nf), np.uint8), np.zeros(nb, np.uint32), np.zeros((nb, nv), np.uint32)
         match, score = np.zeros((nb, nc), np.uint8), np.full((nb, nc), np.nan)
-        self._check(self._frontend_fn("bbox_frontend_associate")(self._h, C.c_int64(nf), _ptr(fi, C.c_uint64), _ptr(fx, C.c_double), C.c_int64(nb), _ptr(bc, C.c_double), _ptr(bl, C.c_int32),
+        self._check(self._entry("bbox_frontend_associate", "obvi_bbox_frontend.h")(self._h, C.c_int64(nf), _ptr(fi, C.c_uint64), _ptr(fx, C.c_double), C.c_int64(nb), _ptr(bc, C.c_double), _ptr(bl, C.c_int32),
                                                                 C.c_int64(nc), _ptr(cl, C.c_int32), C.c_int64(nv), _ptr(vp, C.c_uint64), C.c_int64(len(vf)), _ptr(fp, C.c_uint64),
                                                                 _ptr(vf, C.c_uint64), C.byref(prm), _ptr(in_box, C.c_uint8), _ptr(count, C.c_uint32), _ptr(overlap, C.c_uint32),
                                                                 _ptr(match, C.c_uint8), _ptr(score, C.c_double)), "bbox_frontend_associate")
@@ -896,11 +836,7 @@ class BundleAdjuster:
 
     def map_allow_exchange(self, on=True):
         """Joint map priors and Map.condition_on / extend_on / from_handle on a handle that exchanges shared objects (include/obvi_map_shared.h): off by default."""
-        try:
-            f = getattr(self._lib, self._pre + "map_allow_exchange")
-        except AttributeError:
-            raise ObviError("%smap_allow_exchange: this library has no collective map entries (include/obvi_map_shared.h is served by libobvi_ba.so only)" % self._pre)
-        f.restype = C.c_int
+        f = self._entry("map_allow_exchange", "obvi_map_shared.h")
         self._check(f(self._h, C.c_int32(int(on))), "map_allow_exchange")
 
     def measure_peaks(self):

@@ -34,6 +34,7 @@ import map_match_cases
 import map_merge_cases
 from map_update_cases import LD, N_SMALL, inverse, map_information, map_of, sym
 from test_gpu_map_pair_priors import inv_ld, spd
+from map_support import errors  # noqa: F401  (the tests call it as cases.errors)
 
 N_SWEEP = 33
 DT = {7: 4, 9: 6}
@@ -242,11 +243,6 @@ def reference(which, od, tname, with_sigma):
 
 def leading(mean, cov, n, od):
     return np.ascontiguousarray(mean[:n]), np.ascontiguousarray(cov[:n * od, :n * od])
-
-
-def errors(mean, cov, mean_ref, cov_ref):
-    """(covariance, means): the largest difference over the largest entry of the reference."""
-    return (float(np.abs(cov - cov_ref).max() / np.abs(cov_ref).max()), float(np.abs(mean - mean_ref).max() / np.abs(mean_ref).max()))
 
 
 # ---- the chain ---------------------------------------------------------------------------------------------------------------------------------------------------

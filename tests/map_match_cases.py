@@ -13,7 +13,8 @@ whose residuals are long double; s is at a minimum in z, so what is left of the 
 
 Maps: the 24- and 70-object maps of tests/map_update_cases.py; every leading sub-map of the large one (objects 0 .. n - 1, n = 1 .. 33: its pairs are the large
 map's pairs with b < n, so their reference is a slice of the large map's); the small map grown by five noisy copies of five of its objects (`planted`), one of
-them turned by pi + 0.05 in a variant (od 7); and a map with two exact copies, E Cr E^T copied entry by entry, whose pairs (2, 6) and (4, 7) have T = 0.
+them turned by pi + 0.05 in a variant (od 7); a 258-object map whose leading sub-maps of 257 and 258 objects stand at the edge of the scatter's 256-wide sweep
+(`sweep`); and a map with two exact copies, E Cr E^T copied entry by entry, whose pairs (2, 6) and (4, 7) have T = 0.
 
 A gate or a distance is never a literal: `midpoint` puts it midway between two neighbours of the sorted long-double reference where their relative gap is at
 least 1e-9, so membership never hangs on a rounding."""
@@ -26,6 +27,7 @@ from map_update_cases import LD, N_SMALL, map_information, map_of, sym
 from test_gpu_map_pair_priors import inv_ld, spd
 
 N_SWEEP = 33                     # leading sub-maps 1 .. 33: across the pair kernel's blocks of 9 (od 7) and 7 (od 9) objects at B, B + 1, 2 B + 1 and beyond
+N_EDGE = 258                    # the scatter's sweep of 256 candidates of a row: row 0 of 257 objects fills one exactly, of 258 objects starts a second
 N_COPIES = 5
 YAW_TURN = np.pi + 0.05
 MASKS = ("all", "centre", "row", "no_yaw")
@@ -102,9 +104,20 @@ def copies_map(od):
     return mean, cov
 
 
+@functools.lru_cache(maxsize=None)
+def sweep_map(od):
+    """N_EDGE objects: row 0 of the leading sub-maps of N_EDGE - 1 and N_EDGE objects has exactly one 256-wide sweep of candidates, and one more than a sweep."""
+    rng = np.random.default_rng(740 + od)
+    mean, cov = rng.normal(size=(N_EDGE, od)), spd(rng, N_EDGE * od)
+    mean.setflags(write=False); cov.setflags(write=False)
+    return mean, cov
+
+
 def case_map(name, od):
     if name in ("small", "large"):
         return map_of(name, od)
+    if name == "sweep":
+        return sweep_map(od)
     if name == "copies":
         return copies_map(od)
     return planted_map(od, yaw=(name == "planted_yaw"))

@@ -26,8 +26,9 @@ import map_extend_cases as cases
 import obvi_ba
 import synth
 from map_update_cases import N_SMALL, rows_of, selection, small_map, sym
-from test_gpu_map_pair_priors import base_problem, inv_ld, objects_only, product
-from test_gpu_map_resident import N_MAP, det_objects_only, status_of, the_map
+from test_gpu_map_pair_priors import base_problem, inv_ld, product
+from test_gpu_map_resident import N_MAP, the_map
+from map_support import errors, lender, objects_only, records, status_of
 
 pytestmark = pytest.mark.gpu
 
@@ -39,19 +40,6 @@ OLD_OBJ, OLD_MAP, NEW_OBJ = [0, 3, 1], [41, 7, 66], [4, 2]
 def device_map(which, od):
     mean, cov = cases.map_of(which, od)
     return obvi_ba.Map.create(mean, cov, object_block_size=od, library=helpers.PRODUCT_LIB)
-
-
-def lender(od, deterministic=False):
-    """A handle that only lends its stream and workspaces."""
-    return (det_objects_only if deterministic else objects_only)(np.zeros((1, od)), od)
-
-
-def errors(mean, cov, mean_ref, cov_ref):
-    return (float(np.abs(cov - cov_ref).max() / np.abs(cov_ref).max()), float(np.abs(mean - mean_ref).max() / np.abs(mean_ref).max()))
-
-
-def records(ba):
-    return [(i.iteration, i.step_is_successful, i.cost) for i in ba.iterations()]
 
 
 # ---- 1. / 2. tile edges, host-pointer form; the old block against the conditioning entry ------------------------------------------------------------

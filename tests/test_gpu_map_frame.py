@@ -14,8 +14,9 @@ import helpers
 import map_frame_cases as cases
 import obvi_ba
 from map_update_cases import N_SMALL, rows_of, sym
-from test_gpu_map_pair_priors import inv_ld, objects_only
-from test_gpu_map_resident import N_MAP, det_objects_only, status_of
+from test_gpu_map_pair_priors import inv_ld
+from test_gpu_map_resident import N_MAP
+from map_support import last_error, lender, objects_only, status_of
 
 pytestmark = pytest.mark.gpu
 
@@ -26,22 +27,11 @@ def device_map(mean, cov, od):
     return obvi_ba.Map.create(mean, cov, object_block_size=od, library=helpers.PRODUCT_LIB)
 
 
-def lender(od, deterministic=False):
-    """A handle that only lends its stream and workspaces."""
-    return (det_objects_only if deterministic else objects_only)(np.zeros((1, od)), od)
-
-
 def moved(mp, ba, transform, cov=None):
     """(mean, cov) of a move whose map is read back and destroyed."""
     with mp.transform(ba, transform, cov) as new:
         assert new.n_objects == mp.n_objects
         return new.get()
-
-
-def last_error(ba):
-    f = ba._fn("ba_last_error")
-    f.restype = C.c_char_p
-    return (f(ba._h) or b"").decode()
 
 
 def dimension_rows(n, od):

@@ -14,8 +14,8 @@ import helpers
 import map_frame_cases as frame
 import map_locate_cases as cases
 import obvi_ba
-from test_gpu_map_pair_priors import objects_only
-from test_gpu_map_resident import N_MAP, det_objects_only, status_of
+from test_gpu_map_resident import N_MAP
+from map_support import last_error, lender, objects_only, status_of
 
 pytestmark = pytest.mark.gpu
 
@@ -25,17 +25,6 @@ LD = np.longdouble
 
 def device_map(mean, cov, od):
     return obvi_ba.Map.create(mean, cov, object_block_size=od, library=helpers.PRODUCT_LIB)
-
-
-def lender(od, deterministic=False):
-    """A handle that only lends its stream and workspaces."""
-    return (det_objects_only if deterministic else objects_only)(np.zeros((1, od)), od)
-
-
-def last_error(ba):
-    f = ba._fn("ba_last_error")
-    f.restype = C.c_char_p
-    return (f(ba._h) or b"").decode()
 
 
 def ptr(a):

@@ -18,8 +18,8 @@ import helpers
 import map_match_cases as cases
 import obvi_ba
 from map_update_cases import N_SMALL
-from test_gpu_map_pair_priors import objects_only
-from test_gpu_map_resident import N_MAP, det_objects_only, status_of, the_map
+from test_gpu_map_resident import N_MAP, the_map
+from map_support import det_objects_only, last_error, objects_only, status_of
 
 pytestmark = pytest.mark.gpu
 
@@ -87,6 +87,27 @@ def test_leading_sub_maps_of_one_to_thirty_three_objects(od):
                 gate, _ = cases.midpoint(ref.stat, count)
                 worst = max(worst, check(mp, ba, ref, od, "all", gate))
     print("od %d, sub-maps of 1 .. %d objects: statistics within %.2e" % (od, cases.N_SWEEP, worst))
+    assert worst <= 1e-12
+
+
+def test_a_row_of_one_sweep_of_candidates_and_of_one_more():
+    """The scatter walks a row's candidates 256 at a time: row 0 of 257 objects has exactly one sweep of them, of 258 objects one more than a sweep."""
+    od = 7
+    full = cases.reference("sweep", od)
+    assert not full.singular.any()
+    ba = lender(od)
+    worst = 0.0
+    for n in (cases.N_EDGE - 1, cases.N_EDGE):
+        ref = cases.leading(full, n)
+        assert int((ref.a == 0).sum()) == n - 1 and n - 1 in (256, 257)
+        p = n * (n - 1) // 2
+        with device_map("sweep", od, n) as mp:
+            worst = max(worst, check(mp, ba, ref, od, "all", cases.midpoint(ref.stat, p // 2)[0]))   # half of the pairs
+            gate, found = cases.midpoint(ref.stat, p)                                                 # all of them: row 0 reports every candidate
+            assert found == p
+            for capacity in (None, 256, 257):                                                         # 256: the reported prefix ends at the sweep's edge
+                worst = max(worst, check(mp, ba, ref, od, "all", gate, capacity=capacity))
+    print("od %d, sub-maps of %d and %d objects: statistics within %.2e" % (od, cases.N_EDGE - 1, cases.N_EDGE, worst))
     assert worst <= 1e-12
 
 
@@ -190,12 +211,6 @@ def test_the_same_call_twice_and_on_either_kind_of_handle_gives_the_same_bits_an
     assert np.array_equal(after[0], mean) and np.array_equal(after[1], cov)         # the map is as it was
     assert status_of(lambda: user.solve(helpers.ba_params(max_it=3))) == 0          # the handle is usable
     user.close()
-
-
-def last_error(ba):
-    f = ba._fn("ba_last_error")
-    f.restype = C.c_char_p
-    return (f(ba._h) or b"").decode()
 
 
 def test_refusals_leave_the_handle_and_the_outputs_as_they_were():

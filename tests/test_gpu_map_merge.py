@@ -15,8 +15,9 @@ import map_extend_cases
 import map_merge_cases as cases
 import obvi_ba
 from map_update_cases import N_SMALL, posterior, rows_of, sym, update_formula
-from test_gpu_map_pair_priors import inv_ld, objects_only, spd
-from test_gpu_map_resident import N_MAP, det_objects_only, status_of, the_map
+from test_gpu_map_pair_priors import inv_ld, spd
+from test_gpu_map_resident import N_MAP, the_map
+from map_support import errors, lender, objects_only, status_of
 
 pytestmark = pytest.mark.gpu
 
@@ -26,15 +27,6 @@ T = obvi_ba.FACTOR_MAP_GROUP_PRIOR
 def device_map(which, od):
     mean, cov = cases.map_of(which, od)
     return obvi_ba.Map.create(mean, cov, object_block_size=od, library=helpers.PRODUCT_LIB)
-
-
-def lender(od, deterministic=False):
-    """A handle that only lends its stream and workspaces."""
-    return (det_objects_only if deterministic else objects_only)(np.zeros((1, od)), od)
-
-
-def errors(mean, cov, mean_ref, cov_ref):
-    return (float(np.abs(cov - cov_ref).max() / np.abs(cov_ref).max()), float(np.abs(mean - mean_ref).max() / np.abs(mean_ref).max()))
 
 
 def merged(mp, ba, *args):

@@ -13,6 +13,7 @@ import helpers
 import obvi_ba
 import synth
 from helpers import rel_err
+from map_support import objects_only
 
 pytestmark = pytest.mark.gpu
 
@@ -234,14 +235,6 @@ def test_block_diagonal_pair_is_two_ltm_priors():
 
 
 # ---- 4. / 5. objects-only problems --------------------------------------------------------------------------------------------------------
-def objects_only(objects, od=7):
-    """One constant pose, no features, no factors but what the caller adds."""
-    ba = helpers.product_ba(object_block_size=od)
-    ba.set_cameras(synth.K_DEFAULT[None], synth.EXT_DEFAULT[None])
-    ba.set_poses(np.zeros((1, 6)), np.ones(1, np.uint8))
-    ba.set_points(np.zeros((0, 3)), np.zeros(0, np.uint8))
-    ba.set_objects(objects, np.zeros(len(objects), np.uint8))
-    return ba
 
 
 def test_a_tree_of_conditionals_is_the_exact_joint():

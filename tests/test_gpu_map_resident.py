@@ -15,9 +15,9 @@ import torch  # noqa: F401  (loaded before libobvi_ba.so: torch brings its own H
 
 import helpers
 import obvi_ba
-import synth
 from helpers import rel_err
-from test_gpu_map_pair_priors import base_problem, inv_ld, objects_only, product, spd
+from test_gpu_map_pair_priors import base_problem, inv_ld, product, spd
+from map_support import det_objects_only, objects_only, records, status_of
 
 pytestmark = pytest.mark.gpu
 
@@ -75,18 +75,6 @@ def linearised(ba):
     r, W, J1 = ba.debug_linearize(T)
     assert J1 is None
     return r, W
-
-
-def records(ba):
-    return [(i.iteration, i.step_is_successful, i.cost) for i in ba.iterations()]
-
-
-def status_of(call):
-    try:
-        call()
-    except obvi_ba.ObviError as e:
-        return int(str(e).split("status ")[1].split()[0])
-    return 0
 
 
 # ---- 1. sizes at the tile edges ------------------------------------------------------------------------------------------------------------
@@ -227,15 +215,6 @@ def test_the_same_call_twice_and_a_smaller_call_after_it(deterministic):
         assert np.array_equal(Wa[g], Wf[g]) and np.array_equal(ra[g], rf[g])
     Sa, Sf = ba.debug_reduced_system(1e300), fresh.debug_reduced_system(1e300)
     assert np.array_equal(Sa[0], Sf[0]) and np.array_equal(Sa[1], Sf[1])
-
-
-def det_objects_only(objects, od=7):
-    ba = helpers.product_ba(object_block_size=od, deterministic=True)
-    ba.set_cameras(synth.K_DEFAULT[None], synth.EXT_DEFAULT[None])
-    ba.set_poses(np.zeros((1, 6)), np.ones(1, np.uint8))
-    ba.set_points(np.zeros((0, 3)), np.zeros(0, np.uint8))
-    ba.set_objects(objects, np.zeros(len(objects), np.uint8))
-    return ba
 
 
 def test_cleared_groups_leave_no_trace():

@@ -12,15 +12,12 @@ import pytest
 
 import helpers
 import map_extend_cases as cases
+from map_support import header as _header
 
 sys.path.insert(0, helpers.ROOT)
 import __graft_entry__ as entry  # noqa: E402
 
 SYMBOLS = ["obvi_map_extend", "obvi_map_extend_on_handle", "obvi_map_select"]
-
-
-def _header(name):
-    return open(os.path.join(helpers.ROOT, "include", name)).read()
 
 
 def test_the_header_declares_the_three_entries_and_the_library_exports_them():

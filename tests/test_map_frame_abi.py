@@ -19,6 +19,7 @@ import pytest
 
 import helpers
 import map_frame_cases as cases
+from map_support import header as _header
 
 sys.path.insert(0, helpers.ROOT)
 import __graft_entry__ as entry  # noqa: E402
@@ -26,10 +27,6 @@ import __graft_entry__ as entry  # noqa: E402
 LD = np.longdouble
 SYMBOLS = ["obvi_map_join", "obvi_map_transform"]
 RESERVED = ["map_merge", "map_match", "map_update", "map_extend", "obvi_map_condition", "obvi_map_get", "obvi_map_extend", "obvi_map_select"]
-
-
-def _header(name):
-    return open(os.path.join(helpers.ROOT, "include", name)).read()
 
 
 def test_the_header_declares_the_two_entries_and_the_library_exports_them():

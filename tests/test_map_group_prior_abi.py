@@ -7,13 +7,10 @@ import re
 import sys
 
 import helpers
+from map_support import header as _header
 
 sys.path.insert(0, helpers.ROOT)
 import __graft_entry__ as entry  # noqa: E402
-
-
-def _header(name):
-    return open(os.path.join(helpers.ROOT, "include", name)).read()
 
 
 def test_the_group_prior_entry_is_declared_and_exported():

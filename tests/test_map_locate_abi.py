@@ -20,6 +20,7 @@ import pytest
 
 import helpers
 import map_locate_cases as cases
+from map_support import header as _header
 
 sys.path.insert(0, helpers.ROOT)
 import __graft_entry__ as entry  # noqa: E402
@@ -27,10 +28,6 @@ import __graft_entry__ as entry  # noqa: E402
 LD = np.longdouble
 SYMBOLS = ["obvi_map_locate"]
 RESERVED = ["map_merge", "map_match", "map_update", "map_extend", "map_frame", "obvi_map_condition", "obvi_map_get", "obvi_map_extend", "obvi_map_select", "obvi_map_join"]
-
-
-def _header(name):
-    return open(os.path.join(helpers.ROOT, "include", name)).read()
 
 
 def test_the_header_declares_the_entry_and_its_struct_and_the_library_exports_it():

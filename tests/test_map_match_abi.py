@@ -18,6 +18,7 @@ import pytest
 
 import helpers
 import map_match_cases as cases
+from map_support import header as _header
 
 sys.path.insert(0, helpers.ROOT)
 import __graft_entry__ as entry  # noqa: E402
@@ -25,10 +26,6 @@ import __graft_entry__ as entry  # noqa: E402
 SYMBOLS = ["obvi_map_match", "obvi_map_match_resolve"]
 RESERVED = ["map_merge", "map_update", "obvi_map_condition", "obvi_map_get", "map_extend", "obvi_map_extend", "obvi_map_select"]
 U32, F64 = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
-
-
-def _header(name):
-    return open(os.path.join(helpers.ROOT, "include", name)).read()
 
 
 def test_the_header_declares_the_two_entries_and_the_library_exports_them():

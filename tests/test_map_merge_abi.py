@@ -17,16 +17,13 @@ import pytest
 
 import helpers
 import map_merge_cases as cases
+from map_support import header as _header
 
 sys.path.insert(0, helpers.ROOT)
 import __graft_entry__ as entry  # noqa: E402
 
 SYMBOLS = ["obvi_map_merge"]
 RESERVED = ["map_update", "obvi_map_condition", "obvi_map_get", "map_extend", "obvi_map_extend", "obvi_map_select"]
-
-
-def _header(name):
-    return open(os.path.join(helpers.ROOT, "include", name)).read()
 
 
 def test_the_header_declares_the_one_entry_and_the_library_exports_it():

@@ -9,15 +9,12 @@ import sys
 import numpy as np
 
 import helpers
+from map_support import header as _header
 
 sys.path.insert(0, helpers.ROOT)
 import __graft_entry__ as entry  # noqa: E402
 
 SYMBOLS = ["obvi_map_create", "obvi_map_destroy", "obvi_map_num_objects", "obvi_map_set_group_priors_from_map"]
-
-
-def _header(name):
-    return open(os.path.join(helpers.ROOT, "include", name)).read()
 
 
 def _lib():

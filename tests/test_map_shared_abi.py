@@ -8,15 +8,12 @@ import re
 import sys
 
 import helpers
+from map_support import header as _header
 
 sys.path.insert(0, helpers.ROOT)
 import __graft_entry__ as entry  # noqa: E402
 
 SYMBOLS = ["obvi_map_allow_exchange"]
-
-
-def _header(name):
-    return open(os.path.join(helpers.ROOT, "include", name)).read()
 
 
 def test_the_header_declares_the_one_entry_and_the_library_exports_it():
