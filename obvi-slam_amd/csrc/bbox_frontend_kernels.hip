@@ -1,12 +1,8 @@
 // bbox_frontend_kernels.hip -- bounding-box data association on the device (include/obvi_bbox_frontend.h): one (frame, camera) round of the reference's
 // feature-based front end (feature_based_bounding_box_front_end.h:190-209, :357-479, :917-940) up to the assignment, and the greedy assignment itself
 // (bounding_box_front_end_helpers.h:125-184) on the host.  The inner work of the reference is set intersection through unordered_set look-ups: every box of the
-// frame against every earlier view of every candidate of its class.  Here the frame's features are sorted by id once on the host, and
-//   k_bbox_membership  one thread per frame feature (in sorted order): which boxes hold it, as a row of ceil(n_box / 64) 64-bit words; per-box counts from
-//                      wavefront ballots and one integer atomic per wavefront and box
-//   k_bbox_overlap     one wavefront per view: a lane looks one id of the view up in the sorted list (binary search; the list in LDS while it fits) and fetches
-//                      the bit row of the feature found; the count of a box is the popcount of the ballot of its bit
-//   k_bbox_score       one thread per (box, candidate): the largest overlap and the sum of intersection over union over the candidate's views, in view order
+// frame against every earlier view of every candidate of its class.  Here the frame's features are sorted by id once on the host, and the three kernels of
+// bbox_kernels.h (k_bbox_membership, k_bbox_overlap, k_bbox_score; shared with the store of bbox_store_kernels.hip) run over views given as a CSR.
 // All integer work except the score; the only atomics are integer adds, so a deterministic handle runs the same code.
 #include <algorithm>
 #include <cmath>
@@ -15,129 +11,13 @@
 
 #include "../../include/obvi_bbox_frontend.h"
 #include "ba_device.h"
+#include "bbox_kernels.h"
 #include "host_util.h"
 
 namespace obvi {
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWavesPerBlock = kBlock / 64;
-constexpr int kLdsFeatureLimit = 4096;      // ids of the frame kept in LDS by k_bbox_overlap: 32 KiB, five workgroups per CU
-constexpr int64_t kMaxOutputEntries = (int64_t)1 << 31;   // n_box x n_feat, n_box x n_views, n_box x n_cand each: buffers below 16 GiB, the score grid below 2^23 workgroups
-constexpr int kOverlapMaxBlocks = 1024;     // k_bbox_overlap strides over the views: a workgroup stages the list once for all of its views
-
-struct MemberBatch {
-  int64_t n_feat; int32_t n_box, words;
-  const double* pixel;        // [n_feat][2] in sorted-id order
-  const uint32_t* orig;       // position of sorted feature s in the caller's arrays
-  const double* corners;      // [n_box][4] min_x max_x min_y max_y
-  double inflation;
-};
-
-__global__ void __launch_bounds__(kBlock) k_bbox_membership(MemberBatch m, uint64_t* bits, uint8_t* in_box, uint32_t* count) {
-  const int64_t s = blockIdx.x * (int64_t)kBlock + threadIdx.x;
-  const bool live = s < m.n_feat;                                  // no early return: every lane takes part in the ballots
-  const int lane = threadIdx.x & 63;
-  const double px = live ? m.pixel[2 * s] : 0.0, py = live ? m.pixel[2 * s + 1] : 0.0;
-  const int64_t o = live ? (int64_t)m.orig[s] : 0;
-  for (int w = 0; w < m.words; ++w) {
-    const int nb = min(64, m.n_box - 64 * w);
-    uint64_t word = 0;
-    for (int j = 0; j < nb; ++j) {
-      const int64_t b = 64 * (int64_t)w + j;
-      const double* c = m.corners + 4 * b;
-      // inflateBoundingBox, then pixelInBoundingBoxClosedSet (ellipsoid_utils.h:347-361)
-      const bool inside = live && (c[0] - m.inflation <= px) && (c[2] - m.inflation <= py) && (c[1] + m.inflation >= px) && (c[3] + m.inflation >= py);
-      if (inside) word |= (uint64_t)1 << j;
-      if (in_box && live) in_box[b * m.n_feat + o] = inside ? 1 : 0;
-      const unsigned long long votes = __ballot(inside);
-      if (lane == 0 && votes) atomicAdd(&count[b], (uint32_t)__popcll(votes));
-    }
-    if (live) bits[s * m.words + w] = word;
-  }
-}
-
-struct OverlapBatch {
-  int64_t n_feat, n_views; int32_t n_box, words;
-  const uint64_t* ids;        // the frame's ids, ascending
-  const uint64_t* bits;       // [n_feat][words]
-  const uint64_t* feat_ptr; const uint64_t* view_feat;
-};
-
-// position of id in the ascending list, or -1
-__device__ inline int64_t find_id(const uint64_t* list, int64_t n, uint64_t id) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (list[mid] < id) lo = mid + 1; else hi = mid;
-  }
-  return (lo < n && list[lo] == id) ? lo : -1;
-}
-
-template <bool kLds>
-__global__ void __launch_bounds__(kBlock) k_bbox_overlap(OverlapBatch o, uint32_t* overlap) {
-  __shared__ uint64_t s_ids[kLds ? kLdsFeatureLimit : 1];
-  if (kLds) {
-    for (int64_t i = threadIdx.x; i < o.n_feat; i += kBlock) s_ids[i] = o.ids[i];
-    __syncthreads();
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int64_t v = blockIdx.x * (int64_t)kWavesPerBlock + wave; v < o.n_views; v += (int64_t)gridDim.x * kWavesPerBlock) {
-    const uint64_t k0 = o.feat_ptr[v], k1 = o.feat_ptr[v + 1];
-    for (int w = 0; w < o.words; ++w) {
-      const int nb = min(64, o.n_box - 64 * w);
-      uint32_t acc = 0;                                             // lane j: the count of box 64 w + j
-      for (uint64_t base = k0; base < k1; base += 64) {
-        const uint64_t k = base + lane;
-        uint64_t word = 0;
-        if (k < k1) {
-          const uint64_t id = o.view_feat[k];
-          int64_t at;
-          if (kLds) at = find_id(s_ids, o.n_feat, id); else at = find_id(o.ids, o.n_feat, id);
-          if (at >= 0) word = o.bits[at * o.words + w];
-        }
-        for (int j = 0; j < nb; ++j) {
-          const uint32_t c = (uint32_t)__popcll(__ballot((word >> j) & 1));
-          if (lane == j) acc += c;
-        }
-      }
-      if (lane < nb) overlap[(64 * (int64_t)w + lane) * o.n_views + v] = acc;
-    }
-  }
-}
-
-struct ScoreBatch {
-  int64_t n_box, n_cand, n_views;
-  const int32_t* box_label; const int32_t* cand_label;
-  const uint64_t* view_ptr; const uint64_t* feat_ptr;
-  const uint32_t* overlap; const uint32_t* count;
-  double min_overlap;
-};
-
-__global__ void __launch_bounds__(kBlock) k_bbox_score(ScoreBatch s, uint8_t* is_match, double* score) {
-  const int64_t t = blockIdx.x * (int64_t)kBlock + threadIdx.x;
-  if (t >= s.n_box * s.n_cand) return;
-  const int64_t b = t / s.n_cand, c = t % s.n_cand;
-  uint8_t match = 0;
-  double value = 0.0;
-  if (s.box_label[b] == s.cand_label[c]) {
-    const uint64_t v0 = s.view_ptr[c], v1 = s.view_ptr[c + 1];
-    const uint64_t in_box = s.count[b];
-    uint32_t best = 0;
-    double sum = 0.0;
-    for (uint64_t v = v0; v < v1; ++v) {
-      const uint32_t n = s.overlap[b * s.n_views + (int64_t)v];
-      best = max(best, n);
-      if (n != 0) sum += (double)n / (double)(in_box + (s.feat_ptr[v + 1] - s.feat_ptr[v]) - n);   // :467-473
-    }
-    if (v1 > v0 && (double)best >= s.min_overlap) {                 // :408-411; no views: not a match (the header's first departure)
-      match = 1;
-      value = sum / (double)(v1 - v0);                              // :476
-    }
-  }
-  is_match[t] = match;
-  score[t] = value;
-}
+using namespace bbox;   // NOLINT: the kernels and their limits (bbox_kernels.h)
 
 // offsets[0] == 0, ascending, offsets[n] == total
 bool csr_ok(const uint64_t* offsets, int64_t n, int64_t total) {
@@ -205,10 +85,11 @@ int obvi_bbox_frontend_associate(obvi_ba_handle* h, int64_t n_feat, const uint64
       d_overlap.resize((size_t)(n_box * n_views));
       if (n_feat > 0) {
         d_vfeat.upload(view_feat, (size_t)n_view_feat, s);
-        OverlapBatch o{n_feat, n_views, (int32_t)n_box, words, d_ids.get(), d_bits.get(), d_fptr.get(), d_vfeat.get()};
+        OverlapBatch o{n_feat, n_views, (int32_t)n_box, words, d_ids.get(), d_bits.get()};
+        const CsrViews views{d_fptr.get(), d_vfeat.get()};
         const unsigned grid = (unsigned)std::min<int64_t>((n_views + kWavesPerBlock - 1) / kWavesPerBlock, kOverlapMaxBlocks);
-        if (n_feat <= kLdsFeatureLimit) hipLaunchKernelGGL(k_bbox_overlap<true>, dim3(grid), dim3(kBlock), 0, s, o, d_overlap.get());
-        else hipLaunchKernelGGL(k_bbox_overlap<false>, dim3(grid), dim3(kBlock), 0, s, o, d_overlap.get());
+        if (n_feat <= kLdsFeatureLimit) hipLaunchKernelGGL((k_bbox_overlap<true, CsrViews>), dim3(grid), dim3(kBlock), 0, s, o, views, d_overlap.get());
+        else hipLaunchKernelGGL((k_bbox_overlap<false, CsrViews>), dim3(grid), dim3(kBlock), 0, s, o, views, d_overlap.get());
         OBVI_HIP(hipGetLastError());
       } else {
         d_overlap.zero(s);                                          // no features in the frame: nothing to search in
@@ -219,8 +100,8 @@ int obvi_bbox_frontend_associate(obvi_ba_handle* h, int64_t n_feat, const uint64
     if (n_cand > 0 && (is_match || score)) {
       d_blabel.upload(box_label, (size_t)n_box, s); d_clabel.upload(cand_label, (size_t)n_cand, s); d_vptr.upload(view_ptr, (size_t)n_cand + 1, s);
       d_match.resize((size_t)(n_box * n_cand)); d_score.resize((size_t)(n_box * n_cand));
-      ScoreBatch sb{n_box, n_cand, n_views, d_blabel.get(), d_clabel.get(), d_vptr.get(), d_fptr.get(), d_overlap.get(), d_count.get(), prm->min_overlapping_features_for_match};
-      hipLaunchKernelGGL(k_bbox_score, dim3((unsigned)((n_box * n_cand + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, sb, d_match.get(), d_score.get());
+      ScoreBatch sb{n_box, n_cand, n_views, d_blabel.get(), d_clabel.get(), d_vptr.get(), d_overlap.get(), d_count.get(), prm->min_overlapping_features_for_match};
+      hipLaunchKernelGGL(k_bbox_score<CsrViews>, dim3((unsigned)((n_box * n_cand + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, sb, CsrViews{d_fptr.get(), d_vfeat.get()}, d_match.get(), d_score.get());
       OBVI_HIP(hipGetLastError());
       h_match.resize((size_t)(n_box * n_cand));
       d_match.download(h_match.data(), h_match.size(), s);

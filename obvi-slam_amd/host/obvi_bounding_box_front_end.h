@@ -18,10 +18,14 @@
 // order, then the pose graph's objects in ascending id; an object's views are kept in ascending (frame, camera) order, which is the order its score is summed
 // in; mergeable pending objects, their merge candidates and the pending objects that become new objects are visited in ascending id, and equal merge scores go
 // by (pending index, object id).
+// Store mode (useAppearanceStore, opt-in, before the first round): the views live in an obvi_bbox_store (include/obvi_bbox_store.h) on the device instead of
+// observed_feats_ / object_appearance_info_, which stay empty; a pending object and an object carry an owner token of the store.  The sequence, the order of the
+// views and the events are the same.
 #ifndef OBVI_HOST_BOUNDING_BOX_FRONT_END_H_
 #define OBVI_HOST_BOUNDING_BOX_FRONT_END_H_
 
 #include <obvi_bbox_frontend.h>
+#include <obvi_bbox_store.h>
 
 #include <algorithm>
 #include <climits>
@@ -32,6 +36,7 @@
 #include <optional>
 #include <set>
 #include <string>
+#include <tuple>
 #include <unordered_map>
 #include <unordered_set>
 #include <utility>
@@ -85,6 +90,7 @@ struct FeatureBasedPendingObject {                // UninitializedEllispoidInfo<
   std::string semantic_class_;
   std::vector<ObjectObservationFactor> observation_factors_;   // object_id_ unused while pending
   FrameId min_frame_id_ = 0, max_frame_id_ = 0;
+  int64_t store_owner_ = -1;                      // store mode: the owner token of its views (observed_feats_ stays empty)
 };
 struct AssociatedObjectIdentifier { bool initialized_ellipsoid_; ObjectId object_id_; };   // bounding_box_front_end.h:37-44
 enum ObjectInitializationStatus { NOT_INITIALIZED, ENOUGH_VIEWS_FOR_MERGE, SUFFICIENT_VIEWS_FOR_NEW };
@@ -164,9 +170,35 @@ class FeatureBasedBoundingBoxFrontEnd {
       };
     }
   }
+  FeatureBasedBoundingBoxFrontEnd(const FeatureBasedBoundingBoxFrontEnd&) = delete;
+  FeatureBasedBoundingBoxFrontEnd& operator=(const FeatureBasedBoundingBoxFrontEnd&) = delete;
+  ~FeatureBasedBoundingBoxFrontEnd() {
+#if !defined(OBVI_TESTS_ORACLE_ABI_SHIM_H_) && !defined(OBVI_TESTS_LOCKSTEP_SHIM_H_)
+    obvi_bbox_store_destroy(store_);             // before the handle, which the caller destroys after this object
+#endif
+  }
+
+  // Store mode: from now on the views are kept in a store on the handle's device.  To be called before the first round and before
+  // initializeWithLongTermMapFrontEndData; false when it comes later or the store cannot be made.
+  bool useAppearanceStore(const obvi_bbox_store_options& options) {
+#if !defined(OBVI_TESTS_ORACLE_ABI_SHIM_H_) && !defined(OBVI_TESTS_LOCKSTEP_SHIM_H_)
+    if (store_ || !uninitialized_object_info_.empty() || !object_appearance_info_.empty()) return false;
+    const int rc = obvi_bbox_store_create(handle_, &options, &store_);
+    if (rc != 0) std::cerr << "obvi_bbox_store_create failed: status " << rc << " " << obvi_ba_last_error(handle_) << std::endl;
+    return rc == 0;
+#else
+    (void)options;
+    std::cerr << "the appearance store is served by libobvi_ba.so only" << std::endl;
+    return false;
+#endif
+  }
+  bool usesAppearanceStore() const { return store_ != nullptr; }
 
   // objects a long-term map brought: they are candidates once they have views (initializeWithLongTermMapFrontEndData: the map carries no appearance data)
-  void initializeWithLongTermMapFrontEndData(const std::vector<ObjectId>& object_ids) { for (ObjectId o : object_ids) object_appearance_info_[o]; }
+  void initializeWithLongTermMapFrontEndData(const std::vector<ObjectId>& object_ids) {
+    if (store_) { for (ObjectId o : object_ids) if (!object_owner_.count(o)) object_owner_[o] = newStoreOwner(); return; }
+    for (ObjectId o : object_ids) object_appearance_info_[o];
+  }
 
   bool addBoundingBoxObservations(const FrameId& frame_id, const CameraId& camera_id, const std::vector<RawBoundingBox>& bounding_boxes, const FeatureBasedContextInfo& bb_context) {
     last_assignments_.clear();
@@ -181,6 +213,7 @@ class FeatureBasedBoundingBoxFrontEnd {
     std::vector<AssociatedObjectIdentifier> assignments;
     if (!getBoundingBoxAssignments(boxes, bb_context, &features_in_bb, &assignments)) return false;
     last_assignments_ = assignments;
+    std::vector<int64_t> box_owner(assignments.size(), -1);                                     // store mode: whose view each box becomes
 
     for (size_t i = 0; i < assignments.size(); ++i) {                                          // bounding_box_front_end.h:137-202
       const RawBoundingBox& bb = boxes[i];
@@ -189,7 +222,8 @@ class FeatureBasedBoundingBoxFrontEnd {
       const BbCorners corners = cornerLocationsPairToVector(bb.pixel_corner_locations_);
       if (assoc.initialized_ellipsoid_) {
         addObservationForObject(frame_id, camera_id, assoc.object_id_, corners, bb_cov, bb.detection_confidence_);
-        object_appearance_info_[assoc.object_id_][{frame_id, camera_id}] = features_in_bb[i];
+        if (store_) box_owner[i] = object_owner_.at(assoc.object_id_);
+        else object_appearance_info_[assoc.object_id_][{frame_id, camera_id}] = features_in_bb[i];
         continue;
       }
       ObjectObservationFactor factor;
@@ -199,7 +233,8 @@ class FeatureBasedBoundingBoxFrontEnd {
         FeatureBasedPendingObject fresh;
         fresh.semantic_class_ = bb.semantic_class_;
         fresh.observation_factors_.push_back(factor);
-        fresh.observed_feats_[{frame_id, camera_id}] = features_in_bb[i];
+        if (store_) box_owner[i] = fresh.store_owner_ = newStoreOwner();
+        else fresh.observed_feats_[{frame_id, camera_id}] = features_in_bb[i];
         fresh.max_confidence_ = bb.detection_confidence_;
         fresh.min_frame_id_ = fresh.max_frame_id_ = frame_id;
         RawEllipsoid est;
@@ -211,13 +246,16 @@ class FeatureBasedBoundingBoxFrontEnd {
         p.max_frame_id_ = std::max(frame_id, p.max_frame_id_);
         p.min_frame_id_ = std::min(frame_id, p.min_frame_id_);
         p.max_confidence_ = std::max(p.max_confidence_, bb.detection_confidence_);
-        p.observed_feats_[{frame_id, camera_id}] = features_in_bb[i];
+        if (store_) box_owner[i] = p.store_owner_;
+        else p.observed_feats_[{frame_id, camera_id}] = features_in_bb[i];
         if (!p.object_estimate_.has_value()) {
           RawEllipsoid est;
           if (generateSingleViewEllipsoidEstimate(pose_graph_, frame_id, camera_id, bb.semantic_class_, corners, est)) p.object_estimate_ = est;
         }
       }
     }
+
+    if (store_ && !commitStoreRound(frame_id, camera_id, box_owner)) return false;              // one commit carries the owners of all boxes
 
     if (!setupInitialEstimateGeneration(assignments, frame_id, camera_id)) return false;
     std::vector<ObjectId> added_pending_object_indices;
@@ -238,7 +276,8 @@ class FeatureBasedBoundingBoxFrontEnd {
       const FeatureBasedPendingObject info = uninitialized_object_info_[add_obj.first];
       const ObjectId new_obj_id = pose_graph_->addNewEllipsoid(add_obj.second, info.semantic_class_);
       events_.push_back("new_object " + std::to_string(add_obj.first) + " " + std::to_string(new_obj_id));
-      object_appearance_info_[new_obj_id] = info.observed_feats_;
+      if (store_) object_owner_[new_obj_id] = info.store_owner_;                               // the token moves to the object: no store call
+      else object_appearance_info_[new_obj_id] = info.observed_feats_;
       for (const ObjectObservationFactor& f : info.observation_factors_)
         addObservationForObject(f.frame_id_, f.camera_id_, new_obj_id, f.bounding_box_corners_, f.bounding_box_corners_covariance_, f.detection_confidence_);
       added_pending_object_indices.push_back(add_obj.first);
@@ -246,17 +285,66 @@ class FeatureBasedBoundingBoxFrontEnd {
     erasePending(added_pending_object_indices);
     erasePending(mergeExistingPendingObjects());
     cleanupBbAssociationRound(frame_id);
-    return true;
+    return !store_failed_;
   }
 
   const std::vector<FeatureBasedPendingObject>& pendingObjects() const { return uninitialized_object_info_; }
   const std::map<ObjectId, ObservedFeats>& objectAppearanceInfo() const { return object_appearance_info_; }
   const std::vector<AssociatedObjectIdentifier>& lastAssignments() const { return last_assignments_; }
+  // store mode: the owner tokens of the objects, an owner's views as (frame, camera, number of ids) in (frame, camera) order -- the host directory's answer, no
+  // device work --, and the store's counters
+  const std::map<ObjectId, int64_t>& objectStoreOwners() const { return object_owner_; }
+  std::vector<std::tuple<FrameId, CameraId, size_t>> storedViewSizes(int64_t owner) const {
+    std::vector<std::tuple<FrameId, CameraId, size_t>> out;
+#if !defined(OBVI_TESTS_ORACLE_ABI_SHIM_H_) && !defined(OBVI_TESTS_LOCKSTEP_SHIM_H_)
+    int64_t n_views = 0;
+    if (!store_ || obvi_bbox_store_views(store_, owner, &n_views, nullptr, nullptr, nullptr, nullptr, nullptr) != 0) return out;
+    std::vector<uint64_t> frame((size_t)n_views), camera((size_t)n_views), feat_ptr((size_t)n_views + 1);
+    if (obvi_bbox_store_views(store_, owner, nullptr, nullptr, frame.data(), camera.data(), feat_ptr.data(), nullptr) != 0) return out;
+    for (int64_t k = 0; k < n_views; ++k) out.emplace_back((FrameId)frame[k], (CameraId)camera[k], (size_t)(feat_ptr[k + 1] - feat_ptr[k]));
+#else
+    (void)owner;
+#endif
+    return out;
+  }
+  bool appearanceStoreStats(obvi_bbox_store_stats* stats) const {
+#if !defined(OBVI_TESTS_ORACLE_ABI_SHIM_H_) && !defined(OBVI_TESTS_LOCKSTEP_SHIM_H_)
+    return store_ && obvi_bbox_store_get_stats(store_, stats) == 0;
+#else
+    (void)stats;
+    return false;
+#endif
+  }
   // what happened, in order: "open <pending>", "merge <pending> <object>", "new_object <pending> <object>", "discard <n>", "views_dropped <n>"
   std::vector<std::string> takeEvents() { std::vector<std::string> e; e.swap(events_); return e; }
 
  private:
   int32_t labelOf(const std::string& semantic_class) { return label_ids_.emplace(semantic_class, (int32_t)label_ids_.size()).first->second; }
+
+  // ---- store mode: the calls on the store.  A failure is reported on stderr and fails the round (store_failed_).
+  bool storeCall(int rc, const char* what) {
+    if (rc == 0) return true;
+#if !defined(OBVI_TESTS_ORACLE_ABI_SHIM_H_) && !defined(OBVI_TESTS_LOCKSTEP_SHIM_H_)
+    std::cerr << what << " failed: status " << rc << " " << obvi_ba_last_error(handle_) << std::endl;
+#endif
+    store_failed_ = true;
+    return false;
+  }
+  int64_t newStoreOwner() {
+    int64_t owner = -1;
+#if !defined(OBVI_TESTS_ORACLE_ABI_SHIM_H_) && !defined(OBVI_TESTS_LOCKSTEP_SHIM_H_)
+    storeCall(obvi_bbox_store_new_owners(store_, 1, &owner), "obvi_bbox_store_new_owners");
+#endif
+    return owner;
+  }
+  bool commitStoreRound(const FrameId& frame_id, const CameraId& camera_id, const std::vector<int64_t>& box_owner) {
+#if !defined(OBVI_TESTS_ORACLE_ABI_SHIM_H_) && !defined(OBVI_TESTS_LOCKSTEP_SHIM_H_)
+    return !store_failed_ && storeCall(obvi_bbox_store_commit(store_, (uint64_t)frame_id, (uint64_t)camera_id, (int64_t)box_owner.size(), box_owner.data()), "obvi_bbox_store_commit");
+#else
+    (void)frame_id; (void)camera_id; (void)box_owner;
+    return false;
+#endif
+  }
 
   // the device round plus the assignment, in place of :355-490
   bool getBoundingBoxAssignments(const std::vector<RawBoundingBox>& boxes, const FeatureBasedContextInfo& context, std::vector<std::vector<FeatureId>>* features_in_bb,
@@ -268,6 +356,7 @@ class FeatureBasedBoundingBoxFrontEnd {
     for (int64_t i = 0; i < n_feat; ++i) { feat_id[i] = context.observed_features_[i].first; feat_pixel[2 * i] = context.observed_features_[i].second[0]; feat_pixel[2 * i + 1] = context.observed_features_[i].second[1]; }
     std::vector<int32_t> box_label((size_t)n_box), cand_label;
     for (int64_t b = 0; b < n_box; ++b) { const BbCorners c = cornerLocationsPairToVector(boxes[b].pixel_corner_locations_); std::copy(c.begin(), c.end(), corners.begin() + 4 * b); box_label[b] = labelOf(boxes[b].semantic_class_); }
+    if (store_) return getStoreAssignments(n_feat, feat_id, feat_pixel, n_box, corners, box_label, features_in_bb, assignments);
     std::vector<uint64_t> view_ptr{0}, feat_ptr{0}, view_feat;
     std::vector<ObjectId> cand_object;                                                         // of the initialised candidates
     auto add_views = [&](const ObservedFeats& views) {
@@ -311,6 +400,45 @@ class FeatureBasedBoundingBoxFrontEnd {
     return false;
 #endif
   }
+
+#if !defined(OBVI_TESTS_ORACLE_ABI_SHIM_H_) && !defined(OBVI_TESTS_LOCKSTEP_SHIM_H_)
+  // store mode: the same round over the stored views of the candidates' owners; the host needs neither the views nor, afterwards, the ids inside the boxes
+  bool getStoreAssignments(int64_t n_feat, const std::vector<uint64_t>& feat_id, const std::vector<double>& feat_pixel, int64_t n_box, const std::vector<double>& corners,
+                           const std::vector<int32_t>& box_label, std::vector<std::vector<FeatureId>>* features_in_bb, std::vector<AssociatedObjectIdentifier>* assignments) {
+    std::vector<int32_t> cand_label;
+    std::vector<int64_t> cand_owner;
+    std::vector<ObjectId> cand_object;                                                         // of the initialised candidates
+    const int64_t n_pending = (int64_t)uninitialized_object_info_.size();
+    for (const FeatureBasedPendingObject& p : uninitialized_object_info_) { cand_label.push_back(labelOf(p.semantic_class_)); cand_owner.push_back(p.store_owner_); }
+    std::unordered_map<ObjectId, std::pair<std::string, RawEllipsoid>> object_estimates;
+    pose_graph_->getObjectEstimates(object_estimates);
+    std::map<ObjectId, std::string> objects;
+    for (const auto& o : object_estimates) objects[o.first] = o.second.first;
+    for (const auto& o : objects) {
+      const auto owner = object_owner_.find(o.first);
+      if (owner == object_owner_.end()) continue;                                               // as in the host path: an object without appearance info is no candidate
+      cand_label.push_back(labelOf(o.second)); cand_object.push_back(o.first); cand_owner.push_back(owner->second);
+    }
+    const int64_t n_cand = (int64_t)cand_label.size();
+    std::vector<uint8_t> is_match((size_t)(n_box * n_cand));
+    std::vector<double> score((size_t)(n_box * n_cand));
+    const obvi_bbox_frontend_params prm{association_params_.bounding_box_inflation_size_, association_params_.min_overlapping_features_for_match_};
+    if (!storeCall(obvi_bbox_store_associate(store_, n_feat, feat_id.data(), feat_pixel.data(), n_box, corners.data(), box_label.data(), n_cand, cand_owner.data(), cand_label.data(), &prm,
+                                             nullptr, nullptr, nullptr, is_match.data(), score.data()), "obvi_bbox_store_associate")) return false;
+    std::vector<int64_t> assigned((size_t)n_box);
+    std::vector<uint8_t> is_new((size_t)n_box);
+    const int rc = obvi_bbox_frontend_assign(n_box, n_cand, n_pending, is_match.data(), score.data(), assigned.data(), is_new.data());
+    if (rc != 0) { std::cerr << "obvi_bbox_frontend_assign failed: status " << rc << std::endl; return false; }
+    features_in_bb->assign((size_t)n_box, {});                                                  // stays empty: the commit cuts the views out of the round on the device
+    assignments->clear();
+    for (int64_t b = 0; b < n_box; ++b) {
+      if (is_new[b]) { assignments->push_back({false, (ObjectId)assigned[b]}); events_.push_back("open " + std::to_string(assigned[b])); }
+      else if (assigned[b] < n_pending) assignments->push_back({false, (ObjectId)assigned[b]});
+      else assignments->push_back({true, cand_object[(size_t)(assigned[b] - n_pending)]});
+    }
+    return true;
+  }
+#endif
 
   void addObservationForObject(const FrameId& frame_id, const CameraId& camera_id, const ObjectId& object_id, const BbCorners& corners, const Covariance<4>& cov, const double& confidence) {
     ObjectObservationFactor f;                                                                  // bounding_box_front_end.h:563-577
@@ -400,15 +528,23 @@ class FeatureBasedBoundingBoxFrontEnd {
 
   std::vector<ObjectId> mergePending(const std::vector<std::pair<ObjectId, ObjectId>>& to_merge) {   // bounding_box_front_end.h:438-468
     std::vector<ObjectId> merged;
+    std::vector<int64_t> merge_from, merge_into;                                                // store mode: one merge call for the whole list
     for (const auto& m : to_merge) {
       const FeatureBasedPendingObject info = uninitialized_object_info_[m.first];
       for (const ObjectObservationFactor& f : info.observation_factors_)
         addObservationForObject(f.frame_id_, f.camera_id_, m.second, f.bounding_box_corners_, f.bounding_box_corners_covariance_, f.detection_confidence_);
-      ObservedFeats& into = object_appearance_info_.at(m.second);                               // mergeObjectAssociationInfo :244-273
-      for (const auto& v : info.observed_feats_) into[v.first] = v.second;
+      if (store_) {
+        merge_from.push_back(info.store_owner_); merge_into.push_back(object_owner_.at(m.second));
+      } else {
+        ObservedFeats& into = object_appearance_info_.at(m.second);                             // mergeObjectAssociationInfo :244-273
+        for (const auto& v : info.observed_feats_) into[v.first] = v.second;
+      }
       events_.push_back("merge " + std::to_string(m.first) + " " + std::to_string(m.second));
       merged.push_back(m.first);
     }
+#if !defined(OBVI_TESTS_ORACLE_ABI_SHIM_H_) && !defined(OBVI_TESTS_LOCKSTEP_SHIM_H_)
+    if (store_ && !merge_from.empty()) storeCall(obvi_bbox_store_merge(store_, (int64_t)merge_from.size(), merge_from.data(), merge_into.data()), "obvi_bbox_store_merge");
+#endif
     return merged;
   }
 
@@ -433,6 +569,17 @@ class FeatureBasedBoundingBoxFrontEnd {
       for (const FeatureBasedPendingObject& p : uninitialized_object_info_) if (frame_id <= p.max_frame_id_ + association_params_.discard_candidate_after_num_frames_) keep.push_back(p);
     if (keep.size() != uninitialized_object_info_.size()) events_.push_back("discard " + std::to_string(uninitialized_object_info_.size() - keep.size()));
     size_t dropped = 0;
+#if !defined(OBVI_TESTS_ORACLE_ABI_SHIM_H_) && !defined(OBVI_TESTS_LOCKSTEP_SHIM_H_)
+    if (store_) {                                                                               // the discarded owners go, then the window over everything left
+      std::set<int64_t> kept;
+      for (const FeatureBasedPendingObject& p : keep) kept.insert(p.store_owner_);
+      std::vector<int64_t> discarded;
+      for (const FeatureBasedPendingObject& p : uninitialized_object_info_) if (!kept.count(p.store_owner_)) discarded.push_back(p.store_owner_);
+      if (!discarded.empty()) storeCall(obvi_bbox_store_release(store_, (int64_t)discarded.size(), discarded.data()), "obvi_bbox_store_release");
+      int64_t n = 0;
+      if (storeCall(obvi_bbox_store_apply_window(store_, (uint64_t)frame_id, (uint64_t)association_params_.feature_validity_window_, &n), "obvi_bbox_store_apply_window")) dropped = (size_t)n;
+    }
+#endif
     auto apply_window = [&](ObservedFeats& views) {
       for (auto it = views.begin(); it != views.end();)
         if (it->first.first + association_params_.feature_validity_window_ < frame_id) { it = views.erase(it); ++dropped; } else ++it;
@@ -454,6 +601,9 @@ class FeatureBasedBoundingBoxFrontEnd {
   std::map<std::string, int32_t> label_ids_;
   std::vector<AssociatedObjectIdentifier> last_assignments_;
   std::vector<std::string> events_;
+  obvi_bbox_store* store_ = nullptr;                // store mode
+  std::map<ObjectId, int64_t> object_owner_;       // store mode: the objects with appearance data and their owner tokens
+  bool store_failed_ = false;
 };
 
 }  // namespace vslam_types_refactor

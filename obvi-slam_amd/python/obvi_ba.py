@@ -404,6 +404,124 @@ def bbox_assign(is_match, score, n_pending, library=None, prefix="obvi_"):
     return assigned, is_new
 
 
+class BboxStoreOptions(C.Structure):
+    """obvi_bbox_store_options (include/obvi_bbox_store.h); 0: the library's default."""
+    _fields_ = [("initial_pool_ids", C.c_int64), ("compact_min_dead_ids", C.c_int64)]
+
+
+class BboxStoreStatsC(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("owners", "views", "live_ids", "dead_ids", "pool_capacity_ids", "pool_growths", "compactions", "replaced_views", "last_round_upload_bytes")]
+
+
+BboxStoreStats = collections.namedtuple("BboxStoreStats", [k for k, _ in BboxStoreStatsC._fields_])
+
+
+class BboxStore:
+    """The appearance store of the bounding-box association (include/obvi_bbox_store.h): the views of BundleAdjuster.bbox_associate kept on the device between
+    rounds.  It belongs to the BundleAdjuster it was made from and must be closed before it."""
+
+    def __init__(self, ba, initial_pool_ids=0, compact_min_dead_ids=0):
+        self._ba = ba
+        self._s = C.c_void_p()
+        opt = BboxStoreOptions(int(initial_pool_ids), int(compact_min_dead_ids))
+        ba._check(self._fn("create")(ba._h, C.byref(opt), C.byref(self._s)), "bbox_store_create")
+
+    def _fn(self, name):
+        return self._ba._entry("bbox_store_" + name, "obvi_bbox_store.h")
+
+    def _check(self, rc, what):
+        self._ba._check(rc, "bbox_store_" + what)
+
+    def close(self):
+        if self._s:
+            f = self._fn("destroy")
+            f.restype = None
+            f(self._s)
+            self._s = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def new_owners(self, n):
+        out = np.zeros(int(n), np.int64)
+        self._check(self._fn("new_owners")(self._s, C.c_int64(int(n)), _ptr(out, C.c_int64)), "new_owners")
+        return out
+
+    def put_views(self, owner, frame, camera, views):
+        """views: one list of feature ids per (owner[k], frame[k], camera[k])."""
+        ow = np.ascontiguousarray(owner, dtype=np.int64).ravel(); fr = np.ascontiguousarray(frame, dtype=np.uint64).ravel(); ca = np.ascontiguousarray(camera, dtype=np.uint64).ravel()
+        if not (len(ow) == len(fr) == len(ca) == len(views)):
+            raise ObviError("put_views: array lengths disagree")
+        fp = np.concatenate([[0], np.cumsum([len(v) for v in views])]).astype(np.uint64)
+        vf = np.array([i for v in views for i in v], dtype=np.uint64)
+        self._check(self._fn("put_views")(self._s, C.c_int64(len(ow)), _ptr(ow, C.c_int64), _ptr(fr, C.c_uint64), _ptr(ca, C.c_uint64), _ptr(fp, C.c_uint64), _ptr(vf, C.c_uint64)), "put_views")
+
+    def associate(self, feat_id, feat_pixel, box_corners, box_label, cand_owner, cand_label, params=None, want_in_box=True, n_views=None):
+        """BundleAdjuster.bbox_associate over the stored views of cand_owner: (in_box, feats_in_box, overlap, is_match, score); in_box is None when not wanted.
+        n_views: the candidates' views in all, for a caller that knows; otherwise the store's directory is asked, owner by owner."""
+        fi = np.ascontiguousarray(feat_id, dtype=np.uint64).ravel(); fx = _f64(feat_pixel, (-1, 2))
+        bc = _f64(box_corners, (-1, 4)); bl = np.ascontiguousarray(box_label, dtype=np.int32).ravel()
+        co = np.ascontiguousarray(cand_owner, dtype=np.int64).ravel(); cl = np.ascontiguousarray(cand_label, dtype=np.int32).ravel()
+        if len(fx) != len(fi) or len(bl) != len(bc) or len(co) != len(cl):
+            raise ObviError("BboxStore.associate: array lengths disagree")
+        prm = params or BboxFrontendParams()
+        nf, nb, nc = len(fi), len(bc), len(cl)
+        if n_views is not None:
+            nv = int(n_views)
+        else:
+            nv = sum(self.view_sizes(int(o))[0] for o in co) if len(set(co.tolist())) == nc else 0   # a refusal is the library's to make
+        in_box = np.zeros((nb, nf), np.uint8) if want_in_box else None
+        count, overlap = np.zeros(nb, np.uint32), np.zeros((nb, nv), np.uint32)
+        match, score = np.zeros((nb, nc), np.uint8), np.full((nb, nc), np.nan)
+        self._check(self._fn("associate")(self._s, C.c_int64(nf), _ptr(fi, C.c_uint64), _ptr(fx, C.c_double), C.c_int64(nb), _ptr(bc, C.c_double), _ptr(bl, C.c_int32), C.c_int64(nc),
+                                          _ptr(co, C.c_int64), _ptr(cl, C.c_int32), C.byref(prm), _ptr(in_box, C.c_uint8), _ptr(count, C.c_uint32), _ptr(overlap, C.c_uint32),
+                                          _ptr(match, C.c_uint8), _ptr(score, C.c_double)), "associate")
+        return in_box, count, overlap, match, score
+
+    def commit(self, frame_id, camera_id, box_owner):
+        bo = np.ascontiguousarray(box_owner, dtype=np.int64).ravel()
+        self._check(self._fn("commit")(self._s, C.c_uint64(int(frame_id)), C.c_uint64(int(camera_id)), C.c_int64(len(bo)), _ptr(bo, C.c_int64)), "commit")
+
+    def merge(self, from_owner, into_owner):
+        fr = np.ascontiguousarray(from_owner, dtype=np.int64).ravel(); to = np.ascontiguousarray(into_owner, dtype=np.int64).ravel()
+        if len(fr) != len(to):
+            raise ObviError("BboxStore.merge: array lengths disagree")
+        self._check(self._fn("merge")(self._s, C.c_int64(len(fr)), _ptr(fr, C.c_int64), _ptr(to, C.c_int64)), "merge")
+
+    def release(self, owner):
+        ow = np.ascontiguousarray(owner, dtype=np.int64).ravel()
+        self._check(self._fn("release")(self._s, C.c_int64(len(ow)), _ptr(ow, C.c_int64)), "release")
+
+    def apply_window(self, frame_id, window):
+        dropped = C.c_int64(0)
+        self._check(self._fn("apply_window")(self._s, C.c_uint64(int(frame_id)), C.c_uint64(int(window)), C.byref(dropped)), "apply_window")
+        return dropped.value
+
+    def compact(self):
+        self._check(self._fn("compact")(self._s), "compact")
+
+    def view_sizes(self, owner):
+        """(number of views, number of ids) of an owner: the host directory's answer, no device work."""
+        nv, ni = C.c_int64(0), C.c_int64(0)
+        self._check(self._fn("views")(self._s, C.c_int64(int(owner)), C.byref(nv), C.byref(ni), None, None, None, None), "views")
+        return nv.value, ni.value
+
+    def views(self, owner):
+        """The owner's views in (frame, camera) order: [((frame, camera), [ids])]."""
+        nv, ni = self.view_sizes(owner)
+        fr, ca, fp, vf = np.zeros(nv, np.uint64), np.zeros(nv, np.uint64), np.zeros(nv + 1, np.uint64), np.zeros(ni, np.uint64)
+        self._check(self._fn("views")(self._s, C.c_int64(int(owner)), None, None, _ptr(fr, C.c_uint64), _ptr(ca, C.c_uint64), _ptr(fp, C.c_uint64), _ptr(vf, C.c_uint64)), "views")
+        return [((int(fr[k]), int(ca[k])), [int(i) for i in vf[int(fp[k]):int(fp[k + 1])]]) for k in range(nv)]
+
+    def stats(self):
+        st = BboxStoreStatsC()
+        self._check(self._fn("get_stats")(self._s, C.byref(st)), "get_stats")
+        return BboxStoreStats(*[getattr(st, k) for k in BboxStoreStats._fields])
+
+
 class BundleAdjuster:
     """One handle == one GPU == one HIP stream (include/obvi_ba.h)."""
 
