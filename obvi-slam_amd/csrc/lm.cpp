@@ -370,6 +370,9 @@ int obvi_ba_solve(obvi_ba_handle* h, const obvi_solver_params* prm, obvi_summary
     it.step_is_valid = (finite && model_cost_change > 0.0) ? 1 : 0;
     if (!it.step_is_valid) {
       if (++num_invalid >= kMaxInvalid) {
+        // the record of the step that ends the solve: not counted, but a record of an invalid step like the others (the current cost -- final_cost is the
+        // minimum over the records --, the gradient norms and the radius it was tried with)
+        it.cost = x_cost + fixed_cost; it.gradient_max_norm = prev.gradient_max_norm; it.gradient_norm = prev.gradient_norm; it.trust_region_radius = radius;
         h->iterations.push_back(it);
         finish(OBVI_FAILURE, "Number of consecutive invalid steps more than Solver::Options::max_num_consecutive_invalid_steps");
         break;

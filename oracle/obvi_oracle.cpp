@@ -144,6 +144,9 @@ struct OracleProblem {
   obvi_allreduce_fn allreduce = nullptr; void* allreduce_user = nullptr;
   // last solve
   std::vector<obvi_iteration_summary> iterations;
+  // test hook (oracle_ba_debug_keep_visited): poses then points of every candidate the last solve evaluated, accepted or not
+  bool keep_visited = false;
+  std::vector<std::vector<double>> visited;
   std::string err;
 };
 
@@ -1205,6 +1208,7 @@ int oracle_ba_solve(oracle_handle* h, const obvi_solver_params* prm, obvi_summar
   const double t_start = now_s();
   std::memset(sum, 0, sizeof(*sum));
   pb.iterations.clear();
+  pb.visited.clear();
   double t_lin = 0, t_res = 0, t_solve = 0;
 
   Reduced rd; build_reduced(pb, &rd);
@@ -1423,6 +1427,9 @@ int oracle_ba_solve(oracle_handle* h, const obvi_solver_params* prm, obvi_summar
     if (!it.step_is_valid) {
       // HandleInvalidStep
       if (++num_invalid >= kMaxInvalid) {
+        // the record of the step that ends the solve: not counted, but a record of an invalid step like the others (the current cost -- final_cost is the
+        // minimum over the records --, the gradient norms and the radius it was tried with)
+        it.cost = x_cost + rd.fixed_cost; it.gradient_max_norm = prev_gmax; it.gradient_norm = prev_gnorm; it.trust_region_radius = radius;
         pb.iterations.push_back(it);
         finish(OBVI_FAILURE, "Number of consecutive invalid steps more than Solver::Options::max_num_consecutive_invalid_steps");
         failed = true;
@@ -1441,6 +1448,7 @@ int oracle_ba_solve(oracle_handle* h, const obvi_solver_params* prm, obvi_summar
     for (int64_t p = 0; p < pb.P; ++p) if (rd.pose_vid[p] >= 0) for (int k = 0; k < 6; ++k) { const real d = -y_c[pose_row(rd, p) + k]; pb.poses[6 * p + k] = (double)(pb.poses[6 * p + k] + d); step_sq += d * d; }
     for (int64_t o = 0; o < pb.O; ++o) if (rd.obj_vid[o] >= 0) for (int k = 0; k < pb.od; ++k) { const real d = -y_c[obj_row(rd, o) + k]; pb.objects[pb.od * o + k] = (double)(pb.objects[pb.od * o + k] + d); if (counted_row(obj_row(rd, o))) step_sq += d * d; }
     for (int64_t l = 0; l < pb.L; ++l) if (rd.point_var[l]) for (int k = 0; k < 3; ++k) { const real d = delta_l[3 * l + k]; pb.points[3 * l + k] = (double)(pb.points[3 * l + k] + d); step_sq += d * d; }
+    if (pb.keep_visited) { pb.visited.push_back(pb.poses); pb.visited.back().insert(pb.visited.back().end(), pb.points.begin(), pb.points.end()); }
     tt = now_s();
     double cand_cost = reduced_cost(pb, rd);
     t_res += now_s() - tt;
@@ -1556,6 +1564,18 @@ int oracle_ba_select_outliers(oracle_handle* h, int32_t type, double fraction, u
     return OBVI_OK;
   }
   return OBVI_ERR_INVALID_ARGUMENT;
+}
+
+// Test hook (tests/lm_cases.py: the depths at every point a solve evaluates, of which the solve itself hands back only the best): with `on`, a solve keeps
+// the poses and points of each candidate it forms, in the order of its valid steps; get_visited returns their number and, for 0 <= k < that, copies the k-th.
+int oracle_ba_debug_keep_visited(oracle_handle* h, int32_t on) { h->pb.keep_visited = on != 0; if (!on) h->pb.visited.clear(); return OBVI_OK; }
+int oracle_ba_debug_get_visited(oracle_handle* h, int32_t k, double* poses, double* points) {
+  const int32_t n = (int32_t)h->pb.visited.size();
+  if (k >= 0 && k < n && poses && points) {
+    const std::vector<double>& v = h->pb.visited[(size_t)k];
+    std::memcpy(poses, v.data(), sizeof(double) * 6 * h->pb.P); std::memcpy(points, v.data() + 6 * h->pb.P, sizeof(double) * 3 * h->pb.L);
+  }
+  return n;
 }
 
 int oracle_ba_snapshot(oracle_handle* h) { h->pb.snap_poses = h->pb.poses; h->pb.snap_points = h->pb.points; h->pb.snap_objects = h->pb.objects; return OBVI_OK; }
